@@ -12,6 +12,7 @@ replay a segmented plan: the compute work between two collectives as graph segme
 calls issued eagerly between them (--graph-comm captures the collectives too, opt-in).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n BODIES] [--dtype fp32|fp64]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,17 +25,30 @@ skipped). Data: synthetic Sun/Earth/Mars + uniform random bodies generated on de
 (seeded). Rank 0 prints ONE JSON line; value is the whole-job body-updates/s =
 N * K / max_rank(wall).
 
+A plain run does what the headline needs and no more: set-up (multi-rank: the topology check
+and the overlap self-check that picks the schedule), one eager step that sizes the deadlines,
+the warmup, the K timed steps, and what those steps recorded on the device as they ran (the
+unit count below, the non-finite count, the engine clock, the HBM ledger). --dump-outputs DIR
+then writes the state the last timed step left, as a caller of the step would read it back:
+DIR/pos.npy and DIR/vel.npy, (N, 3), float32 for fp32 runs and float64 for fp64 runs (beyond
+60 MB in all, a fixed seeded sample of the rows). The ICs are seeded, so the same arguments
+give the same inputs in every run. Everything else below (the replay audit, the sampled
+accuracy, the conserved quantities, the phase steps, the exact-cutoff timing, the
+P-independence audit) takes passes of its own and runs only with --full; their options
+(--check-samples, --phase-steps, --exact-steps, --no-replay-audit, --no-energy, --p-audit) tune
+a --full run and do nothing without it.
+
 Audits of the timed work (outside the timed region; the run exits non-zero if one fails):
   * unit count: the sym force kernels count every unit they run on device; after the loop
     each rank must have run exactly rows x (S + D + (Np - 1) Kr) units per timed step (a split
     segment counts as its Np parts);
-  * replay: the same warmup + K steps are re-run from the same ICs on an independent
+  * replay (--full): the same warmup + K steps are re-run from the same ICs on an independent
     schedule (eager launches, one static unit per workgroup, ungated) and must give the
     same bits on every rank.
 If the gated local-first launch (--overlap auto picked 3 after its 2-step self-check) fails
 them, that is a failure of the multi-rank default: the ungated schedule is timed from the same
 ICs (config.overlap_fallback), but work_audit reports the failure and the run exits 1.
-Also outside it: the sampled accuracy of the step's own accelerations at step 0 and after
+Also outside it (--full): the sampled accuracy of the step's own accelerations at step 0 and after
 the last timed step, the relative drift of total momentum over the run, the drift of total
 energy (kinetic + exact-cutoff potential) and angular momentum (two O(N^2) passes), a few
 steps with phase events for the comm split (multi-rank: replayed from the same segmented plan
@@ -44,9 +58,9 @@ as the timed loop), and the reference's exact hard-cutoff select timed on its ow
 RCCL's INFO log, sent to a file), and refuse to report a number (error line, exit 70) when two
 ranks share a GPU, the communicator is not the job, or a single-node connection runs through a
 network transport (parallel/verify.py; recorded but not enforced in the one-GPU rehearsal,
-GRAVSIM_RCCL_RANK_HOSTS=1). After the timed run they also check P-independence: rank 0 recomputes
-2 steps from the same ICs as a 1-rank engine on its own GPU and every rank's rows must be bitwise
-equal (--p-audit).
+GRAVSIM_RCCL_RANK_HOSTS=1). After the timed run, with --full, they also check P-independence:
+rank 0 recomputes 2 steps from the same ICs as a 1-rank engine on its own GPU and every rank's
+rows must be bitwise equal (--p-audit).
 
 Clock-normalised cost: every force workgroup of the timed steps records its s_memtime (shader
 clock) and s_memrealtime (100 MHz) spans; the line reports engine_clock_ghz and
@@ -131,7 +145,42 @@ def parse(argv=None) -> argparse.Namespace:
                     help="P > 1: after the timed run, rank 0 recomputes 2 steps from the same "
                          "ICs as a 1-rank engine on its own GPU and every rank's rows must have "
                          "the same bits (auto: up to 4M bodies fp32, 1M fp64)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks and side measurements that take GPU or host passes "
+                         "of their own (sampled accuracy, conserved quantities, phase steps, "
+                         "replay audit, P-independence audit, exact-cutoff timing); the options "
+                         "that tune them apply only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step produced (pos.npy, vel.npy; "
+                         "float32 for fp32 runs, float64 for fp64) into DIR")
+    a = ap.parse_args(argv)
+    if not a.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        a.check_samples = a.phase_steps = a.exact_steps = 0
+        a.replay_audit = a.energy = False
+        a.p_audit = "off"
+    return a
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # of all dumped arrays together
+
+
+def dump_outputs(directory: str, pos, vel, fp64: bool) -> None:
+    """What a caller of the timed path receives after the last timed step: positions and
+    velocities of all bodies, in the run's own precision (the fp32 state is held exactly).
+    Past DUMP_LIMIT_BYTES a fixed seeded sample of the rows is written instead (the same rows
+    for the same --n and --dtype)."""
+    import numpy as np
+
+    dt = np.float64 if fp64 else np.float32
+    n = pos.shape[0]
+    rows = DUMP_LIMIT_BYTES // (2 * 3 * np.dtype(dt).itemsize)
+    if n > rows:
+        keep = np.sort(np.random.default_rng(20250307).choice(n, size=rows, replace=False))
+        pos, vel = pos[keep], vel[keep]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "pos.npy"), np.ascontiguousarray(pos, dtype=dt))
+    np.save(os.path.join(directory, "vel.npy"), np.ascontiguousarray(vel, dtype=dt))
 
 
 def rccl_log_setup(directory: str, rank: int) -> str | None:
@@ -478,8 +527,10 @@ def run(a, g) -> int:
     if a.check_samples > 0:
         err, bound0 = (comm.allreduce_max(dist, x) for x in sampled_error(eng, cfg,
                                                                            a.check_samples))
-    _, vel0, mass = own_state(eng)
-    p0, pscale = momentum(dist, comm, vel0, mass)
+    p0 = pscale = mass = None
+    if a.full:
+        _, vel0, mass = own_state(eng)
+        p0, pscale = momentum(dist, comm, vel0, mass)
     g.stage("energy", budget(4, 180))
     cons0 = engine_conserved(eng, dist) if a.energy else None  # exact-cutoff potential pass
 
@@ -531,9 +582,20 @@ def run(a, g) -> int:
         if overlap == 3 and os.environ.get("GRAVSIM_TEST_FAIL_GATED_AUDIT") == "1":
             failures.append("injected failure (GRAVSIM_TEST_FAIL_GATED_AUDIT, test hook)")
         bad = comm.allreduce_sum(dist, eng.nonfinite())
-        pos_t, vel_t, _ = own_state(eng)
-        p1, _ = momentum(dist, comm, vel_t, mass)
-        drift = float(np.linalg.norm(p1 - p0)) / max(pscale, 1e-300)
+        pos_t = vel_t = pos_all = drift = None
+        if a.full or a.dump_outputs:
+            # the state after the last timed step (before the phase steps move it on)
+            full_state = eng.state()
+            own = eng.layout.real_local
+            pos_all = full_state.pos
+            pos_t = pos_all[own.start:own.stop].copy()
+            vel_t = full_state.vel[own.start:own.stop].copy()
+        dump = None
+        if a.dump_outputs:  # every rank holds all positions and its own velocity rows
+            dump = (pos_all, np.concatenate(comm.allgather_object(dist, vel_t)))
+        if a.full:
+            p1, _ = momentum(dist, comm, vel_t, mass)
+            drift = float(np.linalg.norm(p1 - p0)) / max(pscale, 1e-300)
         err_end = bound_end = None
         if a.check_samples > 0:
             err_end, bound_end = (comm.allreduce_max(dist, x) for x in sampled_error(
@@ -588,7 +650,7 @@ def run(a, g) -> int:
             eng.set_schedule((2 if a.graph_comm else 1) if a.graph else 0, cap)
             eng.set_overlap(overlap)
         return dict(extra=extra, wall=wall, clk=clk, ginfo=ginfo, mem=mem, hbm_max=hbm_max,
-                    failures=failures,
+                    failures=failures, dump=dump,
                     units=units, bad=bad, drift=drift, err_end=err_end, bound_end=bound_end,
                     conservation=conservation, phase=phase, replay=replay)
 
@@ -614,6 +676,9 @@ def run(a, g) -> int:
     err_end, conservation, phase, replay = (res["err_end"], res["conservation"], res["phase"],
                                             res["replay"])
     bound_end = res["bound_end"]
+    if a.dump_outputs and rank == 0:
+        g.stage("dump", budget(0, 180))
+        dump_outputs(a.dump_outputs, *res["dump"], fp64=a.dtype == "fp64")
     # Engine clock over the timed steps, per rank (each GPU holds its own DVFS state): the
     # whole job's workgroup-cycles and the CUs it ran on, for clock-normalised costs
     clk = res["clk"]

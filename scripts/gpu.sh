@@ -136,7 +136,7 @@ for task in "$@"; do
       : > $out/perturb64.txt
       for t in scale bench; do
         if [ $t = scale ]; then cmd=(python -u -m pytest tests/test_gpu_scale.py -x -q -k fp64_512k --timeout 300)
-        else cmd=(python bench.py --dtype fp64 --n 524288 --steps 2 --warmup 1 --exact-steps 0 --phase-steps 0 --no-replay-audit --no-energy); fi
+        else cmd=(python bench.py --full --dtype fp64 --n 524288 --steps 2 --warmup 1 --exact-steps 0 --phase-steps 0 --no-replay-audit --no-energy); fi
         timeout -k 10 400 env GRAVSIM_NATIVE_DIR=abv/perturbed64 "${cmd[@]}" > $out/perturb64_$t.log 2>&1
         rc=$?
         echo "perturbed fp64 build, $t: rc=$rc (a gate that bites exits non-zero)" | tee -a $out/perturb64.txt

@@ -11,22 +11,22 @@ export TMPDIR=/tmp GRAVSIM_RCCL_RANK_HOSTS=1
 out=gpurun_out/tr
 run="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
 # bench.py without a launcher starts its own ranks (parallel/launch.py)
-timeout -k 10 240 python bench.py --gpus 2 --steps 3 --warmup 1 --n 65536 > $out/bench2_self.log 2>&1 \
+timeout -k 10 240 python bench.py --gpus 2 --full --steps 3 --warmup 1 --n 65536 > $out/bench2_self.log 2>&1 \
   || { tail -30 $out/bench2_self.log; exit 1; }
 grep '^{' $out/bench2_self.log
-timeout -k 10 240 $run --nproc-per-node 2 --master-port 29611 bench.py --gpus 2 --steps 3 \
+timeout -k 10 240 $run --nproc-per-node 2 --master-port 29611 bench.py --gpus 2 --full --steps 3 \
   --warmup 1 --num-bodies 65536 > $out/bench2.log 2>&1 || { tail -30 $out/bench2.log; exit 1; }
 grep '^{' $out/bench2.log
-timeout -k 10 240 $run --nproc-per-node 4 --master-port 29612 bench.py --gpus 4 --steps 2 \
+timeout -k 10 240 $run --nproc-per-node 4 --master-port 29612 bench.py --gpus 4 --full --steps 2 \
   --warmup 1 --num-bodies 131072 > $out/bench4.log 2>&1 || { tail -30 $out/bench4.log; exit 1; }
 grep '^{' $out/bench4.log
-timeout -k 10 240 $run --nproc-per-node 2 --master-port 29613 bench.py --gpus 2 --steps 2 \
+timeout -k 10 240 $run --nproc-per-node 2 --master-port 29613 bench.py --gpus 2 --full --steps 2 \
   --warmup 1 --num-bodies 65536 --strategy ring --mode split > $out/bench2_ring.log 2>&1 \
   || { tail -30 $out/bench2_ring.log; exit 1; }
 grep '^{' $out/bench2_ring.log
 # The driver's N=8 shape: bench.py --gpus 8 at the headline N = 1M, 8 ranks sharing this GPU
 # (RCCL over loopback sockets; throughput meaningless, the contract and the path are not).
-timeout -k 10 600 python bench.py --gpus 8 --steps 2 --warmup 1 --n 1048576 > $out/bench8_1m.log 2>&1 \
+timeout -k 10 600 python bench.py --gpus 8 --full --steps 2 --warmup 1 --n 1048576 > $out/bench8_1m.log 2>&1 \
   || { tail -30 $out/bench8_1m.log; exit 1; }
 grep '^{' $out/bench8_1m.log
 # CLI: 2 ranks (sym, checkpoint every 3) vs 1 rank, then a 1-rank resume of the 2-rank

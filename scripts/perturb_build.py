@@ -19,7 +19,7 @@ PERTURB = {
     "carrier": ("    c.cx[0] = row_from<1>(c.cx[0]) - tx.x;",
                 "    c.cx[0] = row_from<2>(c.cx[0]) - tx.x;"),
     # the fp64 tile's x carrier (tests/test_gpu_scale.py::test_sym_fp64_512k_bands_accel_sampled
-    # and bench.py --dtype fp64's sampled gate must fail on it)
+    # and bench.py --full --dtype fp64's sampled gate must fail on it)
     "carrier64": ("    c.cx[0] = row_from<1>(c.cx[0]) - tx;",
                   "    c.cx[0] = row_from<2>(c.cx[0]) - tx;"),
 }

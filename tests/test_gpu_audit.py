@@ -79,7 +79,8 @@ def _bench(args, env_extra=None):
 
 
 def test_bench_audit_ok_and_reports_physics(hip):
-    r, out = _bench(["--n", "65536", "--steps", "6", "--warmup", "2", "--exact-steps", "2"])
+    r, out = _bench(["--full", "--n", "65536", "--steps", "6", "--warmup", "2", "--exact-steps",
+                     "2"])
     assert r.returncode == 0, r.stderr[-3000:]
     assert out["work_audit"] == "ok"
     assert out["audit"]["replay"] == "bitwise"
@@ -99,8 +100,8 @@ def test_bench_audit_ok_and_reports_physics(hip):
 def test_bench_audit_catches_skipped_units(hip):
     """The dynamic counter starts at 64 in every force launch: 64 units per step never run.
     The step is slightly faster and wrong; bench.py must say so and exit non-zero."""
-    r, out = _bench(["--n", "65536", "--steps", "4", "--warmup", "1", "--exact-steps", "0",
-                     "--phase-steps", "0"], {"GRAVSIM_FAULT_SKIP_UNITS": "64"})
+    r, out = _bench(["--full", "--n", "65536", "--steps", "4", "--warmup", "1", "--exact-steps",
+                     "0", "--phase-steps", "0"], {"GRAVSIM_FAULT_SKIP_UNITS": "64"})
     assert r.returncode == 1, (r.returncode, r.stderr[-3000:])
     assert "work audit FAILED" in r.stderr
     assert out is not None and out["work_audit"] != "ok"
@@ -210,7 +211,7 @@ def test_bench_two_ranks_gated_audit_failure_is_reported(hip):
     test hook) is a failure of the multi-rank default: the ungated schedule is timed from the
     same ICs (config.overlap_fallback, so the line still carries a labelled number), but
     work_audit reports the gated failure and bench.py exits 1."""
-    r, out = _bench(["--gpus", "2", "--n", "65536", "--steps", "3", "--warmup", "1",
+    r, out = _bench(["--full", "--gpus", "2", "--n", "65536", "--steps", "3", "--warmup", "1",
                      "--exact-steps", "0", "--phase-steps", "0", "--check-samples", "0",
                      "--no-energy"],
                     {"GRAVSIM_RCCL_RANK_HOSTS": "1", "GRAVSIM_TEST_FAIL_GATED_AUDIT": "1"})

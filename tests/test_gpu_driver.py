@@ -150,8 +150,8 @@ def test_bench_json_contract(hip, tmp_path):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "bench.py", "--n", "65536", "--steps", "20", "--warmup",
-                        "4", "--exact-steps", "2", "--phase-steps", "2"], cwd=root,
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--n", "65536", "--steps", "20",
+                        "--warmup", "4", "--exact-steps", "2", "--phase-steps", "2"], cwd=root,
                        capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -168,3 +168,47 @@ def test_bench_json_contract(hip, tmp_path):
     assert d["config"]["graph"] == "graph" and d["config"]["graph_steps_per_launch"] == 32
     assert 0.5 < d["engine_clock_ghz"] < 3.5 and 0.1 < d["cycles_per_pair_eval"] < 0.4, d
     assert abs(d["value"] - 65536 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+
+
+def test_bench_plain_run_dumps_the_timed_state(hip, tmp_path):
+    """A plain bench.py run (no --full) times its steps, runs none of the audits that take
+    passes of their own, and --dump-outputs writes the state after the last timed step: the
+    same bits as an engine stepped warmup + alignment + K times from the same seeded ICs."""
+    import subprocess
+    import sys
+
+    from gravsim.runtime.engines import HipEngine
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, steps, warmup = 65536, 5, 3  # (odd counts: one alignment step, an eager last step)
+    r = subprocess.run([sys.executable, "bench.py", "--n", str(n), "--steps", str(steps),
+                        "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "out")],
+                       cwd=root, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["status"] == "ok"
+    assert d["ms_per_step"] > 0 and d["unit"] == "body-updates/s" and d["higher_is_better"]
+    assert abs(d["value"] - n * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    u = d["audit"]["units"]  # counted by the timed steps themselves: exactly K steps' worth
+    assert u["units_done_rank0"] == steps * u["units_per_step_rank0"]
+    c = d["config"]
+    assert d["audit"]["replay"] is None and c["conservation"] is None
+    assert c["sampled_rel_err"] is None and c["exact_cutoff_ms_per_step"] is None
+    assert "comm_ms" not in d
+    pos, vel = np.load(tmp_path / "out" / "pos.npy"), np.load(tmp_path / "out" / "vel.npy")
+    assert pos.shape == vel.shape == (n, 3) and pos.dtype == vel.dtype == np.float32
+    extra = c["warmup_align_steps"]
+    assert extra == 1
+    e = HipEngine(SimConfig(n=n, dtype="fp32", device="gpu"))
+    try:
+        e.init_ics("solar+random", e.cfg.seed)
+        e.step(warmup + extra + steps)
+        e.sync()
+        b = e.state()
+    finally:
+        e.close()
+    assert np.array_equal(pos, b.pos.astype(np.float32))
+    assert np.array_equal(vel, b.vel.astype(np.float32))
+    assert np.array_equal(pos.astype(np.float64), b.pos)  # the fp32 state is held exactly
