@@ -257,6 +257,129 @@ int accel_abs_range(const double* X4, int64_t n_real, int64_t i0, int64_t i1, do
   return 0;
 }
 
+// ---- 4th-order Hermite (Makino & Aarseth 1992) --------------------------------------------
+// Acceleration, jerk and potential of body i at (X4, V4): the arithmetic of the GPU kernel
+// (nbody_hermite.hip hinteract), chunk sums from zero in j order, added in chunk order.
+template <typename T>
+inline void accjerk_one(const T* X4, const T* V4, int64_t n_real, int64_t i, int32_t chunk,
+                        T cut2, T eps2, T a4[4], T j4[4]) {
+  const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
+  const T ui = V4[4 * i], vi = V4[4 * i + 1], wi = V4[4 * i + 2];
+  const int64_t n_chunks = (n_real + chunk - 1) / chunk;
+  T tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
+  for (int64_t c = 0; c < n_chunks; ++c) {
+    T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
+    const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
+    for (int64_t j = j0; j < j1; ++j) {
+      const T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+      const T wx = V4[4 * j] - ui, wy = V4[4 * j + 1] - vi, wz = V4[4 * j + 2] - wi;
+      const T r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
+      const T inv = (r2 >= cut2) ? rsqrt_ref(r2) : T(0);
+      const T inv2 = inv * inv;
+      const T mi = X4[4 * j + 3] * inv;
+      const T s = mi * inv2;
+      const T dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
+      const T al = dw * (T(3) * inv2);
+      ax = std::fma(s, dx, ax);
+      ay = std::fma(s, dy, ay);
+      az = std::fma(s, dz, az);
+      jx = std::fma(s, std::fma(-al, dx, wx), jx);
+      jy = std::fma(s, std::fma(-al, dy, wy), jy);
+      jz = std::fma(s, std::fma(-al, dz, wz), jz);
+      ph += mi;
+    }
+    tx += ax; ty += ay; tz += az; tp += ph;
+    sx += jx; sy += jy; sz += jz;
+  }
+  a4[0] = tx; a4[1] = ty; a4[2] = tz; a4[3] = -tp;
+  j4[0] = sx; j4[1] = sy; j4[2] = sz; j4[3] = 0;
+}
+
+template <typename T>
+int accjerk_range(const T* X4, const T* V4, int64_t n_real, int64_t i0, int64_t i1,
+                  int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4) {
+  if (chunk <= 0 || i1 < i0 || i1 > n_real) {
+    gs_set_error("cpu_accjerk: bad arguments");
+    return -1;
+  }
+#pragma omp parallel for schedule(static)
+  for (int64_t i = i0; i < i1; ++i)
+    accjerk_one<T>(X4, V4, n_real, i, chunk, cut2, eps2, acc4 + 4 * (i - i0),
+                   jerk4 + 4 * (i - i0));
+  return 0;
+}
+
+inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
+
+template <typename T>
+double hermite_first_dt(const T* A4, const T* J4, int64_t n, double eta) {
+  double dtm = INFINITY;
+#pragma omp parallel for schedule(static) reduction(min : dtm)
+  for (int64_t i = 0; i < n; ++i) {
+    const double an = norm3(A4[4 * i], A4[4 * i + 1], A4[4 * i + 2]);
+    const double jn = norm3(J4[4 * i], J4[4 * i + 1], J4[4 * i + 2]);
+    const double d = 0.5 * eta * an / jn;
+    if (jn > 0.0 && std::isfinite(d) && d < dtm) dtm = d;
+  }
+  return dtm;
+}
+
+// One step of size h in place (the GPU chain's predict / evaluate / correct arithmetic).
+// scratch: xp, vp, a1, j1 (n_real * 4 each).
+template <typename T>
+int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chunk, double hd,
+                 T cut2, T eps2, double eta, double* dt_min_out) {
+  if (chunk <= 0 || n < 1 || !(hd > 0.0) || !scratch) {
+    gs_set_error("cpu_hermite_step: bad arguments");
+    return -1;
+  }
+  T *XP = scratch, *VP = scratch + 4 * n, *A1 = scratch + 8 * n, *J1 = scratch + 12 * n;
+  const T h = (T)hd;
+  const T h2 = (h * h) / T(2), h3 = (h * h * h) / T(6);
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) {
+      const int64_t k = 4 * i + d;
+      XP[k] = X4[k] + (V4[k] * h + (A4[k] * h2 + J4[k] * h3));
+      VP[k] = V4[k] + (A4[k] * h + J4[k] * h2);
+    }
+    XP[4 * i + 3] = X4[4 * i + 3];
+    VP[4 * i + 3] = 0;
+  }
+  if (accjerk_range<T>(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
+  const T hh = h / T(2), h12 = (h * h) / T(12);
+  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
+  double dtm = INFINITY;
+#pragma omp parallel for schedule(static) reduction(min : dtm)
+  for (int64_t i = 0; i < n; ++i) {
+    double s2[3], s3[3];
+    for (int d = 0; d < 3; ++d) {
+      const int64_t k = 4 * i + d;
+      const T a0 = A4[k], j0 = J4[k], a1 = A1[k], j1 = J1[k], v = V4[k];
+      const T v1 = v + ((a0 + a1) * hh + (j0 - j1) * h12);
+      X4[k] = X4[k] + ((v + v1) * hh + (a0 - a1) * h12);
+      V4[k] = v1;
+      A4[k] = a1;
+      J4[k] = j1;
+      const double da = (double)a0 - (double)a1;
+      const double a2 = (-6.0 * da - hd * (4.0 * (double)j0 + 2.0 * (double)j1)) * ih2;
+      s3[d] = (12.0 * da + 6.0 * hd * ((double)j0 + (double)j1)) * ih3;
+      s2[d] = a2 + hd * s3[d];
+    }
+    A4[4 * i + 3] = 0;
+    J4[4 * i + 3] = 0;
+    if (eta > 0.0) {
+      const double an = norm3(A4[4 * i], A4[4 * i + 1], A4[4 * i + 2]);
+      const double jn = norm3(J4[4 * i], J4[4 * i + 1], J4[4 * i + 2]);
+      const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
+      const double d = std::sqrt(eta * (an * n2 + jn * jn) / (jn * n3 + n2 * n2));
+      if (jn > 0.0 && std::isfinite(d) && d < dtm) dtm = d;
+    }
+  }
+  if (dt_min_out) *dt_min_out = dtm;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -285,6 +408,33 @@ int gs_cpu_step_f64(const double* X4, double* Xn4, double* vel4, int64_t n_real,
 int gs_cpu_step_f32(const float* X4, float* Xn4, float* vel4, int64_t n_real, int64_t i0,
                     int64_t i1, int32_t chunk, float dt, float cut2, float eps2) {
   return step_range<float>(X4, Xn4, vel4, n_real, i0, i1, chunk, dt, cut2, eps2);
+}
+int gs_cpu_accjerk_f64(const double* X4, const double* V4, int64_t n_real, int64_t i0, int64_t i1,
+                       int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4) {
+  return accjerk_range<double>(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+}
+int gs_cpu_accjerk_f32(const float* X4, const float* V4, int64_t n_real, int64_t i0, int64_t i1,
+                       int32_t chunk, float cut2, float eps2, float* acc4, float* jerk4) {
+  return accjerk_range<float>(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+}
+double gs_cpu_hermite_first_dt_f64(const double* A4, const double* J4, int64_t n_real,
+                                   double eta) {
+  return hermite_first_dt<double>(A4, J4, n_real, eta);
+}
+double gs_cpu_hermite_first_dt_f32(const float* A4, const float* J4, int64_t n_real, double eta) {
+  return hermite_first_dt<float>(A4, J4, n_real, eta);
+}
+int gs_cpu_hermite_step_f64(double* X4, double* V4, double* A4, double* J4, double* scratch,
+                            int64_t n_real, int32_t chunk, double h, double cut2, double eps2,
+                            double eta, double* dt_min_out) {
+  return hermite_step<double>(X4, V4, A4, J4, scratch, n_real, chunk, h, cut2, eps2, eta,
+                              dt_min_out);
+}
+int gs_cpu_hermite_step_f32(float* X4, float* V4, float* A4, float* J4, float* scratch,
+                            int64_t n_real, int32_t chunk, double h, float cut2, float eps2,
+                            double eta, double* dt_min_out) {
+  return hermite_step<float>(X4, V4, A4, J4, scratch, n_real, chunk, h, cut2, eps2, eta,
+                             dt_min_out);
 }
 int gs_cpu_set_threads(int32_t n) {
 #ifdef _OPENMP

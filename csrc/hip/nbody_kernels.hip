@@ -25,31 +25,9 @@
 #include "gs_common.h"
 #include "gravsim.h"
 #include "gs_kernels.h"
+#include "gs_tile.h"
 
 namespace gs {
-
-template <typename T> struct VecT;
-template <> struct VecT<float> { using type = float __attribute__((ext_vector_type(4))); };
-template <> struct VecT<double> { using type = double __attribute__((ext_vector_type(4))); };
-template <typename T> using V4 = typename VecT<T>::type;
-
-constexpr int kBlock = kForceBlock;  // 256 = 4 waves of 64
-
-__device__ __forceinline__ float rsqrt_dev(float x) { return __builtin_amdgcn_rsqf(x); }
-
-// fp64: v_rsq_f64 seed (max relative error 5.2e-8, measured: profiles/r1_microbench_v3.jsonl)
-// + one Halley step, cubically convergent: e = 1 - x y^2, y <- y + y e (1/2 + 3/8 e).
-// (5.2e-8)^3 is far below 2^-53, so one step reaches double precision in 5 f64 ops where two
-// Newton steps need 7 (512K fp64: profiles/r1_sweep_512k_fp64_halley.log vs _newton.log).
-__device__ __forceinline__ double rsqrt_dev(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = __builtin_fma(-x * y, y, 1.0);
-  const double p = __builtin_fma(e, 0.375, 0.5);
-  return __builtin_fma(y * e, p, y);
-}
-
-__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // Force modes (template FM):
 //   FM_FAST  : r^2 + eps2 with eps2 >= a tiny overflow-safe core (set by the host), no select.
@@ -111,7 +89,6 @@ __device__ __forceinline__ void interact(T xi, T yi, T zi, T xj, T yj, T zj, T m
 // interactions, and the j scalar is broadcast by op_sel instead of SGPR-pair copies. Each
 // element sees exactly the scalar interact() arithmetic, so results are bit-identical
 // (+10 % over the compiler's own SLP packing: profiles/r1_ab_explicit_pk.jsonl).
-using f2 = float __attribute__((ext_vector_type(2)));
 
 template <int FM>
 __device__ __forceinline__ void interact_pk(f2 xi, f2 yi, f2 zi, float xj, float yj, float zj,
@@ -167,29 +144,6 @@ __device__ __forceinline__ void interact_all(IState<T, IPL>& s, const V4<T>& q, 
                      s.az[k], s.ph[k]);
 }
 
-
-// LDS tile geometry: kTileBytes per tile buffer (4 KiB = 256 fp32 / 128 fp64 bodies),
-// double-buffered. Each wave-instruction of the fill moves one 1-KiB piece.
-constexpr int kTileBytes = 4096;
-static_assert(kTileBytes % 1024 == 0, "tile must be whole 1 KiB wave pieces");
-template <typename T> struct Tile { static constexpr int kBodies = kTileBytes / sizeof(V4<T>); };
-
-// Issue the LDS-DMA fill of one tile: per round each of the 4 waves moves one 1-KiB piece
-// (64 lanes x 16 B); the LDS destination is the wave-uniform base + lane*16.
-template <typename T>
-__device__ __forceinline__ void tile_fill(const V4<T>* __restrict__ src, V4<T>* dst) {
-  constexpr int kRound = kBlock * 16;  // bytes one pass of the workgroup moves
-  static_assert(kTileBytes % kRound == 0, "tile must be whole workgroup x 1 KiB-per-wave passes");
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int r = 0; r < kTileBytes / kRound; ++r) {
-    const char* g = reinterpret_cast<const char*>(src) + r * kRound + wave * 1024 + lane * 16;
-    char* l = reinterpret_cast<char*>(dst) + r * kRound + wave * 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-  }
-}
 
 // A contiguous run of virtual chunk indices [v0, v1) over the chunk sequence
 // [c_begin, c_end) minus the skipped range [skip_begin, skip_end): chunk(v) maps back to the

@@ -151,6 +151,28 @@ int gs_cpu_step_f64(const double* X4, double* Xnext4, double* vel4, int64_t n_re
                     int64_t i1, int32_t chunk, double dt, double cut2, double eps2);
 int gs_cpu_step_f32(const float* X4, float* Xnext4, float* vel4, int64_t n_real, int64_t i0,
                     int64_t i1, int32_t chunk, float dt, float cut2, float eps2);
+// Hermite derivatives of global bodies [i0, i1) at (X4, V4 = vx, vy, vz, 0): acc4 gets
+// (ax, ay, az, phi), jerk4 (jx, jy, jz, 0), with a_i = sum mu d / r^3 and
+// j_i = sum mu (w - 3 (d.w) d / r^2) / r^3 (d = x_j - x_i, w = v_j - v_i, r^2 = |d|^2 + eps2),
+// a pair contributing zero to all when r^2 < cut2; canonical chunk order, OpenMP over i.
+int gs_cpu_accjerk_f64(const double* X4, const double* V4, int64_t n_real, int64_t i0, int64_t i1,
+                       int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4);
+int gs_cpu_accjerk_f32(const float* X4, const float* V4, int64_t n_real, int64_t i0, int64_t i1,
+                       int32_t chunk, float cut2, float eps2, float* acc4, float* jerk4);
+// One 4th-order Hermite step of size h on the n_real bodies, in place: predict, evaluate at the
+// predicted state, correct; A4 / J4 carry the derivatives from step to step (scratch: 4 arrays
+// of n_real * 4). *dt_min_out (if given and eta > 0) gets min_i of Aarseth's criterion
+// (+inf when no body takes part).
+// The first adaptive step of a run: (eta / 2) min_i |a_i| / |j_i| over the bodies with |j| > 0
+// and a finite ratio (+inf when none is left). A4 / J4: n_real rows of 4.
+double gs_cpu_hermite_first_dt_f64(const double* A4, const double* J4, int64_t n_real, double eta);
+double gs_cpu_hermite_first_dt_f32(const float* A4, const float* J4, int64_t n_real, double eta);
+int gs_cpu_hermite_step_f64(double* X4, double* V4, double* A4, double* J4, double* scratch,
+                            int64_t n_real, int32_t chunk, double h, double cut2, double eps2,
+                            double eta, double* dt_min_out);
+int gs_cpu_hermite_step_f32(float* X4, float* V4, float* A4, float* J4, float* scratch,
+                            int64_t n_real, int32_t chunk, double h, float cut2, float eps2,
+                            double eta, double* dt_min_out);
 int gs_cpu_num_threads(void);
 int gs_cpu_set_threads(int32_t n);  // OpenMP threads for the CPU engine (returns the new max)
 
@@ -247,6 +269,47 @@ int gs_stepper_set_timeout(gs_stepper* s, double step_timeout_s);
 // Resolved force path: *exact = 1 for the hard-cutoff select, *eps2 = r^2 offset in use.
 int gs_stepper_force_mode(gs_stepper* s, int32_t* exact, double* eps2);
 void* gs_stepper_compute_stream(gs_stepper* s);
+
+// ---------------------------------------------------------------- Hermite (libgravsim_hip)
+// 4th-order Hermite predictor-corrector (Makino & Aarseth 1992) on one GPU: hermite.hip, the
+// acceleration+jerk kernel in nbody_hermite.hip. Uses cfg's n, dtype, device, dt (the fixed step,
+// or the ceiling of the adaptive one), G, cutoff, softening, chunk, ipl (0 auto; 1, 2, fp32: 4)
+// and split_groups (chunk groups of the evaluate grid, 0 auto); every launch shape gives the
+// same bits. Refuses nranks != 1 and cutoff == softening == 0.
+typedef struct gs_hermite gs_hermite;
+typedef struct gs_hermite_info {
+  double time;      // time reached [s]
+  double dt_last;   // size of the last step taken
+  double dt_next;   // min(dt, min_i dt_i): the next step before the t_end cut (fixed step: dt)
+  double dt_min;    // smallest step so far (a last step cut short by t_end not counted)
+  int64_t steps;    // steps taken (steps enqueued past t_end are no-ops and not counted)
+  int32_t finished; // t_end is set and reached
+  int32_t ipl;      // resolved i-bodies per lane
+} gs_hermite_info;
+int gs_hermite_create(const gs_config* cfg, gs_hermite** out);
+int gs_hermite_destroy(gs_hermite* h);
+int gs_hermite_layout(gs_hermite* h, gs_layout* out);
+// eta > 0: shared adaptive step by Aarseth's criterion (0: fixed dt_max); t_end >= 0: stop
+// there (the last step is cut to reach it exactly), t_end < 0: none. Call before the state is
+// set: the first adaptive step, (eta / 2) min |a| / |j|, is formed when the run starts.
+int gs_hermite_set_adaptive(gs_hermite* h, double eta, double dt_max, double t_end);
+int gs_hermite_init_ics(gs_hermite* h, int32_t ic, uint64_t seed);
+// Upload a global fp64 state at time t; the step count restarts at 0. acc / jerk NULL:
+// evaluated from (pos, vel). Given (a resumed run: n*3 each, with the dt_next and dt_min its
+// status reported; <= 0: none): taken as they are.
+int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, const double* mass,
+                         const double* acc, const double* jerk, double t, double dt_next,
+                         double dt_min);
+// Download (any pointer may be NULL): pos, vel, acc, jerk n*3, mass n.
+int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, double* acc,
+                         double* jerk);
+// (ax, ay, az, phi) and (jx, jy, jz, 0) of the current state through the step's own kernel.
+int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4);
+// Enqueue n steps (asynchronous: the step size and the time live on the device).
+int gs_hermite_step(gs_hermite* h, int32_t nsteps);
+int gs_hermite_sync(gs_hermite* h);
+int gs_hermite_status(gs_hermite* h, gs_hermite_info* out);  // waits for the enqueued steps
+int64_t gs_hermite_count_nonfinite(gs_hermite* h);
 
 // Virtual ranks on one device: shards[r] created with rank r of P; steps all of them in
 // lockstep with the all-gather done by device copies (the RCCL schedule without RCCL).

@@ -34,9 +34,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--cutoff-mode", choices=["auto", "exact", "fast"], default=d.cutoff_mode,
                    help="GPU force path: exact hard-cutoff select, or fast (r^2 + a core of "
                         "the cutoff scale, no select; bit-identical for separations above ~1 cm)")
-    p.add_argument("--integrator", choices=["kd", "leapfrog"], default=d.integrator,
+    p.add_argument("--integrator", choices=["kd", "leapfrog", "hermite"], default=d.integrator,
                    help="kd: the reference's kick-drift update; leapfrog: the same kernel on "
-                        "half-step-staggered velocities (second order)")
+                        "half-step-staggered velocities (second order); hermite: 4th-order "
+                        "predictor-corrector with its own acceleration+jerk kernel (one rank)")
+    p.add_argument("--eta", type=float, default=d.eta,
+                   help="hermite: accuracy parameter of the shared adaptive step (Aarseth's "
+                        "criterion; --dt is then the largest step); 0 = fixed step")
+    p.add_argument("--t-end", dest="t_end", type=float, default=d.t_end,
+                   help="hermite: stop at this time [s], reached exactly (--steps caps the count)")
     p.add_argument("--kernel", choices=["auto", "lds", "smem", "mfma"], default=d.kernel,
                    help="GPU force kernel: lds (LDS-DMA j tiles), smem (SGPR j stream), mfma "
                         "(experimental fp32: r^2 on the matrix cores, re-centred; slower)")
@@ -111,7 +117,8 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
             resume = ckpt.latest(resume)
     return SimConfig(n=a.n, dt=a.dt, steps=a.steps, dtype=a.dtype, device=a.device, init=a.init,
                      seed=a.seed, G=a.G, cutoff=a.cutoff, softening=a.softening,
-                     cutoff_mode=a.cutoff_mode, integrator=a.integrator, kernel=a.kernel,
+                     cutoff_mode=a.cutoff_mode, integrator=a.integrator, eta=a.eta,
+                     t_end=a.t_end, kernel=a.kernel,
                      mode=a.mode, ipl=a.ipl, chunk=a.chunk, graph=a.graph, graph_comm=a.graph_comm,
                      strategy=a.strategy, step_timeout_s=a.step_timeout_s, overlap=a.overlap,
                      threads=a.threads,

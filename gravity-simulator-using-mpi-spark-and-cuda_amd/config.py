@@ -17,6 +17,7 @@ DTYPES = ("fp32", "fp64")
 DEVICES = ("auto", "cpu", "gpu")
 KERNELS = ("auto", "lds", "smem", "mfma")
 MODES = ("auto", "fused", "split", "sym")
+INTEGRATORS = ("kd", "leapfrog", "hermite")
 COMMS = ("auto", "rccl", "gloo", "none")
 LOG_FORMATS = ("mpi", "spark", "cuda", "none")
 
@@ -34,7 +35,11 @@ class SimConfig:
     cutoff: float = 1e-10         # hard cutoff radius (cuda.cu:39, mpi.c:64, pyspark.py:38)
     softening: float = 0.0        # Plummer softening length (0 = reference semantics)
     cutoff_mode: str = "auto"     # GPU: exact (select) | fast (overflow-safe core) | auto
-    integrator: str = "kd"        # kd (reference kick-drift) | leapfrog (staggered KDK)
+    integrator: str = "kd"        # kd (reference kick-drift) | leapfrog (staggered KDK) |
+                                  # hermite (4th-order predictor-corrector, one rank)
+    eta: float = 0.0              # hermite: Aarseth accuracy parameter of the shared adaptive
+                                  # step (0 = fixed step dt; then dt is the step's ceiling)
+    t_end: Optional[float] = None  # hermite: stop at this time [s] (steps caps the step count)
     kernel: str = "auto"          # GPU j-source variant: lds | smem
     mode: str = "auto"            # GPU schedule: fused | split | sym (Newton-3, fp32)
     ipl: int = 0                  # i-bodies per lane (0 = auto)
@@ -101,8 +106,21 @@ class SimConfig:
             raise ValueError("ipl must be 0, 1, 2, 4 (or 8 for fp32)")
         if self.chunk and self.chunk % 1024:
             raise ValueError("chunk must be a multiple of 1024")
-        if self.integrator not in ("kd", "leapfrog"):
-            raise ValueError("integrator must be kd or leapfrog")
+        if self.integrator not in INTEGRATORS:
+            raise ValueError(f"integrator must be one of {INTEGRATORS}")
+        if self.integrator != "hermite" and (self.eta != 0 or self.t_end is not None):
+            raise ValueError("eta and t_end belong to integrator hermite")
+        if self.integrator == "hermite":
+            if not self.eta >= 0:
+                raise ValueError("eta must be >= 0")
+            if self.t_end is not None and not self.t_end >= 0:
+                raise ValueError("t_end must be >= 0")
+            if not self.dt > 0:
+                raise ValueError("hermite needs dt > 0")
+            if self.cutoff == 0 and self.softening == 0:
+                raise ValueError("hermite needs cutoff > 0 or softening > 0 (the self term)")
+            if self.ipl == 8 or (self.ipl == 4 and self.dtype != "fp32"):
+                raise ValueError("hermite: ipl must be 0, 1, 2 (or 4 for fp32)")
         if self.cutoff_mode not in ("auto", "exact", "fast"):
             raise ValueError("cutoff_mode must be auto, exact or fast")
         if self.strategy not in ("allgather", "ring"):

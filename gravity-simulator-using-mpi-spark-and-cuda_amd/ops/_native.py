@@ -47,6 +47,13 @@ class GsLayout(ctypes.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class GsHermiteInfo(ctypes.Structure):
+    _fields_ = [
+        ("time", c_double), ("dt_last", c_double), ("dt_next", c_double), ("dt_min", c_double),
+        ("steps", c_int64), ("finished", c_int32), ("ipl", c_int32),
+    ]
+
+
 GS_FP32, GS_FP64 = 0, 1
 KERNEL_IDS = {"auto": 0, "lds": 1, "smem": 2, "mfma": 3}
 MODE_IDS = {"auto": 0, "fused": 1, "split": 2, "sym": 3}
@@ -127,6 +134,11 @@ def cpu_lib():
             _sig(lib, f"gs_cpu_accel_{t}", c_int32, [P, c_int64, c_int64, c_int64, c_int32, T, T, P])
             _sig(lib, f"gs_cpu_step_{t}", c_int32,
                  [P, P, P, c_int64, c_int64, c_int64, c_int32, T, T, T])
+            _sig(lib, f"gs_cpu_accjerk_{t}", c_int32,
+                 [P, P, c_int64, c_int64, c_int64, c_int32, T, T, P, P])
+            _sig(lib, f"gs_cpu_hermite_step_{t}", c_int32,
+                 [P, P, P, P, P, c_int64, c_int32, c_double, T, T, c_double, _PD])
+            _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, c_int64, c_double])
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
                                                     c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_ld", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -192,6 +204,19 @@ def hip_lib():
         _sig(lib, "gs_stepper_unit_trace", c_int64, [S, c_void_p, c_int64])
         _sig(lib, "gs_stepper_compute_stream", c_void_p, [S])
         _sig(lib, "gs_stepper_force_mode", c_int32, [S, POINTER(c_int32), POINTER(c_double)])
+        _sig(lib, "gs_hermite_create", c_int32, [POINTER(GsConfig), POINTER(S)])
+        _sig(lib, "gs_hermite_destroy", c_int32, [S])
+        _sig(lib, "gs_hermite_layout", c_int32, [S, POINTER(GsLayout)])
+        _sig(lib, "gs_hermite_set_adaptive", c_int32, [S, c_double, c_double, c_double])
+        _sig(lib, "gs_hermite_init_ics", c_int32, [S, c_int32, c_uint64])
+        _sig(lib, "gs_hermite_set_state", c_int32, [S, _PD, _PD, _PD, _PD, _PD, c_double,
+                                                    c_double, c_double])
+        _sig(lib, "gs_hermite_get_state", c_int32, [S, _PD, _PD, _PD, _PD, _PD])
+        _sig(lib, "gs_hermite_derivs", c_int32, [S, _PD, _PD])
+        _sig(lib, "gs_hermite_step", c_int32, [S, c_int32])
+        _sig(lib, "gs_hermite_sync", c_int32, [S])
+        _sig(lib, "gs_hermite_status", c_int32, [S, POINTER(GsHermiteInfo)])
+        _sig(lib, "gs_hermite_count_nonfinite", c_int64, [S])
         _sig(lib, "gs_group_step", c_int32, [POINTER(S), c_int32, c_int32])
         _sig(lib, "gs_rccl_unique_id", c_int32, [c_void_p])
         _sig(lib, "gs_stepper_comm_init", c_int32, [S, c_void_p, c_int32, c_int32])

@@ -62,3 +62,31 @@ def accelerations(pos, mass, device: str = "cpu", **kw):
     if device == "gpu":
         return hip_accelerations(pos, mass, **kw)
     raise ValueError(f"unknown device {device!r}")
+
+
+def acc_jerk(pos, vel, mass, device: str = "cpu", dtype: str = "fp64", G: float = G_SI,
+             cutoff: float = 1e-10, softening: float = 0.0, chunk: int = 0, ipl: int = 0,
+             split_groups: int = 0):
+    """One-shot Hermite derivatives: (acc (n,3), jerk (n,3), phi (n,)) as float64 arrays.
+
+    device "oracle": NumPy fp64; "cpu": the native C++ engine; "gpu": the gfx950
+    acceleration+jerk kernel (raises if the HIP path is unavailable)."""
+    pos, vel = np.asarray(pos, np.float64), np.asarray(vel, np.float64)
+    mass = np.asarray(mass, np.float64)
+    n = int(mass.shape[0])
+    if device == "oracle":
+        return oracle.acc_jerk(pos, vel, mass, G, cutoff, softening, with_potential=True)
+    if device not in ("cpu", "gpu"):
+        raise ValueError(f"unknown device {device!r}")
+    from ..runtime.hermite import HermiteCpuEngine, HermiteHipEngine
+
+    cfg = SimConfig(n=n, dtype=dtype, G=G, cutoff=cutoff, softening=softening, chunk=chunk,
+                    ipl=ipl, split_groups=split_groups, device=device,
+                    integrator="hermite").validate()
+    eng = HermiteCpuEngine(cfg) if device == "cpu" else HermiteHipEngine(cfg)
+    try:
+        eng.load(BodySet(pos, vel, mass))
+        a4, j4 = eng.derivs()
+    finally:
+        eng.close()
+    return a4[:, :3], j4[:, :3], a4[:, 3]

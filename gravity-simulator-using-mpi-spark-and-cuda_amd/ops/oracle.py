@@ -67,6 +67,121 @@ def accelerations(pos: np.ndarray, mass: np.ndarray, G: float = G_SI, cutoff: fl
     return out if len(out) > 1 else acc
 
 
+def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: float = 0.0,
+             block: int = 256, with_potential: bool = False, with_abs: bool = False):
+    """Direct-sum accelerations and jerks (n, 3) in fp64; optionally phi (n,) too.
+
+        a_i = sum_j mu_j d / r^3,  j_i = sum_j mu_j (w - 3 (d.w) d / r^2) / r^3,
+        d = x_j - x_i, w = v_j - v_i, r^2 = |d|^2 + eps^2, mu = G m,
+
+    a pair contributing zero to all three when r^2 < cutoff^2 (the pair law of
+    accelerations()). with_abs also returns the rounding scales (n, 3) of both sums:
+    sum_j |a term| and, per component c,
+    sum_j mu_j r^-3 (|w_c| + 3 (sum_k |d_k w_k|) |d_c| / r^2)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    vel = np.asarray(vel, dtype=np.float64)
+    mu = G * np.asarray(mass, dtype=np.float64)
+    n = pos.shape[0]
+    acc, jerk = np.zeros((n, 3)), np.zeros((n, 3))
+    absacc, absjerk = np.zeros((n, 3)), np.zeros((n, 3))
+    phi = np.zeros(n)
+    cut2 = cutoff * cutoff
+    eps2 = softening * softening
+    def rows(i0: int) -> None:
+        i1 = min(n, i0 + block)
+        d = pos[None, :, :] - pos[i0:i1, None, :]            # (b, n, 3)  x_j - x_i
+        w = vel[None, :, :] - vel[i0:i1, None, :]
+        r2 = (d * d).sum(-1) + eps2
+        ok = r2 >= cut2
+        inv = np.zeros_like(r2)
+        inv[ok] = 1.0 / np.sqrt(r2[ok])
+        inv2 = inv * inv
+        mi = mu[None, :] * inv
+        s = mi * inv2
+        al = 3.0 * (d * w).sum(-1) * inv2
+        acc[i0:i1] = (s[:, :, None] * d).sum(1)
+        jerk[i0:i1] = (s[:, :, None] * (w - al[:, :, None] * d)).sum(1)
+        phi[i0:i1] = -mi.sum(1)
+        if with_abs:
+            absacc[i0:i1] = (s[:, :, None] * np.abs(d)).sum(1)
+            aal = 3.0 * np.abs(d * w).sum(-1) * inv2
+            absjerk[i0:i1] = (s[:, :, None] * (np.abs(w) + aal[:, :, None] * np.abs(d))).sum(1)
+
+    starts = range(0, n, block)
+    if n * n >= 1 << 22 and len(starts) > 1:
+        # (independent row blocks on a few threads, as in accelerations())
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+            list(ex.map(rows, starts))
+    else:
+        for i0 in starts:
+            rows(i0)
+    out = (acc, jerk)
+    if with_potential:
+        out += (phi,)
+    if with_abs:
+        out += (absacc, absjerk)
+    return out
+
+
+def hermite_dt(a0, j0, a1, j1, h, eta):
+    """Aarseth's criterion after a Hermite step of size h from (a0, j0) to (a1, j1):
+    min over the bodies of sqrt(eta (|a1||a2'| + |j1|^2) / (|j1||a3| + |a2'|^2)) with the 2nd
+    and 3rd derivatives the two evaluations imply; bodies with |j1| = 0 or a non-finite ratio
+    are skipped (inf when none is left)."""
+    da = a0 - a1
+    a2 = (-6.0 * da - h * (4.0 * j0 + 2.0 * j1)) / h ** 2
+    a3 = (12.0 * da + 6.0 * h * (j0 + j1)) / h ** 3
+    a2p = a2 + h * a3
+    nrm = lambda y: np.sqrt((y * y).sum(1))  # noqa: E731
+    an, jn, n2, n3 = nrm(a1), nrm(j1), nrm(a2p), nrm(a3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dt = np.sqrt(eta * (an * n2 + jn * jn) / (jn * n3 + n2 * n2))
+    dt = dt[(jn > 0) & np.isfinite(dt)]
+    return float(dt.min()) if dt.size else float("inf")
+
+
+def hermite_first_dt(a, j, eta):
+    """(eta / 2) min |a| / |j| over the bodies with |j| > 0 and a finite ratio."""
+    an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        dt = 0.5 * eta * an / jn
+    dt = dt[(jn > 0) & np.isfinite(dt)]
+    return float(dt.min()) if dt.size else float("inf")
+
+
+def simulate_hermite(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=0.0, eta=0.0,
+                     t_end=None, record_every=0):
+    """4th-order Hermite predictor-corrector (Makino & Aarseth 1992), one evaluation per step at
+    the predicted state. eta > 0: one shared step h = min(dt, min_i dt_i) chosen each step
+    (hermite_dt; the first from hermite_first_dt); t_end: the step is cut to reach it exactly and
+    the run stops there (`steps` caps the count). Returns (pos, vel, traj, t, list of steps)."""
+    x = np.array(pos, dtype=np.float64, copy=True)
+    v = np.array(vel, dtype=np.float64, copy=True)
+    a, j = acc_jerk(x, v, mass, G, cutoff, softening)
+    t, taken, traj = 0.0, [], []
+    nxt = hermite_first_dt(a, j, eta) if eta > 0 else dt
+    while len(taken) < steps and (t_end is None or t < t_end):
+        h = min(dt, nxt)
+        cut = t_end is not None and h >= t_end - t
+        if cut:
+            h = t_end - t
+        xp = x + (v * h + (a * (h * h / 2) + j * (h * h * h / 6)))
+        vp = v + (a * h + j * (h * h / 2))
+        a1, j1 = acc_jerk(xp, vp, mass, G, cutoff, softening)
+        v1 = v + ((a + a1) * (h / 2) + (j - j1) * (h * h / 12))
+        x = x + ((v + v1) * (h / 2) + (a - a1) * (h * h / 12))
+        if eta > 0:
+            nxt = hermite_dt(a, j, a1, j1, h, eta)
+        v, a, j = v1, a1, j1
+        t = t_end if cut else t + h
+        taken.append(h)
+        if record_every and len(taken) % record_every == 0:
+            traj.append(x.copy())
+    return x, v, traj, t, taken
+
+
 def step(pos, vel, mass, dt, G=G_SI, cutoff=1e-10, softening=0.0):
     """One synchronous kick-drift step; returns new (pos, vel)."""
     a = accelerations(pos, mass, G, cutoff, softening)
@@ -76,11 +191,18 @@ def step(pos, vel, mass, dt, G=G_SI, cutoff=1e-10, softening=0.0):
 
 
 def simulate(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=0.0, record_every=0,
-             integrator="kd"):
+             integrator="kd", eta=0.0, t_end=None):
     """Run `steps` steps. Returns (pos, vel, trajectory list of positions if record_every).
 
     integrator "leapfrog": kick-drift-kick, v_{1/2} = v_0 + a_0 dt/2, x_1 = x_0 + v_{1/2} dt,
-    v_1 = v_{1/2} + a_1 dt/2 (velocities returned synchronized)."""
+    v_1 = v_{1/2} + a_1 dt/2 (velocities returned synchronized).
+    integrator "hermite" (simulate_hermite; eta, t_end): also returns the time reached and the
+    list of steps taken: (pos, vel, traj, t, steps)."""
+    if integrator == "hermite":
+        return simulate_hermite(pos, vel, mass, dt, steps, G, cutoff, softening, eta, t_end,
+                                record_every)
+    if eta or t_end is not None:
+        raise ValueError("eta and t_end belong to integrator hermite")
     x = np.array(pos, dtype=np.float64, copy=True)
     v = np.array(vel, dtype=np.float64, copy=True)
     traj = []

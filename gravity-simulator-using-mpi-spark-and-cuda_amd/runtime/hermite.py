@@ -1,0 +1,297 @@
+"""Engines of the 4th-order Hermite integrator (Makino & Aarseth 1992), one rank.
+
+The same interface as the engines of runtime/engines.py (load / init_ics / step / sync / state /
+accel / nonfinite / steps_done / close) plus status(): the integrator carries x, v, a, j, t and
+the next step size, so the time reached is the engine's, not step * dt.
+
+* HermiteHipEngine: the native gs_hermite object (csrc/hip/hermite.hip): device-resident state,
+  the acceleration+jerk kernel of csrc/hip/nbody_hermite.hip, the step size chosen on the device.
+* HermiteCpuEngine: the native C++/OpenMP step (csrc/cpu/cpu_engine.cpp gs_cpu_hermite_step_*).
+
+One step of size h: predict xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2; evaluate
+a1, j1 at (xp, vp); correct v1 = v + (a + a1) h/2 + (j - j1) h^2/12,
+x1 = x + (v + v1) h/2 + (a - a1) h^2/12; a1, j1 become the next step's a, j. With eta > 0 every
+step takes h = min(dt, min_i dt_i) of Aarseth's criterion; with t_end set the last step is cut
+to reach it exactly and further steps are no-ops.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from ..config import SimConfig
+from ..models.initial_conditions import DEVICE_IC_IDS, BodySet, make
+from ..ops import _native
+from ..parallel.partition import Layout, layout as make_layout
+
+
+@dataclass
+class HermiteStatus:
+    time: float       # time reached [s]
+    dt_last: float    # size of the last step taken (0 before the first)
+    dt_next: float    # min(dt, min_i dt_i): the next step before the t_end cut
+    dt_min: float     # smallest step so far (inf before the first; a last step cut short by
+                      # t_end is not counted)
+    steps: int        # steps taken (steps enqueued past t_end are no-ops, not counted)
+    finished: bool    # t_end is set and reached
+
+
+def _require_one_rank(nranks: int) -> None:
+    if nranks != 1:
+        raise ValueError("hermite runs on one rank")
+
+
+class HermiteHipEngine:
+    """GPU engine: one native gs_hermite per process."""
+
+    kind = "gpu"
+
+    def __init__(self, cfg: SimConfig, rank: int = 0, nranks: int = 1, device: int = 0):
+        _require_one_rank(nranks)
+        from .engines import _gs_config
+
+        self.cfg = cfg
+        self.rank, self.nranks, self.device = 0, 1, device
+        self.lib = _native.hip_lib()
+        c = _gs_config(cfg.replace(kernel="auto", mode="auto"), 0, 1, device)
+        self._h = ctypes.c_void_p()
+        _native.check(self.lib, self.lib.gs_hermite_create(ctypes.byref(c), ctypes.byref(self._h)),
+                      "gs_hermite_create")
+        L = _native.GsLayout()
+        _native.check(self.lib, self.lib.gs_hermite_layout(self._h, ctypes.byref(L)), "layout")
+        self.native_layout = L.as_dict()
+        self.layout: Layout = make_layout(cfg.n, 0, 1, L.chunk)
+        assert self.layout.n_pad == L.n_pad, "Python layout mirror disagrees with native"
+        _native.check(self.lib, self.lib.gs_hermite_set_adaptive(
+            self._h, float(cfg.eta), float(cfg.dt),
+            -1.0 if cfg.t_end is None else float(cfg.t_end)), "set_adaptive")
+
+    def init_ics(self, family: str, seed: int) -> None:
+        if family in DEVICE_IC_IDS:
+            _native.check(self.lib, self.lib.gs_hermite_init_ics(self._h, DEVICE_IC_IDS[family],
+                                                                 seed), "init_ics")
+        else:
+            self.load(make(family, self.cfg.n, seed, self.cfg.G))
+
+    def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
+             dt_next: Optional[float] = None, dt_min: Optional[float] = None) -> None:
+        """Set the state at time t. acc, jerk None: evaluated from (pos, vel); given (with the
+        dt_next and dt_min a status() reported): a run continues as if never interrupted."""
+        pos = np.ascontiguousarray(b.pos, dtype=np.float64)
+        vel = np.ascontiguousarray(b.vel, dtype=np.float64)
+        mass = np.ascontiguousarray(b.mass, dtype=np.float64)
+        have = acc is not None and jerk is not None
+        a = np.ascontiguousarray(acc, dtype=np.float64) if have else None
+        j = np.ascontiguousarray(jerk, dtype=np.float64) if have else None
+        _native.check(self.lib, self.lib.gs_hermite_set_state(
+            self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
+            _native.dptr(a) if have else None, _native.dptr(j) if have else None, float(t),
+            float(dt_next) if dt_next is not None and math.isfinite(dt_next) else -1.0,
+            float(dt_min) if dt_min is not None and math.isfinite(dt_min) else -1.0),
+            "set_state")
+
+    def abort(self) -> bool:
+        """The run guard's abort hook: one rank holds no communicator whose collectives could
+        hang, so there is nothing to abort (the guard's stage deadline still ends the job)."""
+        return False
+
+    def comm_stage(self) -> str:
+        """The run guard's probe (HipEngine.comm_stage): no communicator is ever formed."""
+        return "no communicator (one rank)"
+
+    def step(self, n: int) -> None:
+        if n > 0:
+            _native.check(self.lib, self.lib.gs_hermite_step(self._h, int(n)), "step")
+
+    def sync(self, timeout_s: float = 0.0) -> None:
+        _native.check(self.lib, self.lib.gs_hermite_sync(self._h), "sync")
+
+    def status(self) -> HermiteStatus:
+        """Waits for the enqueued steps."""
+        s = _native.GsHermiteInfo()
+        _native.check(self.lib, self.lib.gs_hermite_status(self._h, ctypes.byref(s)), "status")
+        return HermiteStatus(s.time, s.dt_last, s.dt_next, s.dt_min, int(s.steps),
+                             bool(s.finished))
+
+    def _get(self, want_deriv: bool):
+        n = self.cfg.n
+        pos, vel, mass = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+        acc = np.zeros((n, 3)) if want_deriv else None
+        jerk = np.zeros((n, 3)) if want_deriv else None
+        _native.check(self.lib, self.lib.gs_hermite_get_state(
+            self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
+            _native.dptr(acc) if want_deriv else None, _native.dptr(jerk) if want_deriv else None),
+            "get_state")
+        return BodySet(pos, vel, mass), acc, jerk
+
+    def state(self) -> BodySet:
+        return self._get(False)[0]
+
+    def carried(self) -> tuple[np.ndarray, np.ndarray]:
+        """(acc, jerk) (n, 3) as the integrator carries them (evaluated at the last predicted
+        state): what a checkpoint keeps so that a resumed run is bit-exact."""
+        _, a, j = self._get(True)
+        return a, j
+
+    def derivs(self) -> tuple[np.ndarray, np.ndarray]:
+        """(n, 4) (ax, ay, az, phi) and (jx, jy, jz, 0) of the current (x, v), through the
+        step's own kernel."""
+        n = self.cfg.n
+        a4, j4 = np.zeros((n, 4)), np.zeros((n, 4))
+        _native.check(self.lib, self.lib.gs_hermite_derivs(self._h, _native.dptr(a4),
+                                                           _native.dptr(j4)), "derivs")
+        return a4, j4
+
+    def accel(self, step_path: bool = False) -> np.ndarray:
+        """(n_local, 4) = (ax, ay, az, phi), ghost rows zero."""
+        out = np.zeros((self.layout.n_local, 4))
+        out[: self.cfg.n] = self.derivs()[0]
+        return out
+
+    def nonfinite(self) -> int:
+        r = int(self.lib.gs_hermite_count_nonfinite(self._h))
+        if r < 0:
+            raise RuntimeError("nonfinite check failed: " + self.lib.gs_last_error().decode())
+        return r
+
+    @property
+    def steps_done(self) -> int:
+        return self.status().steps
+
+    def close(self) -> None:
+        if self._h:
+            self.lib.gs_hermite_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HermiteCpuEngine:
+    """Native CPU engine: gs_cpu_hermite_step_* per step; the step-size bookkeeping (a few
+    scalars) stays in Python."""
+
+    kind = "cpu"
+
+    def __init__(self, cfg: SimConfig, rank: int = 0, nranks: int = 1):
+        _require_one_rank(nranks)
+        self.cfg = cfg
+        self.rank, self.nranks = 0, 1
+        self.lib = _native.cpu_lib()
+        self.layout: Layout = make_layout(cfg.n, 0, 1, cfg.chunk)
+        self.np_dtype = np.float64 if cfg.dtype == "fp64" else np.float32
+        n, T = cfg.n, self.np_dtype
+        self.X, self.V = np.zeros((n, 4), T), np.zeros((n, 4), T)
+        self.A, self.J = np.zeros((n, 4), T), np.zeros((n, 4), T)
+        self._scratch = np.zeros((4 * n, 4), T)
+        self.mass = np.zeros(n)
+        suf = "f64" if cfg.dtype == "fp64" else "f32"
+        self._step = getattr(self.lib, f"gs_cpu_hermite_step_{suf}")
+        self._accjerk = getattr(self.lib, f"gs_cpu_accjerk_{suf}")
+        self._first_dt = getattr(self.lib, f"gs_cpu_hermite_first_dt_{suf}")
+        self._ptr = _native.dptr if cfg.dtype == "fp64" else _native.fptr
+        self._cut2 = T(cfg.cutoff ** 2)
+        self._eps2 = T(cfg.softening ** 2)
+        self.t, self.dt_last, self.dt_min, self.k = 0.0, 0.0, math.inf, 0
+        self._next = math.inf  # min_i dt_i of the last step (adaptive)
+        if cfg.threads:
+            self.lib.gs_cpu_set_threads(int(cfg.threads))
+
+    def init_ics(self, family: str, seed: int) -> None:
+        self.load(make(family, self.cfg.n, seed, self.cfg.G))
+
+    def _derivs(self) -> tuple[np.ndarray, np.ndarray]:
+        n, T = self.cfg.n, self.np_dtype
+        a4, j4 = np.zeros((n, 4), T), np.zeros((n, 4), T)
+        rc = self._accjerk(self._ptr(self.X), self._ptr(self.V), n, 0, n, self.layout.chunk,
+                           self._cut2, self._eps2, self._ptr(a4), self._ptr(j4))
+        _native.check(self.lib, rc, "cpu accjerk")
+        return a4, j4
+
+    def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
+             dt_next: Optional[float] = None, dt_min: Optional[float] = None) -> None:
+        self.X[:, :3] = b.pos
+        self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
+        self.V[:] = 0
+        self.V[:, :3] = b.vel
+        self.mass = np.array(b.mass, dtype=np.float64)
+        self.A[:] = 0
+        self.J[:] = 0
+        if acc is not None and jerk is not None:
+            self.A[:, :3] = acc
+            self.J[:, :3] = jerk
+            self._next = math.inf if dt_next is None else float(dt_next)
+        else:
+            a4, j4 = self._derivs()
+            self.A[:, :3] = a4[:, :3]
+            self.J[:, :3] = j4[:, :3]
+            self._next = math.inf
+            if self.cfg.eta > 0:
+                self._next = float(self._first_dt(self._ptr(self.A), self._ptr(self.J),
+                                                  self.cfg.n, float(self.cfg.eta)))
+        self.t, self.dt_last, self.k = float(t), 0.0, 0
+        self.dt_min = math.inf if dt_min is None else float(dt_min)
+
+    def step(self, n: int) -> None:
+        cfg = self.cfg
+        out = ctypes.c_double(math.inf)
+        for _ in range(int(n)):
+            if cfg.t_end is not None and self.t >= cfg.t_end:
+                return
+            h = min(cfg.dt, self._next) if cfg.eta > 0 else cfg.dt
+            cut = cfg.t_end is not None and h >= cfg.t_end - self.t
+            if cut:
+                h = cfg.t_end - self.t
+            rc = self._step(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
+                            self._ptr(self.J), self._ptr(self._scratch), cfg.n,
+                            self.layout.chunk, h, self._cut2, self._eps2, float(cfg.eta),
+                            ctypes.byref(out))
+            _native.check(self.lib, rc, "cpu hermite step")
+            self._next = out.value
+            self.t = cfg.t_end if cut else self.t + h
+            self.dt_last = h
+            if not cut:
+                self.dt_min = min(self.dt_min, h)
+            self.k += 1
+
+    def sync(self, timeout_s: float = 0.0) -> None:
+        pass
+
+    def status(self) -> HermiteStatus:
+        cfg = self.cfg
+        nxt = min(cfg.dt, self._next) if cfg.eta > 0 else cfg.dt
+        return HermiteStatus(self.t, self.dt_last, nxt, self.dt_min, self.k,
+                             cfg.t_end is not None and self.t >= cfg.t_end)
+
+    def state(self) -> BodySet:
+        return BodySet(self.X[:, :3].astype(np.float64), self.V[:, :3].astype(np.float64),
+                       self.mass.copy())
+
+    def carried(self) -> tuple[np.ndarray, np.ndarray]:
+        return self.A[:, :3].astype(np.float64), self.J[:, :3].astype(np.float64)
+
+    def derivs(self) -> tuple[np.ndarray, np.ndarray]:
+        a4, j4 = self._derivs()
+        return a4.astype(np.float64), j4.astype(np.float64)
+
+    def accel(self) -> np.ndarray:
+        out = np.zeros((self.layout.n_local, 4))
+        out[: self.cfg.n] = self.derivs()[0]
+        return out
+
+    def nonfinite(self) -> int:
+        return int((~np.isfinite(self.X[:, :3])).sum() + (~np.isfinite(self.V[:, :3])).sum())
+
+    @property
+    def steps_done(self) -> int:
+        return self.k
+
+    def close(self) -> None:
+        pass

@@ -17,7 +17,11 @@ design:
   (v_{k-1/2}): a backward half-kick at the start, synchronized velocities
   v_k = v_{k-1/2} + a(x_k) dt/2 on output — second-order (KDK) accuracy at no extra cost per
   step. Checkpoints keep the staggered velocities (meta "velocity": "half-step") so resume
-  stays bit-exact.
+  stays bit-exact;
+* integrator "hermite" (one rank) is the 4th-order predictor-corrector of runtime/hermite.py with
+  its own acceleration+jerk kernel, a fixed step or a shared adaptive one (eta) and an optional
+  end time (t_end); the engine carries the time, so metrics and checkpoints report its t, and a
+  checkpoint keeps the carried a, j and the next step size so that resume stays bit-exact.
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ from ..utils import checkpoint as ckpt
 from ..utils.logs import RunLog
 from ..utils.metrics import RunMetrics
 from .engines import CpuEngine, HipEngine, gpu_available
+from .hermite import HermiteCpuEngine, HermiteHipEngine
 
 
 class NonFiniteError(RuntimeError):
@@ -87,6 +92,9 @@ class Simulation:
     def __init__(self, cfg: SimConfig, dist: Optional[comm.DistInfo] = None, guard=None):
         self.cfg = cfg.validate()
         self.dist = dist or comm.env_info()
+        self.hermite = cfg.integrator == "hermite"
+        if self.hermite and self.dist.world > 1:
+            raise ValueError("hermite runs on one rank")
         self.overlap_check: Optional[str] = None
         use_gpu = cfg.device == "gpu" or (cfg.device == "auto" and gpu_available())
         if cfg.device == "gpu" and not gpu_available():
@@ -100,7 +108,8 @@ class Simulation:
 
             dev = d.local_rank % max(1, torch.cuda.device_count())
             stage("engine", INIT_TIMEOUT_S)
-            self.engine = HipEngine(cfg, d.rank, d.world, device=dev, dist=d)
+            self.engine = (HermiteHipEngine(cfg, device=dev) if self.hermite else
+                           HipEngine(cfg, d.rank, d.world, device=dev, dist=d))
             if guard:
                 guard.on_abort(self.engine.abort)
                 guard.probe(lambda: {"comm_stage": self.engine.comm_stage()})
@@ -122,7 +131,8 @@ class Simulation:
             # instead of killing a slow but healthy start; gloo's own timeouts
             # bound its collectives.
             stage("cpu_setup", None)
-            self.engine = CpuEngine(cfg, d.rank, d.world, dist=d)
+            self.engine = (HermiteCpuEngine(cfg) if self.hermite else
+                           CpuEngine(cfg, d.rank, d.world, dist=d))
         self.step0 = 0
         self.trajectory: list[np.ndarray] = []
         self.staggered = False  # velocities held as v_{k-1/2} (leapfrog)
@@ -130,7 +140,17 @@ class Simulation:
             c = ckpt.load(cfg.resume)
             if c.bodies.n != cfg.n:
                 raise ValueError(f"checkpoint has n={c.bodies.n}, config n={cfg.n}")
-            self.engine.load(c.bodies)
+            if self.hermite and c.meta.get("integrator") == "hermite" and \
+                    "acc" in c.extra and "jerk" in c.extra:
+                # the carried a, j (evaluated at the last predicted state) and the step size
+                # the criterion chose: the run continues bit for bit
+                self.engine.load(c.bodies, c.extra["acc"], c.extra["jerk"],
+                                 t=float(c.meta.get("time", 0.0)), dt_next=c.meta.get("dt_next"),
+                                 dt_min=c.meta.get("dt_min"))
+            elif self.hermite:
+                self.engine.load(c.bodies, t=float(c.meta.get("time", 0.0)))  # a, j afresh
+            else:
+                self.engine.load(c.bodies)
             self.step0 = c.step
             self.staggered = c.meta.get("velocity") == "half-step"
             stored_dt = float(c.meta.get("dt", cfg.dt))
@@ -148,7 +168,7 @@ class Simulation:
         if cfg.integrator == "leapfrog" and not self.staggered:
             self._half_kick(-1.0)
             self.staggered = True
-        elif cfg.integrator == "kd" and self.staggered:
+        elif cfg.integrator in ("kd", "hermite") and self.staggered:
             self._half_kick(+1.0)
             self.staggered = False
 
@@ -199,7 +219,10 @@ class Simulation:
         b = self.engine.state()
         acc = self._own_accel()
         b.vel = b.vel + sign * 0.5 * (self.cfg.dt if dt is None else dt) * acc
-        self.engine.load(b)
+        if self.hermite:  # (a leapfrog checkpoint resumed under hermite: its time carries on)
+            self.engine.load(b, t=self.engine.status().time)
+        else:
+            self.engine.load(b)
 
     def raw_state(self) -> BodySet:
         """Full (pos, vel as stored, mass) on every rank (collective when P > 1)."""
@@ -243,7 +266,15 @@ class Simulation:
                     softening=cfg.softening, init=cfg.init, seed=cfg.seed,
                     time=self.step * cfg.dt, integrator=cfg.integrator,
                     velocity="half-step" if self.staggered else "synchronized")
-        return ckpt.save(path, b, self.step, meta)
+        extra = None
+        if self.hermite:
+            st = self.engine.status()
+            acc, jerk = self.engine.carried()
+            extra = {"acc": acc, "jerk": jerk}
+            fin = lambda y: y if np.isfinite(y) else None  # noqa: E731
+            meta.update(time=st.time, dt_next=fin(st.dt_next), dt_min=fin(st.dt_min),
+                        eta=cfg.eta)
+        return ckpt.save(path, b, self.step, meta, extra)
 
     def run(self, steps: Optional[int] = None, log: Optional[RunLog] = None) -> RunMetrics:
         cfg = self.cfg
@@ -261,15 +292,27 @@ class Simulation:
         if gpu:
             self.engine.audit_reset()
             self.engine.clock()  # (reset: the engine-clock record of this run's steps)
+        # Hermite with an end time: the engine stops by itself (steps past t_end are no-ops), so
+        # the host asks whether it has finished once per 32 enqueued steps and then stops
+        # enqueueing; `steps` caps the count.
+        ends = self.hermite and cfg.t_end is not None
+        st0 = self.engine.status() if self.hermite else None
+        polled = 0
         comm.barrier(self.dist)
         t0 = time.perf_counter()
         s = 0
-        while s < steps:
+        finished = False
+        while s < steps and not finished:
             if log and cfg.progress_every and s % cfg.progress_every == 0 and self.dist.is_root:
                 log.progress(s, steps)
             nxt = min([steps] + [(s // p + 1) * p for p in periods])
+            if ends:
+                nxt = min(nxt, polled + 32)
             self.engine.step(nxt - s)
             s = nxt
+            if ends and s - polled == 32:
+                polled = s
+                finished = self.engine.status().finished
             if cfg.nan_check_every and s % cfg.nan_check_every == 0:
                 self.check_finite()
             if cfg.record_every and s % cfg.record_every == 0:
@@ -317,10 +360,16 @@ class Simulation:
         lay = getattr(self.engine, "native_layout", {})
         from ..ops._native import KERNEL_NAMES, MODE_NAMES
 
+        herm = {}
+        if self.hermite:
+            st = self.engine.status()
+            steps = st.steps - st0.steps  # the steps this run took (none past t_end)
+            herm = dict(time_reached=st.time, steps_taken=steps,
+                        dt_min=st.dt_min if np.isfinite(st.dt_min) else None)
         return RunMetrics(n=cfg.n, steps=steps, dt=cfg.dt, dtype=cfg.dtype, device=self.device,
                           nranks=self.dist.world, wall_s=wall,
                           kernel=KERNEL_NAMES.get(lay.get("kernel", 0), "cpu"),
-                          mode=MODE_NAMES.get(lay.get("mode", 0), "cpu"), extra=extra)
+                          mode=MODE_NAMES.get(lay.get("mode", 0), "cpu"), extra=extra, **herm)
 
     def dump_path_for(self, step: int) -> str:
         cfg = self.cfg

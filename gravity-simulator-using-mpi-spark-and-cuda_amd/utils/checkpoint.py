@@ -7,6 +7,9 @@ Format (little-endian, rank-agnostic global body order):
     pos     n*3 float64
     vel     n*3 float64
     mass    n   float64
+    extra   the arrays the header names in "extra" (a Hermite run: ["acc", "jerk"], n*3 float64
+            each, with "time" and "dt_next" in the header); readers that do not know them stop
+            after mass
 State is always stored in fp64 so an fp32 run resumes exactly (fp32 -> fp64 -> fp32 is exact).
 Writes go to a temp file + rename, so a crash never leaves a torn checkpoint.
 """
@@ -15,7 +18,7 @@ from __future__ import annotations
 import json
 import os
 import struct
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -29,12 +32,16 @@ class Checkpoint:
     bodies: BodySet
     step: int
     meta: dict
+    extra: dict = field(default_factory=dict)  # name -> (n, 3) float64 array
 
 
-def save(path: str, bodies: BodySet, step: int, meta: dict) -> str:
+def save(path: str, bodies: BodySet, step: int, meta: dict, extra: dict | None = None) -> str:
     n = bodies.n
     head = dict(meta)
     head.update(n=n, step=int(step), version=1)
+    extra = extra or {}
+    if extra:
+        head["extra"] = list(extra)
     hb = json.dumps(head, sort_keys=True).encode()
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
@@ -46,6 +53,11 @@ def save(path: str, bodies: BodySet, step: int, meta: dict) -> str:
         f.write(np.ascontiguousarray(bodies.pos, dtype="<f8").tobytes())
         f.write(np.ascontiguousarray(bodies.vel, dtype="<f8").tobytes())
         f.write(np.ascontiguousarray(bodies.mass, dtype="<f8").tobytes())
+        for name in extra:
+            a = np.ascontiguousarray(extra[name], dtype="<f8")
+            if a.shape != (n, 3):
+                raise ValueError(f"checkpoint extra {name!r} must be (n, 3)")
+            f.write(a.tobytes())
     os.replace(tmp, path)
     return path
 
@@ -62,7 +74,13 @@ def load(path: str) -> Checkpoint:
         mass = np.frombuffer(f.read(n * 8), dtype="<f8").copy()
         if mass.shape[0] != n:
             raise ValueError(f"{path}: truncated checkpoint")
-    return Checkpoint(BodySet(pos, vel, mass), int(head["step"]), head)
+        extra = {}
+        for name in head.get("extra", []):
+            a = np.frombuffer(f.read(n * 24), dtype="<f8")
+            if a.shape[0] != n * 3:
+                raise ValueError(f"{path}: truncated checkpoint ({name})")
+            extra[name] = a.reshape(n, 3).copy()
+    return Checkpoint(BodySet(pos, vel, mass), int(head["step"]), head, extra)
 
 
 def path_for(directory: str, step: int) -> str:

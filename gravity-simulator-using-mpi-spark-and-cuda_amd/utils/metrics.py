@@ -27,6 +27,11 @@ class RunMetrics:
     kernel: str = ""
     mode: str = ""
     extra: dict = field(default_factory=dict)
+    # integrator hermite (None otherwise, and then left out of the JSON line): the simulated
+    # time reached, the steps taken (steps past t_end are not taken) and the smallest step
+    time_reached: float | None = None
+    steps_taken: int | None = None
+    dt_min: float | None = None
 
     @property
     def ms_per_step(self) -> float:
@@ -49,6 +54,9 @@ class RunMetrics:
 
     def to_json(self) -> str:
         d = asdict(self)
+        for k in ("time_reached", "steps_taken", "dt_min"):
+            if d[k] is None:
+                del d[k]
         d.update(ms_per_step=self.ms_per_step, body_updates_per_s=self.body_updates_per_s,
                  effective_interactions_per_s=self.effective_interactions_per_s,
                  pair_evals_per_s=self.pair_evals_per_s)
