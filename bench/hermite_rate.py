@@ -12,6 +12,11 @@ counts; each window ends in a device synchronise. Prints one JSON line.
 
 --drift also runs 65,536 solar+random bodies for 24 simulated hours under kd, leapfrog (dt 3600)
 and hermite --eta 0.02 and reports each run's relative energy drift.
+--block runs the same workload (and the same at the other --sizes) with the shared adaptive step
+and with individual block time steps: wall time, steps, body-steps, energy drift and the ratio.
+--active-sweep times one evaluate + reduce of a block step at n_act = 1, 4, 16, ..., N on both
+paths (narrow: parallel over j, up to --narrow-cap active bodies; wide: the gathered i-owned
+kernel): alternating windows of back-to-back launches between device events, median.
 """
 from __future__ import annotations
 
@@ -105,6 +110,78 @@ def drift(n: int, hours: float, seed: int) -> list:
     return out
 
 
+def block(n: int, hours: float, seed: int, dtype: str = "fp32") -> dict:
+    """Shared adaptive step against block steps, same build, same workload."""
+    from gravsim.config import SimConfig
+    from gravsim.runtime.simulation import Simulation
+
+    out = {"n": n, "dtype": dtype, "hours": hours}
+    for name, kw in (("shared", dict(steps=10 ** 6)),
+                     ("block", dict(block_steps=True, steps=int(hours)))):
+        sim = Simulation(SimConfig(n=n, dtype=dtype, device="gpu", dt=3600.0, seed=seed,
+                                   integrator="hermite", eta=0.02, t_end=hours * 3600.0,
+                                   diagnostics=True, **kw))
+        try:
+            m = sim.run()
+        finally:
+            sim.close()
+        r = {"wall_s": m.wall_s, "steps": m.steps, "time_reached": m.time_reached,
+             "dt_min": m.dt_min,
+             "energy_rel_drift": m.extra["conservation"]["energy_rel_drift"]}
+        if name == "block":
+            r.update(block_steps=m.block_steps, body_steps=m.body_steps, level_max=m.level_max,
+                     level_clamped=m.level_clamped,
+                     mean_n_act=m.body_steps / max(1, m.block_steps),
+                     us_per_block_step=1e6 * m.wall_s / max(1, m.block_steps))
+        else:
+            r.update(body_steps=m.steps * n)
+        out[name] = r
+    out["shared_over_block_wall"] = out["shared"]["wall_s"] / out["block"]["wall_s"]
+    out["shared_over_block_body_steps"] = out["shared"]["body_steps"] / out["block"]["body_steps"]
+    return out
+
+
+def active_sweep(n: int, dtype: str, seed: int, repeat: int, narrow_cap: int) -> dict:
+    import numpy as np
+
+    from gravsim.config import SimConfig
+    from gravsim.runtime.hermite import HermiteHipEngine
+
+    eng = HermiteHipEngine(SimConfig(n=n, dtype=dtype, device="gpu", integrator="hermite",
+                                     eta=0.02, block_steps=True))
+    try:
+        eng.init_ics("solar+random", seed)
+        cap = min(n, narrow_cap)
+        default = eng.status_narrow_max()
+        eng.set_block_tuning(narrow_max=cap)
+        perm = np.random.default_rng(seed).permutation(n)
+        sizes = sorted({min(n, 4 ** k) for k in range(0, 12)} | {n} |
+                       {2 ** k for k in range(10, 17) if 2 ** k <= n})
+        rows = []
+        for m in sizes:
+            idx = np.sort(perm[:m]).astype(np.int32)
+            paths = ["wide"] + (["narrow"] if m <= cap else [])
+            t = {p: [] for p in paths}
+            for p in paths:
+                eng.time_active(idx, p, 2)  # warm-up
+            for _ in range(repeat):
+                for p in paths:
+                    once = eng.time_active(idx, p, 1)
+                    t[p].append(eng.time_active(idx, p, max(1, min(50, int(20.0 / max(once,
+                                                                                     1e-3))))))
+            row = {"n_act": m}
+            for p in paths:
+                row[f"{p}_ms"] = statistics.median(t[p])
+            rows.append(row)
+        both = [r for r in rows if "narrow_ms" in r]
+        faster = [r["n_act"] for r in both if r["narrow_ms"] <= r["wide_ms"]]
+        return {"n": n, "dtype": dtype, "narrow_cap": cap, "rows": rows,
+                "narrow_faster_up_to": max(faster) if faster else 0,
+                "default_narrow_max": default}
+    finally:
+        eng.close()
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--sizes", default="65536,262144")
@@ -115,6 +192,14 @@ def main() -> int:
     ap.add_argument("--drift", action="store_true",
                     help="also the 24-hour energy drift of kd, leapfrog and hermite at 65,536")
     ap.add_argument("--drift-n", type=int, default=65536)
+    ap.add_argument("--block", action="store_true",
+                    help="the 24-hour workload at every --sizes: shared adaptive step against "
+                         "block steps (fp32, eta 0.02)")
+    ap.add_argument("--active-sweep", action="store_true",
+                    help="ms per evaluate of a block step at n_act = 1, 4, 16, ..., N, both paths")
+    ap.add_argument("--narrow-cap", type=int, default=65536,
+                    help="--active-sweep: largest n_act timed on the narrow path")
+    ap.add_argument("--no-rates", action="store_true", help="skip the hermite / kd step rates")
     a = ap.parse_args()
     import torch
 
@@ -124,10 +209,16 @@ def main() -> int:
         raise SystemExit("hermite_rate: needs a HIP device")
     res = {"bench": "hermite_rate", "device": torch.cuda.get_device_name(0),
            "engine_clock_ghz": None,  # (the Hermite kernel does not record the engine clock)
-           "rates": [rate(int(n), d, a.seed, a.repeat, a.min_window_s)
+           "rates": [] if a.no_rates else
+                    [rate(int(n), d, a.seed, a.repeat, a.min_window_s)
                      for n in a.sizes.split(",") for d in a.dtypes.split(",")]}
     if a.drift:
         res["drift_24h"] = drift(a.drift_n, 24.0, a.seed)
+    if a.block:
+        res["block_24h"] = [block(int(n), 24.0, a.seed) for n in a.sizes.split(",")]
+    if a.active_sweep:
+        res["active_sweep"] = [active_sweep(int(n), d, a.seed, a.repeat, a.narrow_cap)
+                               for n in a.sizes.split(",") for d in a.dtypes.split(",")]
     print(json.dumps(res), flush=True)
     return 0
 

@@ -309,6 +309,26 @@ int accjerk_range(const T* X4, const T* V4, int64_t n_real, int64_t i0, int64_t 
   return 0;
 }
 
+// The same sums for a list of bodies (a block step's active set): row k of the output is body
+// idx[k].
+template <typename T>
+int accjerk_idx(const T* X4, const T* V4, int64_t n_real, const int32_t* idx, int64_t n_idx,
+                int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4) {
+  if (chunk <= 0 || n_idx < 0 || (n_idx > 0 && !idx)) {
+    gs_set_error("cpu_accjerk_idx: bad arguments");
+    return -1;
+  }
+  for (int64_t k = 0; k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= n_real) {
+      gs_set_error("cpu_accjerk_idx: index out of range");
+      return -1;
+    }
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < n_idx; ++k)
+    accjerk_one<T>(X4, V4, n_real, idx[k], chunk, cut2, eps2, acc4 + 4 * k, jerk4 + 4 * k);
+  return 0;
+}
+
 inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
 
 template <typename T>
@@ -416,6 +436,16 @@ int gs_cpu_accjerk_f64(const double* X4, const double* V4, int64_t n_real, int64
 int gs_cpu_accjerk_f32(const float* X4, const float* V4, int64_t n_real, int64_t i0, int64_t i1,
                        int32_t chunk, float cut2, float eps2, float* acc4, float* jerk4) {
   return accjerk_range<float>(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+}
+int gs_cpu_accjerk_idx_f64(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
+                           double* jerk4) {
+  return accjerk_idx<double>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
+}
+int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, float cut2, float eps2, float* acc4,
+                           float* jerk4) {
+  return accjerk_idx<float>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
 }
 double gs_cpu_hermite_first_dt_f64(const double* A4, const double* J4, int64_t n_real,
                                    double eta) {

@@ -4,6 +4,10 @@
 // control block (t, h, steps; gs_hermite.h). A step is four launches on one stream: control,
 // predict, evaluate (the hot acceleration+jerk kernel, nbody_hermite.hip), reduce + correct.
 // The step size and the time live on the device, so enqueueing steps never waits for one.
+// Block mode (gs_hermite_set_block): per-body times and levels, an active list and a second
+// control block; a block step is a chain of seven launches, and gs_hermite_step advances whole
+// macro steps of dt against a device-side target time, one status read per 32 chains.
+#include <cmath>
 #include <limits>
 #include <utility>
 #include <vector>
@@ -26,6 +30,11 @@ struct gs_hermite {
   std::vector<double> mass_host;
   double eta = 0.0, t_end = 0.0;
   bool has_end = false;
+  // block time steps (gs_hermite_set_block)
+  bool block = false;
+  int32_t max_level = 24, narrow_max = 0;
+  gs::HBlock blk{};
+  int64_t macro0 = 0;  // macro steps of dt the run stood at when its state was set
 };
 
 namespace {
@@ -48,6 +57,7 @@ gs::HArgs<T> make_args(const gs_hermite* h, int mode, bool phi) {
   a.phi = phi ? 1 : 0;
   a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
   a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
+  a.blk = h->blk;
   return a;
 }
 
@@ -132,10 +142,172 @@ int set_wgmin(gs_hermite* h, double first) {
   return 0;
 }
 
+// ---- block time steps ------------------------------------------------------------------
+
+int read_bctrl(gs_hermite* h, gs::HermiteBlockCtrl* c) {
+  GS_HIP(hipMemcpyAsync(c, h->blk.bc, sizeof(*c), hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int write_bctrl(gs_hermite* h, const gs::HermiteBlockCtrl& c) {
+  GS_HIP(hipMemcpyAsync(h->blk.bc, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));  // (c may be on the caller's frame)
+  return 0;
+}
+
+// The default narrow_max for n_pad bodies (a function of n and dtype only: it changes bits).
+int32_t default_narrow_max(const gs_hermite* h) {
+  // The measured crossover of the two evaluate paths, down to a power of two (docs/DESIGN.md
+  // §15): 4096 (fp32) and 2048 (fp64) at 65,536 bodies, 32,768 for both at 262,144. Between and
+  // beyond the measured sizes: n_pad / 8 from 262,144 up, n_pad / 16 (fp32), / 32 (fp64) below.
+  const int64_t div = h->n_pad >= 262144 ? 8 : (h->esz == 4 ? 16 : 32);
+  int64_t d = 1;
+  while (2 * d <= h->n_pad / div) d *= 2;
+  return (int32_t)d;
+}
+
+void free_block(gs_hermite* h) {
+  for (void* p : {(void*)h->blk.bc, (void*)h->blk.tb, (void*)h->blk.level, (void*)h->blk.list,
+                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ})
+    if (p) (void)hipFree(p);
+  h->blk = gs::HBlock{};
+}
+
+// (Re)allocate the narrow partial buffer for narrow_max slots.
+int set_narrow(gs_hermite* h, int32_t narrow_max) {
+  if (narrow_max < 0) narrow_max = default_narrow_max(h);
+  if (narrow_max > h->n_pad) narrow_max = (int32_t)h->n_pad;
+  GS_HIP(hipStreamSynchronize(h->stream));
+  if (h->blk.NA) GS_HIP(hipFree(h->blk.NA));
+  if (h->blk.NJ) GS_HIP(hipFree(h->blk.NJ));
+  h->blk.NA = h->blk.NJ = nullptr;
+  h->blk.cap = narrow_max;
+  h->narrow_max = narrow_max;
+  if (narrow_max > 0) {
+    const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->esz;
+    GS_HIP(hipMalloc(&h->blk.NA, bytes));
+    GS_HIP(hipMalloc(&h->blk.NJ, bytes));
+  }
+  gs::HermiteBlockCtrl c;
+  if (read_bctrl(h, &c)) return -1;
+  c.narrow_max = narrow_max;
+  return write_bctrl(h, c);
+}
+
+// Control block of a block run that stands at `macro` whole steps of dt, counters zero.
+int reset_bctrl(gs_hermite* h, int64_t macro) {
+  gs::HermiteBlockCtrl c{};
+  c.t_ticks = macro << h->max_level;
+  c.target = c.t_ticks;
+  c.dt_max = h->cfg.dt;
+  c.eta = h->eta;
+  c.L = h->max_level;
+  c.narrow_max = h->narrow_max;
+  h->macro0 = macro;
+  return write_bctrl(h, c);
+}
+
+template <typename T>
+int block_start_t(gs_hermite* h, int64_t macro) {
+  if (reset_bctrl(h, macro)) return -1;
+  const gs::HArgs<T> a = make_args<T>(h, gs::HM_STEP, false);
+  GS_HIP(gs::launch_block_init<T>(a, macro << h->max_level, h->stream));
+  return 0;
+}
+
+// Levels afresh from the carried a, j; every body stands at `macro` steps of dt.
+int block_start(gs_hermite* h, int64_t macro) {
+  return h->esz == 4 ? block_start_t<float>(h, macro) : block_start_t<double>(h, macro);
+}
+
+template <typename T>
+int block_chain(gs_hermite* h, const gs::HArgs<T>& a) {
+  GS_HIP(gs::launch_block_next<T>(a, h->stream));
+  GS_HIP(gs::launch_block_predict<T>(a, h->stream));
+  GS_HIP(gs::launch_block_narrow<T>(a, h->stream));
+  GS_HIP(gs::launch_block_wide<T>(a, h->ipl, h->groups, h->stream));
+  GS_HIP(gs::launch_block_correct<T>(a, h->stream));
+  return 0;
+}
+
+// n macro steps: chains in batches of 32 against the device-side target, one status read each.
+template <typename T>
+int block_step_t(gs_hermite* h, int32_t nsteps) {
+  gs::HermiteBlockCtrl c;
+  if (read_bctrl(h, &c)) return -1;
+  const int L = h->max_level;
+  int64_t target = ((c.t_ticks >> L) + nsteps) << L;
+  if (h->has_end) {
+    const int64_t end = (int64_t)llround(h->t_end / h->cfg.dt) << L;
+    if (target > end) target = end;
+  }
+  if (target <= c.t_ticks) return 0;
+  c.target = target;
+  if (write_bctrl(h, c)) return -1;
+  const gs::HArgs<T> a = make_args<T>(h, gs::HM_STEP, false);
+  while (c.t_ticks < target) {
+    const int64_t before = c.t_ticks;
+    for (int k = 0; k < 32; ++k)
+      if (block_chain<T>(h, a)) return -1;
+    if (read_bctrl(h, &c)) return -1;
+    if (c.t_ticks == before) {
+      gs_set_error("hermite block steps: no progress (body times out of step)");
+      return -1;
+    }
+  }
+  return 0;
+}
+
+template <typename T>
+int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
+                    double* jerk4, int32_t reps = 1, double* ms = nullptr) {
+  gs::HermiteBlockCtrl keep;
+  if (read_bctrl(h, &keep)) return -1;
+  gs::HermiteBlockCtrl c = keep;
+  c.n_act = n_idx;
+  c.path = path;
+  c.active = 1;
+  GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
+                        h->stream));
+  if (write_bctrl(h, c)) return -1;
+  gs::HArgs<T> a = make_args<T>(h, gs::HM_OUT, true);
+  a.XP = a.X;
+  a.VP = a.V;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ms) {
+    GS_HIP(hipEventCreate(&e0));
+    GS_HIP(hipEventCreate(&e1));
+    GS_HIP(hipEventRecord(e0, h->stream));
+  }
+  for (int32_t r = 0; r < reps; ++r) {
+    if (path == gs::HP_NARROW)
+      GS_HIP(gs::launch_block_narrow<T>(a, h->stream));
+    else
+      GS_HIP(gs::launch_block_wide<T>(a, h->ipl, h->groups, h->stream));
+    GS_HIP(gs::launch_block_correct<T>(a, h->stream));
+  }
+  if (ms) {
+    float t = 0.0f;
+    GS_HIP(hipEventRecord(e1, h->stream));
+    GS_HIP(hipEventSynchronize(e1));
+    GS_HIP(hipEventElapsedTime(&t, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    *ms = (double)t / reps;
+  }
+  if (download_rows<T>(h, h->a_out, n_idx, acc4, 4) ||
+      download_rows<T>(h, h->j_out, n_idx, jerk4, 4))
+    return -1;
+  return write_bctrl(h, keep);
+}
+
 int start_from_state(gs_hermite* h) {
   if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity())) return -1;
-  return h->esz == 4 ? eval_current<float>(h, gs::HM_INIT, false)
-                     : eval_current<double>(h, gs::HM_INIT, false);
+  if (h->esz == 4 ? eval_current<float>(h, gs::HM_INIT, false)
+                  : eval_current<double>(h, gs::HM_INIT, false))
+    return -1;
+  return h->block ? block_start(h, 0) : 0;
 }
 
 }  // namespace
@@ -230,6 +402,7 @@ int gs_hermite_destroy(gs_hermite* h) {
   for (void* p : {h->X, h->V, h->A, h->J, h->XP, h->VP, h->a_out, h->j_out, h->PA, h->PJ,
                   (void*)h->ctrl, (void*)h->wgmin, (void*)h->mass_dev, (void*)h->nonfinite})
     if (p) (void)hipFree(p);
+  free_block(h);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -297,8 +470,15 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
           : upload_rows<double>(h, h->V, vel, nullptr, 0.0))
     return -1;
   h->mass_host.assign(mass, mass + h->n);
+  // block mode: the run stands at a whole number of steps of dt (a synchronised state)
+  const int64_t macro = h->block ? (int64_t)llround(t / h->cfg.dt) : 0;
+  if (h->block && (double)macro * h->cfg.dt != t) {
+    gs_set_error("hermite block steps: the state's time must be a whole multiple of dt");
+    return -1;
+  }
   if (!acc || !jerk) {
     if (start_from_state(h)) return -1;
+    if (h->block && block_start(h, macro)) return -1;
     gs::HermiteCtrl c;
     if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
     return write_ctrl(h, t, 0, 0.0,
@@ -312,6 +492,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
           : upload_rows<double>(h, h->J, jerk, nullptr, 0.0))
     return -1;
   if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
+  if (h->block && block_start(h, macro)) return -1;  // (levels afresh until set_block_state)
   return write_ctrl(h, t, 0, 0.0,
                     dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity());
 }
@@ -345,6 +526,8 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
+  if (h->block)
+    return h->esz == 4 ? block_step_t<float>(h, nsteps) : block_step_t<double>(h, nsteps);
   return h->esz == 4 ? step_t<float>(h, nsteps) : step_t<double>(h, nsteps);
 }
 
@@ -357,6 +540,24 @@ int gs_hermite_sync(gs_hermite* h) {
 int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   if (!h || !out) { gs_set_error("hermite status: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
+  if (h->block) {
+    gs::HermiteBlockCtrl b;
+    if (read_bctrl(h, &b)) return -1;
+    *out = gs_hermite_info{};
+    const int64_t macro = b.t_ticks >> b.L;
+    out->time = b.dt_max * ldexp((double)b.t_ticks, -b.L);
+    out->dt_last = out->dt_next = b.dt_max;
+    out->dt_min = ldexp(b.dt_max, -b.level_max);
+    out->steps = macro - h->macro0;
+    out->finished = h->has_end && out->time >= h->t_end;
+    out->ipl = h->ipl;
+    out->block_steps = (int64_t)b.block_steps;
+    out->body_steps = (int64_t)b.body_steps;
+    out->level_clamped = (int64_t)b.level_clamped;
+    out->level_max = b.level_max;
+    out->narrow_max = b.narrow_max;
+    return 0;
+  }
   gs::HermiteCtrl c;
   if (read_ctrl(h, &c)) return -1;
   double next = c.dt_max;
@@ -375,7 +576,126 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   out->steps = (int64_t)c.steps;
   out->finished = c.has_end && c.t >= c.t_end;
   out->ipl = h->ipl;
+  out->block_steps = out->body_steps = out->level_clamped = 0;
+  out->level_max = out->narrow_max = 0;
   return 0;
+}
+
+int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
+  if (!h) { gs_set_error("hermite set_block: null argument"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (!on) {
+    GS_HIP(hipStreamSynchronize(h->stream));
+    free_block(h);
+    h->block = false;
+    return 0;
+  }
+  if (max_level < 0 || max_level > 40) {
+    gs_set_error("hermite block steps: max_level must be in 0..40");
+    return -1;
+  }
+  if (!(h->eta > 0.0)) { gs_set_error("hermite block steps need eta > 0"); return -1; }
+  if (h->has_end && (double)llround(h->t_end / h->cfg.dt) * h->cfg.dt != h->t_end) {
+    gs_set_error("hermite block steps: t_end must be a whole multiple of dt");
+    return -1;
+  }
+  GS_HIP(hipStreamSynchronize(h->stream));
+  free_block(h);
+  h->max_level = max_level;
+  const size_t np = (size_t)h->n_pad, wg = (size_t)nwg(h);
+  GS_HIP(hipMalloc((void**)&h->blk.bc, sizeof(gs::HermiteBlockCtrl)));
+  GS_HIP(hipMalloc((void**)&h->blk.tb, np * sizeof(int64_t)));
+  GS_HIP(hipMalloc((void**)&h->blk.level, np * sizeof(int32_t)));
+  GS_HIP(hipMalloc((void**)&h->blk.list, np * sizeof(int32_t)));
+  GS_HIP(hipMalloc((void**)&h->blk.wgcount, wg * sizeof(int32_t)));
+  GS_HIP(hipMalloc((void**)&h->blk.wgnext, wg * sizeof(int64_t)));
+  GS_HIP(hipMemsetAsync(h->blk.tb, 0, np * sizeof(int64_t), h->stream));
+  GS_HIP(hipMemsetAsync(h->blk.level, 0, np * sizeof(int32_t), h->stream));
+  GS_HIP(hipMemsetAsync(h->blk.list, 0, np * sizeof(int32_t), h->stream));
+  GS_HIP(hipMemsetAsync(h->blk.wgcount, 0, wg * sizeof(int32_t), h->stream));
+  h->blk.slice = gs::hermite_narrow_slice(h->n_pad);
+  h->blk.n_slices = (int32_t)((h->n_pad + h->blk.slice - 1) / h->blk.slice);
+  h->block = true;
+  h->narrow_max = 0;
+  if (reset_bctrl(h, 0)) return -1;
+  return set_narrow(h, -1);
+}
+
+int gs_hermite_set_block_tuning(gs_hermite* h, int32_t narrow_max) {
+  if (!h || !h->block) { gs_set_error("hermite block tuning: not in block mode"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return set_narrow(h, narrow_max);
+}
+
+int gs_hermite_get_block_state(gs_hermite* h, int64_t* tb, int32_t* level) {
+  if (!h || !h->block) { gs_set_error("hermite block state: not in block mode"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (tb)
+    GS_HIP(hipMemcpyAsync(tb, h->blk.tb, (size_t)h->n * sizeof(int64_t), hipMemcpyDeviceToHost,
+                          h->stream));
+  if (level)
+    GS_HIP(hipMemcpyAsync(level, h->blk.level, (size_t)h->n * sizeof(int32_t),
+                          hipMemcpyDeviceToHost, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int gs_hermite_set_block_state(gs_hermite* h, const int64_t* tb, const int32_t* level) {
+  if (!h || !h->block) { gs_set_error("hermite block state: not in block mode"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  gs::HermiteBlockCtrl c;
+  if (read_bctrl(h, &c)) return -1;
+  const int L = h->max_level;
+  std::vector<int32_t> lv((size_t)h->n);
+  std::vector<int64_t> tv((size_t)h->n);
+  if (!level) GS_HIP(hipMemcpy(lv.data(), h->blk.level, lv.size() * 4, hipMemcpyDeviceToHost));
+  if (!tb) GS_HIP(hipMemcpy(tv.data(), h->blk.tb, tv.size() * 8, hipMemcpyDeviceToHost));
+  int64_t tmin = std::numeric_limits<int64_t>::max();
+  for (int64_t i = 0; i < h->n; ++i) {
+    if (level) lv[(size_t)i] = level[i];
+    if (tb) tv[(size_t)i] = tb[i];
+    const int32_t k = lv[(size_t)i];
+    if (k < 0 || k > L || tv[(size_t)i] < 0 || (tv[(size_t)i] & (((int64_t)1 << (L - k)) - 1))) {
+      gs_set_error("hermite block state: level out of 0..max_level, or a body time that is no "
+                   "multiple of its step");
+      return -1;
+    }
+    if (tv[(size_t)i] < tmin) tmin = tv[(size_t)i];
+    if (k > c.level_max) c.level_max = k;
+  }
+  GS_HIP(hipMemcpyAsync(h->blk.level, lv.data(), lv.size() * 4, hipMemcpyHostToDevice, h->stream));
+  GS_HIP(hipMemcpyAsync(h->blk.tb, tv.data(), tv.size() * 8, hipMemcpyHostToDevice, h->stream));
+  c.t_ticks = tmin;
+  c.target = tmin;
+  return write_bctrl(h, c);  // (waits for the copies: lv, tv are on this frame)
+}
+
+int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                             double* acc4, double* jerk4) {
+  return gs_hermite_time_active(h, idx, n_idx, path, 1, nullptr, acc4, jerk4);
+}
+
+int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                           int32_t reps, double* ms, double* acc4, double* jerk4) {
+  if (!h || !h->block) { gs_set_error("hermite derivs_active: not in block mode"); return -1; }
+  if (reps < 1) reps = 1;
+  if (!idx || n_idx < 1 || n_idx > h->n || path < 0 || path > 2) {
+    gs_set_error("hermite derivs_active: bad arguments");
+    return -1;
+  }
+  for (int32_t k = 0; k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= h->n) {
+      gs_set_error("hermite derivs_active: index out of range");
+      return -1;
+    }
+  if (path == 0) path = n_idx <= h->narrow_max ? gs::HP_NARROW : gs::HP_WIDE;
+  if (path == gs::HP_NARROW && n_idx > h->narrow_max) {
+    gs_set_error("hermite derivs_active: narrow path needs n_idx <= narrow_max");
+    return -1;
+  }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return h->esz == 4 ? derivs_active_t<float>(h, idx, n_idx, path, acc4, jerk4, reps, ms)
+                     : derivs_active_t<double>(h, idx, n_idx, path, acc4, jerk4, reps, ms);
 }
 
 int64_t gs_hermite_count_nonfinite(gs_hermite* h) {

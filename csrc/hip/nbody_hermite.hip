@@ -18,6 +18,10 @@
 //     bits do not depend on IPL or on how many chunk groups the grid has.
 // Step chain (one stream, no host round trip): control (next h from the last step's
 // per-workgroup dt minima; advances t, steps) -> predict -> evaluate -> reduce + correct.
+// Block time steps (each body on its own step dt 2^-k; second half of this file): next-time
+// minima + control -> predict-all + mark -> compact (scan) -> evaluate of the active bodies,
+// narrow (hermite_narrow_kernel, parallel over j) or wide (the GATHER form of
+// hermite_eval_kernel) by n_act -> reduce + correct + new level of the active bodies.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -130,13 +134,22 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
 
 // EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
 // stores one partial per chunk: PA[c][i] = (ax, ay, az, sum mu/r), PJ[c][i] = (jx, jy, jz, 0).
-template <typename T, int IPL, bool PHI>
+// GATHER (a block step's wide path): lane slot s owns body list[s], the partials are stored per
+// slot and i-blocks beyond n_act exit; the j loop, hence a body's bits, is the same.
+template <typename T, int IPL, bool PHI, bool GATHER = false>
 __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int gated) {
   constexpr int TB = Tile<T>::kBodies;
   __shared__ __attribute__((aligned(16))) V4<T> tx[2][TB];
   __shared__ __attribute__((aligned(16))) V4<T> tv[2][TB];
   if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
   const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);
+  int64_t n_act = 0;
+  if constexpr (GATHER) {
+    const HermiteBlockCtrl* bc = a.blk.bc;
+    if (!bc->active || bc->path != HP_WIDE) return;
+    n_act = bc->n_act;
+    if (ib >= n_act) return;
+  }
   const int per = (a.n_chunks + (int)gridDim.y - 1) / (int)gridDim.y;
   const int c0 = (int)blockIdx.y * per;
   const int c1 = min(c0 + per, a.n_chunks);
@@ -150,8 +163,10 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int ga
   HState<T, IPL> st;
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
-    const V4<T> x = XP[ib + threadIdx.x + k * kBlock];
-    const V4<T> v = VP[ib + threadIdx.x + k * kBlock];
+    int64_t row = ib + threadIdx.x + k * kBlock;
+    if constexpr (GATHER) row = a.blk.list[row < n_act ? row : n_act - 1];  // (spare slots: a copy)
+    const V4<T> x = XP[row];
+    const V4<T> v = VP[row];
     st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
     st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
   }
@@ -355,6 +370,329 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T> a) {
   if (threadIdx.x == 0) a.wgmin[blockIdx.x] = dti;
 }
 
+
+// ---------------------------------------------------------------------------------------
+// Block time steps: body i stands at tb_i ticks and steps by 2^(L - level_i) ticks.
+
+__device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const long long o = __shfl_down((long long)v, off, 64);
+    v = o < v ? (int64_t)o : v;
+  }
+  return v;
+}
+
+__device__ __forceinline__ int wave_sum_i32(int v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// Seconds of a span of ticks: dt_max ticks 2^-L in fp64 (the run's dtype takes a cast of it).
+__device__ __forceinline__ double ticks_seconds(double dt_max, int64_t ticks, int L) {
+  return dt_max * ldexp((double)ticks, -L);
+}
+
+__device__ __forceinline__ bool body_due(const HBlock& b, int64_t i, int L, int64_t t_next) {
+  return b.tb[i] + ((int64_t)1 << (L - b.level[i])) == t_next;
+}
+
+// NEXT, stage 1: per-workgroup minimum of tb + step over the real bodies.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block_next_kernel(HArgs<T> a) {
+  __shared__ int64_t red[kBlock / 64];
+  const HBlock& b = a.blk;
+  const int L = b.bc->L;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int64_t v = INT64_MAX;
+  if (i < a.n_real) v = b.tb[i] + ((int64_t)1 << (L - b.level[i]));
+  v = wave_min_i64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) v = red[w] < v ? red[w] : v;
+    b.wgnext[blockIdx.x] = v;
+  }
+}
+
+// NEXT, stage 2 and CONTROL (one workgroup): t_next = the earliest due time; past the target the
+// chain's other kernels return at once.
+__global__ __launch_bounds__(kBlock) void block_ctrl_kernel(HermiteBlockCtrl* bc,
+                                                            const int64_t* wgnext, int nwg) {
+  __shared__ int64_t red[kBlock / 64];
+  int64_t m = INT64_MAX;
+  for (int k = threadIdx.x; k < nwg; k += kBlock) m = wgnext[k] < m ? wgnext[k] : m;
+  m = wave_min_i64(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int w = 1; w < kBlock / 64; ++w) m = red[w] < m ? red[w] : m;
+  if (bc->t_ticks >= bc->target || m > bc->target) {
+    bc->active = 0;
+    return;
+  }
+  bc->t_ticks = m;
+  bc->n_act = 0;
+  bc->path = 0;
+  bc->active = 1;
+}
+
+// PREDICT-ALL + MARK: every real body from its own tb to t_next; counts the due bodies of the
+// workgroup for the compaction.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T> a) {
+  __shared__ int cnt[kBlock / 64];
+  const HBlock& b = a.blk;
+  if (!b.bc->active) return;
+  const int L = b.bc->L;
+  const int64_t t_next = b.bc->t_ticks;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad: a multiple of 256)
+  V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp;
+  bool due = false;
+  if (i < a.n_real) {
+    due = body_due(b, i, L, t_next);
+    const T h = (T)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L);
+    const T h2 = (h * h) / T(2), h3 = (h * h * h) / T(6);
+    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
+    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
+    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
+    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
+    xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
+    xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
+    xp.w = x.w;
+    vp.x = v.x + (ac.x * h + jk.x * h2);
+    vp.y = v.y + (ac.y * h + jk.y * h2);
+    vp.z = v.z + (ac.z * h + jk.z * h2);
+  }
+  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
+  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
+  const int c = __popcll(__ballot(due));
+  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) b.wgcount[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+// COMPACT: the due bodies in ascending order, by a scan (workgroup offset = sum of the counts of
+// the workgroups before it; ballot prefix inside): no atomic append, so the list is the
+// oracle's. The last workgroup publishes n_act and picks the evaluate path.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T> a) {
+  __shared__ int red[kBlock / 64];
+  __shared__ int cnt[kBlock / 64];
+  const HBlock& b = a.blk;
+  HermiteBlockCtrl* bc = b.bc;
+  if (!bc->active) return;
+  int s = 0;
+  for (int k = threadIdx.x; k < (int)blockIdx.x; k += kBlock) s += b.wgcount[k];
+  s = wave_sum_i32(s);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool due = i < a.n_real && body_due(b, i, bc->L, bc->t_ticks);
+  const unsigned long long mask = __ballot(due);
+  if (lane == 0) {
+    red[wave] = s;
+    cnt[wave] = __popcll(mask);
+  }
+  __syncthreads();
+  const int base = red[0] + red[1] + red[2] + red[3];
+  int off = base;
+  for (int w = 0; w < wave; ++w) off += cnt[w];
+  if (due) b.list[off + __popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)i;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    const int n_act = base + cnt[0] + cnt[1] + cnt[2] + cnt[3];
+    bc->n_act = n_act;
+    bc->path = n_act <= bc->narrow_max ? HP_NARROW : HP_WIDE;
+    bc->block_steps += 1;
+    bc->body_steps += (unsigned long long)n_act;
+  }
+}
+
+// NARROW EVALUATE (n_act <= narrow_max): parallel over j. Grid (n_slices, passes): workgroup
+// (s, y) takes the j rows of slice s and the groups y, y + passes, ... of kNarrowGroup active
+// bodies. The group's predicted rows are wave-uniform (broadcast operands); the lanes stride
+// over the slice with coalesced 16-byte loads of (XP, VP), each summing its rows from zero in
+// j order; the lanes are folded by a fixed tree (shuffle-down 32..1 in the wave, then the
+// four waves in order through LDS) and one partial per (slice, slot) is stored. Slice length and
+// tree depend on n_pad only, so a body's bits depend neither on the other active bodies nor on
+// its slot. fp32 runs two i-bodies as 2-vectors (hinteract_pk).
+template <typename T, bool PHI>
+__global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T> a) {
+  constexpr int G = kNarrowGroup;
+  __shared__ T red[kBlock / 64][G][8];
+  const HBlock& b = a.blk;
+  if (!b.bc->active || b.bc->path != HP_NARROW) return;
+  const int n_act = min(b.bc->n_act, b.cap);
+  const int ngroups = (n_act + G - 1) / G;
+  const int64_t j0 = (int64_t)blockIdx.x * b.slice;
+  const int64_t j1 = min(j0 + (int64_t)b.slice, a.n_pad);
+  const V4<T>* XP = reinterpret_cast<const V4<T>*>(a.XP);
+  const V4<T>* VP = reinterpret_cast<const V4<T>*>(a.VP);
+  V4<T>* NA = reinterpret_cast<V4<T>*>(b.NA);
+  V4<T>* NJ = reinterpret_cast<V4<T>*>(b.NJ);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int g = blockIdx.y; g < ngroups; g += (int)gridDim.y) {
+    HState<T, G> st;
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      const int slot = min(g * G + k, n_act - 1);  // (spare slots of the last group: a copy)
+      const int64_t row = b.list[slot];
+      const V4<T> x = XP[row];
+      const V4<T> v = VP[row];
+      st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
+      st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+    }
+    hzero<T, G>(st);
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += kBlock) {
+      const V4<T> q = XP[j], p = VP[j];
+      hinteract_all<T, G, PHI>(st, q, p, a.cut2, a.eps2);
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      T v[7] = {st.ax[k], st.ay[k], st.az[k], st.ph[k], st.jx[k], st.jy[k], st.jz[k]};
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_down(v[c], off, 64);
+        if (lane == 0) red[wave][k][c] = v[c];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < G && g * G + (int)threadIdx.x < n_act) {
+      const int k = threadIdx.x;
+      T v[7];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) v[c] = ((red[0][k][c] + red[1][k][c]) + red[2][k][c]) + red[3][k][c];
+      V4<T> oa, oj;
+      oa.x = v[0]; oa.y = v[1]; oa.z = v[2]; oa.w = v[3];
+      oj.x = v[4]; oj.y = v[5]; oj.z = v[6]; oj.w = T(0);
+      const int64_t o = (int64_t)blockIdx.x * b.cap + (g * G + k);
+      NA[o] = oa;
+      NJ[o] = oj;
+    }
+    __syncthreads();
+  }
+}
+
+// REDUCE + CORRECT + NEW LEVEL, one thread per slot of the active list: the slice partials in
+// slice order (narrow) or the chunk partials in chunk order (wide), then the corrector over the
+// body's own h, Aarseth's dt_want and the level rule: any number of halvings (capped at L), at
+// most one doubling and only where t_next allows the doubled step. HM_OUT: the sums go to
+// a_out / j_out [slot] and nothing else is touched.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T> a) {
+  const HBlock& b = a.blk;
+  HermiteBlockCtrl* bc = b.bc;
+  if (!bc->active) return;
+  const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (s >= bc->n_act) return;
+  T a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
+  if (bc->path == HP_NARROW) {
+    const V4<T>* NA = reinterpret_cast<const V4<T>*>(b.NA);
+    const V4<T>* NJ = reinterpret_cast<const V4<T>*>(b.NJ);
+#pragma unroll 8
+    for (int c = 0; c < b.n_slices; ++c) {  // (unrolled: the loads of 8 slices are in flight)
+      const V4<T> pa = NA[(int64_t)c * b.cap + s];
+      const V4<T> pj = NJ[(int64_t)c * b.cap + s];
+      a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
+      j1x += pj.x; j1y += pj.y; j1z += pj.z;
+    }
+  } else {
+    const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
+    const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
+    for (int c = 0; c < a.n_chunks; ++c) {
+      const V4<T> pa = PA[(int64_t)c * a.n_pad + s];
+      const V4<T> pj = PJ[(int64_t)c * a.n_pad + s];
+      a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
+      j1x += pj.x; j1y += pj.y; j1z += pj.z;
+    }
+  }
+  if (a.mode == HM_OUT) {
+    V4<T> oa, oj;
+    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = -sp;
+    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
+    reinterpret_cast<V4<T>*>(a.a_out)[s] = oa;
+    reinterpret_cast<V4<T>*>(a.j_out)[s] = oj;
+    return;
+  }
+  const int64_t i = b.list[s];
+  const int L = bc->L;
+  const int64_t t_next = bc->t_ticks;
+  const double dt_max = bc->dt_max, eta = bc->eta;
+  const double hd = ticks_seconds(dt_max, t_next - b.tb[i], L);
+  const T h = (T)hd;
+  const T hh = h / T(2), h12 = (h * h) / T(12);
+  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
+  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
+  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
+  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
+  const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
+  V4<T> v1, x1;
+  v1.x = v.x + ((a0.x + a1x) * hh + (j0.x - j1x) * h12);
+  v1.y = v.y + ((a0.y + a1y) * hh + (j0.y - j1y) * h12);
+  v1.z = v.z + ((a0.z + a1z) * hh + (j0.z - j1z) * h12);
+  v1.w = T(0);
+  x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - a1x) * h12);
+  x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - a1y) * h12);
+  x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - a1z) * h12);
+  x1.w = x.w;
+  X[i] = x1;
+  V[i] = v1;
+  V4<T> oa, oj;
+  oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = T(0);
+  oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
+  A[i] = oa;
+  J[i] = oj;
+  b.tb[i] = t_next;
+  // Aarseth's criterion (as hermite_reduce_kernel), per body
+  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
+  const double da[3] = {(double)a0.x - (double)a1x, (double)a0.y - (double)a1y,
+                        (double)a0.z - (double)a1z};
+  const double jo[3] = {j0.x, j0.y, j0.z}, jn[3] = {j1x, j1y, j1z};
+  double s2[3], s3[3];
+  for (int d = 0; d < 3; ++d) {
+    const double a2 = (-6.0 * da[d] - hd * (4.0 * jo[d] + 2.0 * jn[d])) * ih2;
+    s3[d] = (12.0 * da[d] + 6.0 * hd * (jo[d] + jn[d])) * ih3;
+    s2[d] = a2 + hd * s3[d];
+  }
+  const double an = norm3(a1x, a1y, a1z), jnn = norm3(j1x, j1y, j1z);
+  const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
+  const double want = sqrt(eta * (an * n2 + jnn * jnn) / (jnn * n3 + n2 * n2));
+  int k = b.level[i];
+  if (jnn > 0.0 && isfinite(want)) {
+    const double dtk = ldexp(dt_max, -k);
+    if (want < dtk) {
+      while (k < L && ldexp(dt_max, -k) > want) ++k;
+      if (ldexp(dt_max, -k) > want) atomicAdd(&bc->level_clamped, 1ull);
+    } else if (k > 0 && want >= 2.0 * dtk &&
+               (t_next & (((int64_t)1 << (L - k + 1)) - 1)) == 0) {
+      --k;
+    }
+  }
+  b.level[i] = k;
+  if (k > bc->level_max) atomicMax(&bc->level_max, k);
+}
+
+// START: the level of every real body from the carried a, j (the smallest k with
+// dt_max 2^-k <= (eta / 2) |a| / |j|, capped at L; 0 where |j| = 0 or the ratio is not finite),
+// all standing at tick t0.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T> a, int64_t t0) {
+  const HBlock& b = a.blk;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n_pad) return;
+  int k = 0;
+  if (i < a.n_real) {
+    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
+    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const double an = norm3(ac.x, ac.y, ac.z), jn = norm3(jk.x, jk.y, jk.z);
+    const double want = 0.5 * b.bc->eta * an / jn;
+    if (jn > 0.0 && isfinite(want))
+      while (k < b.bc->L && ldexp(b.bc->dt_max, -k) > want) ++k;
+    if (k > b.bc->level_max) atomicMax(&b.bc->level_max, k);
+  }
+  b.tb[i] = t0;
+  b.level[i] = k;
+}
+
 // ---------------------------------------------------------------------------------------
 // Host launchers.
 
@@ -411,11 +749,98 @@ hipError_t launch_hermite_reduce(const HArgs<T>& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+int32_t hermite_narrow_slice(int64_t n_pad) {
+  // At most 64 slices of at least 1024 rows (4 per lane, which amortise the fold of the lanes;
+  // 64 partials keep the reduce's chain of dependent adds short): a function of n_pad alone,
+  // since it fixes the bits.
+  return (int32_t)round_up(n_pad / 64 > 4 * kBlock ? n_pad / 64 : 4 * kBlock, kBlock);
+}
+
+template <typename T>
+hipError_t launch_block_next(const HArgs<T>& a, hipStream_t s) {
+  const unsigned nwg = (unsigned)(a.n_pad / kBlock);
+  hipLaunchKernelGGL((block_next_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(block_ctrl_kernel, dim3(1), dim3(kBlock), 0, s, a.blk.bc, a.blk.wgnext,
+                     (int)nwg);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_predict(const HArgs<T>& a, hipStream_t s) {
+  const unsigned nwg = (unsigned)(a.n_pad / kBlock);
+  hipLaunchKernelGGL((block_predict_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((block_compact_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_narrow(const HArgs<T>& a, hipStream_t s) {
+  const HBlock& b = a.blk;
+  if (b.cap < 1) return hipSuccess;  // (narrow_max 0: every step is wide)
+  if (b.slice < kBlock || b.slice % kBlock || (int64_t)b.n_slices * b.slice < a.n_pad ||
+      !b.NA || !b.NJ)
+    return hipErrorInvalidValue;
+  const int groups = (b.cap + kNarrowGroup - 1) / kNarrowGroup;
+  const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
+  if (a.phi)
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T, int IPL>
+static hipError_t launch_wide_t(const HArgs<T>& a, int groups, hipStream_t s) {
+  const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
+  if (a.phi)
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true>), grid, dim3(kBlock), 0, s, a, 0);
+  else
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true>), grid, dim3(kBlock), 0, s, a, 0);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_wide(const HArgs<T>& a, int ipl, int groups, hipStream_t s) {
+  if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
+      (int64_t)a.n_chunks * a.chunk != a.n_pad || !a.blk.bc || !a.blk.list)
+    return hipErrorInvalidValue;
+  if (groups < 1) groups = 1;
+  if (groups > a.n_chunks) groups = a.n_chunks;
+  switch (ipl) {
+    case 1: return launch_wide_t<T, 1>(a, groups, s);
+    case 2: return launch_wide_t<T, 2>(a, groups, s);
+    case 4:
+      if constexpr (sizeof(T) == 4) return launch_wide_t<T, 4>(a, groups, s);
+      return hipErrorInvalidValue;
+    default: return hipErrorInvalidValue;
+  }
+}
+
+template <typename T>
+hipError_t launch_block_correct(const HArgs<T>& a, hipStream_t s) {
+  hipLaunchKernelGGL((block_correct_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
+                     0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_block_init(const HArgs<T>& a, int64_t t0, hipStream_t s) {
+  hipLaunchKernelGGL((block_init_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0,
+                     s, a, t0);
+  return hipGetLastError();
+}
+
 #define GS_HERMITE_INSTANTIATE(T)                                                          \
   template hipError_t launch_hermite_ctrl<T>(const HArgs<T>&, hipStream_t);                \
   template hipError_t launch_hermite_predict<T>(const HArgs<T>&, hipStream_t);             \
   template hipError_t launch_hermite_eval<T>(const HArgs<T>&, int, int, bool, hipStream_t); \
-  template hipError_t launch_hermite_reduce<T>(const HArgs<T>&, hipStream_t);
+  template hipError_t launch_hermite_reduce<T>(const HArgs<T>&, hipStream_t);             \
+  template hipError_t launch_block_next<T>(const HArgs<T>&, hipStream_t);                  \
+  template hipError_t launch_block_predict<T>(const HArgs<T>&, hipStream_t);               \
+  template hipError_t launch_block_narrow<T>(const HArgs<T>&, hipStream_t);                \
+  template hipError_t launch_block_wide<T>(const HArgs<T>&, int, int, hipStream_t);        \
+  template hipError_t launch_block_correct<T>(const HArgs<T>&, hipStream_t);               \
+  template hipError_t launch_block_init<T>(const HArgs<T>&, int64_t, hipStream_t);
 GS_HERMITE_INSTANTIATE(float)
 GS_HERMITE_INSTANTIATE(double)
 

@@ -159,6 +159,14 @@ int gs_cpu_accjerk_f64(const double* X4, const double* V4, int64_t n_real, int64
                        int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4);
 int gs_cpu_accjerk_f32(const float* X4, const float* V4, int64_t n_real, int64_t i0, int64_t i1,
                        int32_t chunk, float cut2, float eps2, float* acc4, float* jerk4);
+// The same sums for the n_idx bodies idx[k] (a block step's active set, any order): row k of
+// acc4 / jerk4 belongs to body idx[k] and is bit-equal to its row of gs_cpu_accjerk_*.
+int gs_cpu_accjerk_idx_f64(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
+                           double* jerk4);
+int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, float cut2, float eps2, float* acc4,
+                           float* jerk4);
 // One 4th-order Hermite step of size h on the n_real bodies, in place: predict, evaluate at the
 // predicted state, correct; A4 / J4 carry the derivatives from step to step (scratch: 4 arrays
 // of n_real * 4). *dt_min_out (if given and eta > 0) gets min_i of Aarseth's criterion
@@ -285,6 +293,12 @@ typedef struct gs_hermite_info {
   int64_t steps;    // steps taken (steps enqueued past t_end are no-ops and not counted)
   int32_t finished; // t_end is set and reached
   int32_t ipl;      // resolved i-bodies per lane
+  // block mode (0 otherwise): `steps` above then counts macro steps of dt
+  int64_t block_steps;    // block steps taken
+  int64_t body_steps;     // sum of their active bodies (pair evaluations = body_steps * n)
+  int64_t level_clamped;  // times a body wanted a step below dt 2^-max_level
+  int32_t level_max;      // deepest level any body has had
+  int32_t narrow_max;     // active-set size up to which the j-parallel evaluate runs
 } gs_hermite_info;
 int gs_hermite_create(const gs_config* cfg, gs_hermite** out);
 int gs_hermite_destroy(gs_hermite* h);
@@ -310,6 +324,31 @@ int gs_hermite_step(gs_hermite* h, int32_t nsteps);
 int gs_hermite_sync(gs_hermite* h);
 int gs_hermite_status(gs_hermite* h, gs_hermite_info* out);  // waits for the enqueued steps
 int64_t gs_hermite_count_nonfinite(gs_hermite* h);
+// Individual block time steps (Makino 1991). Body i steps by dt 2^-k_i (k_i in 0..max_level,
+// max_level in 0..40), time is an integer count of ticks of dt 2^-max_level, and a block step
+// predicts every body to the earliest due time, evaluates and corrects the bodies due then.
+// Needs eta > 0 and t_end (if any) a whole multiple of dt; call after set_adaptive and before
+// the state is set. gs_hermite_step(h, n) then advances n macro steps of dt (every multiple of
+// dt synchronises all bodies): it enqueues block-step chains against a device-side target time
+// and reads the status back once per 32 chains.
+int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level);
+// narrow_max: active sets up to this size take the j-parallel evaluate kernel, larger ones the
+// gathered i-owned kernel (0: always the latter; n: always the former; < 0: the default for
+// n and dtype). It changes the summation order, hence bits; (re)allocates the partial buffer.
+int gs_hermite_set_block_tuning(gs_hermite* h, int32_t narrow_max);
+// Per-body time (ticks) and level, n each (either may be NULL). Setting them makes the run
+// stand at min tb; the carried a, j stay as they are.
+int gs_hermite_get_block_state(gs_hermite* h, int64_t* tb, int32_t* level);
+int gs_hermite_set_block_state(gs_hermite* h, const int64_t* tb, const int32_t* level);
+// (ax, ay, az, phi) and (jx, jy, jz, 0) of the n_idx listed bodies (ascending or not, each
+// < n) at the current (x, v) through the block path's evaluate and reduce; row k belongs to
+// idx[k]. path: 0 by narrow_max, 1 narrow (n_idx <= narrow_max), 2 wide.
+int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                             double* acc4, double* jerk4);
+// The same, `reps` times back to back between two events: *ms (if given) gets the milliseconds
+// per evaluate + reduce (bench/hermite_rate.py --active-sweep); acc4 / jerk4 may be NULL.
+int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                           int32_t reps, double* ms, double* acc4, double* jerk4);
 
 // Virtual ranks on one device: shards[r] created with rank r of P; steps all of them in
 // lockstep with the all-gather done by device copies (the RCCL schedule without RCCL).

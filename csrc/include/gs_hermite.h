@@ -21,6 +21,39 @@ struct HermiteCtrl {
   int32_t active;  // 1 while the chain of the current launch takes a step, 0 once t >= t_end
 };
 
+// Control block of a block-step run (individual steps dt_max 2^-k): time is a count of ticks of
+// dt_max 2^-L. The chain's kernels read it on the device and return at once when there is
+// nothing for them to do (the target time is reached, or the step takes the other evaluate path).
+struct HermiteBlockCtrl {
+  int64_t t_ticks;   // time reached
+  int64_t target;    // the chain stops here (a multiple of 2^L: a macro step boundary)
+  double dt_max, eta;
+  unsigned long long block_steps, body_steps, level_clamped;
+  int32_t L;           // max_level
+  int32_t level_max;   // deepest level any body has had
+  int32_t n_act;       // size of the active list of the current block step
+  int32_t narrow_max;  // n_act <= narrow_max: narrow path
+  int32_t path;        // HP_* of the current block step
+  int32_t active;      // 1 while the current chain takes a block step
+};
+enum { HP_NARROW = 1, HP_WIDE = 2 };
+
+// Per-body block-step state and the work arrays of one block step.
+struct HBlock {
+  HermiteBlockCtrl* bc;
+  int64_t* tb;       // [n_pad] body time (ticks), a multiple of the body's step 2^(L - level)
+  int32_t* level;    // [n_pad]
+  int32_t* list;     // [n_pad] active bodies, ascending
+  int32_t* wgcount;  // [n_pad / 256] active bodies per workgroup of the predict kernel
+  int64_t* wgnext;   // [n_pad / 256] per-workgroup min of tb + step
+  void *NA, *NJ;     // narrow partials [n_slices][cap] rows of 4
+  int32_t slice;     // j rows per slice (a multiple of 256; depends on n_pad only)
+  int32_t n_slices;
+  int32_t cap;       // slots of the narrow partial buffer (= narrow_max)
+};
+
+constexpr int kNarrowGroup = 4;  // active bodies a narrow workgroup carries per pass
+
 // What the reduce kernel does with the summed derivatives.
 enum { HM_STEP = 0,   // corrector: x, v, a, j <- corrected; per-workgroup min of dt_i
        HM_INIT = 1,   // a, j <- sums; per-workgroup min of (eta / 2) |a| / |j|
@@ -42,6 +75,7 @@ struct HArgs {
   int32_t mode;      // HM_*
   int32_t phi;       // evaluate: accumulate the potential sum too
   T cut2, eps2;
+  HBlock blk;        // block-step mode (all null otherwise)
 };
 
 template <typename T>
@@ -54,6 +88,24 @@ template <typename T>
 hipError_t launch_hermite_eval(const HArgs<T>& a, int ipl, int groups, bool gated, hipStream_t s);
 template <typename T>
 hipError_t launch_hermite_reduce(const HArgs<T>& a, hipStream_t s);
+// Block-step chain (hermite.hip enqueues them in this order, all on one stream):
+// next-time minima, control, predict-all + mark, compact, narrow evaluate, wide (gathered)
+// evaluate, reduce + correct + new level. mode of the last: HM_STEP or HM_OUT.
+template <typename T>
+hipError_t launch_block_next(const HArgs<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_predict(const HArgs<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_narrow(const HArgs<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_wide(const HArgs<T>& a, int ipl, int groups, hipStream_t s);
+template <typename T>
+hipError_t launch_block_correct(const HArgs<T>& a, hipStream_t s);
+// Levels and times of a run that starts from the carried a, j at tick t0.
+template <typename T>
+hipError_t launch_block_init(const HArgs<T>& a, int64_t t0, hipStream_t s);
+// j rows per narrow slice for n_pad bodies.
+int32_t hermite_narrow_slice(int64_t n_pad);
 // ipl values the evaluate kernel is compiled for (fp32: 1, 2, 4; fp64: 1, 2).
 bool hermite_ipl_ok(int fp64, int ipl);
 

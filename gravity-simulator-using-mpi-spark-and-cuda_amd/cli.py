@@ -43,6 +43,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "criterion; --dt is then the largest step); 0 = fixed step")
     p.add_argument("--t-end", dest="t_end", type=float, default=d.t_end,
                    help="hermite: stop at this time [s], reached exactly (--steps caps the count)")
+    p.add_argument("--block-steps", dest="block_steps", action="store_true",
+                   default=d.block_steps,
+                   help="hermite: individual block time steps dt 2^-k per body (needs --eta > 0; "
+                        "--steps then counts macro steps of --dt)")
+    p.add_argument("--max-level", dest="max_level", type=int, default=d.max_level,
+                   help="hermite block steps: the deepest level k (0..40)")
     p.add_argument("--kernel", choices=["auto", "lds", "smem", "mfma"], default=d.kernel,
                    help="GPU force kernel: lds (LDS-DMA j tiles), smem (SGPR j stream), mfma "
                         "(experimental fp32: r^2 on the matrix cores, re-centred; slower)")
@@ -118,7 +124,8 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
     return SimConfig(n=a.n, dt=a.dt, steps=a.steps, dtype=a.dtype, device=a.device, init=a.init,
                      seed=a.seed, G=a.G, cutoff=a.cutoff, softening=a.softening,
                      cutoff_mode=a.cutoff_mode, integrator=a.integrator, eta=a.eta,
-                     t_end=a.t_end, kernel=a.kernel,
+                     t_end=a.t_end, block_steps=a.block_steps, max_level=a.max_level,
+                     kernel=a.kernel,
                      mode=a.mode, ipl=a.ipl, chunk=a.chunk, graph=a.graph, graph_comm=a.graph_comm,
                      strategy=a.strategy, step_timeout_s=a.step_timeout_s, overlap=a.overlap,
                      threads=a.threads,

@@ -40,6 +40,9 @@ class SimConfig:
     eta: float = 0.0              # hermite: Aarseth accuracy parameter of the shared adaptive
                                   # step (0 = fixed step dt; then dt is the step's ceiling)
     t_end: Optional[float] = None  # hermite: stop at this time [s] (steps caps the step count)
+    block_steps: bool = False     # hermite: individual block time steps dt 2^-k per body (needs
+                                  # eta > 0); `steps` then counts macro steps of dt
+    max_level: int = 24           # hermite block steps: deepest level k (0..40)
     kernel: str = "auto"          # GPU j-source variant: lds | smem
     mode: str = "auto"            # GPU schedule: fused | split | sym (Newton-3, fp32)
     ipl: int = 0                  # i-bodies per lane (0 = auto)
@@ -110,6 +113,16 @@ class SimConfig:
             raise ValueError(f"integrator must be one of {INTEGRATORS}")
         if self.integrator != "hermite" and (self.eta != 0 or self.t_end is not None):
             raise ValueError("eta and t_end belong to integrator hermite")
+        if self.integrator != "hermite" and self.block_steps:
+            raise ValueError("block_steps belongs to integrator hermite")
+        if self.block_steps:
+            if not self.eta > 0:
+                raise ValueError("block steps need eta > 0")
+            if not 0 <= self.max_level <= 40:
+                raise ValueError("max_level must be in 0..40")
+            if self.t_end is not None and self.dt > 0 and \
+                    round(self.t_end / self.dt) * self.dt != self.t_end:
+                raise ValueError("block steps: t_end must be a whole multiple of dt")
         if self.integrator == "hermite":
             if not self.eta >= 0:
                 raise ValueError("eta must be >= 0")

@@ -51,6 +51,8 @@ class GsHermiteInfo(ctypes.Structure):
     _fields_ = [
         ("time", c_double), ("dt_last", c_double), ("dt_next", c_double), ("dt_min", c_double),
         ("steps", c_int64), ("finished", c_int32), ("ipl", c_int32),
+        ("block_steps", c_int64), ("body_steps", c_int64), ("level_clamped", c_int64),
+        ("level_max", c_int32), ("narrow_max", c_int32),
     ]
 
 
@@ -136,6 +138,8 @@ def cpu_lib():
                  [P, P, P, c_int64, c_int64, c_int64, c_int32, T, T, T])
             _sig(lib, f"gs_cpu_accjerk_{t}", c_int32,
                  [P, P, c_int64, c_int64, c_int64, c_int32, T, T, P, P])
+            _sig(lib, f"gs_cpu_accjerk_idx_{t}", c_int32,
+                 [P, P, c_int64, POINTER(c_int32), c_int64, c_int32, T, T, P, P])
             _sig(lib, f"gs_cpu_hermite_step_{t}", c_int32,
                  [P, P, P, P, P, c_int64, c_int32, c_double, T, T, c_double, _PD])
             _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, c_int64, c_double])
@@ -217,6 +221,14 @@ def hip_lib():
         _sig(lib, "gs_hermite_sync", c_int32, [S])
         _sig(lib, "gs_hermite_status", c_int32, [S, POINTER(GsHermiteInfo)])
         _sig(lib, "gs_hermite_count_nonfinite", c_int64, [S])
+        _sig(lib, "gs_hermite_set_block", c_int32, [S, c_int32, c_int32])
+        _sig(lib, "gs_hermite_set_block_tuning", c_int32, [S, c_int32])
+        _sig(lib, "gs_hermite_get_block_state", c_int32, [S, POINTER(c_int64), POINTER(c_int32)])
+        _sig(lib, "gs_hermite_set_block_state", c_int32, [S, POINTER(c_int64), POINTER(c_int32)])
+        _sig(lib, "gs_hermite_derivs_active", c_int32, [S, POINTER(c_int32), c_int32, c_int32,
+                                                        _PD, _PD])
+        _sig(lib, "gs_hermite_time_active", c_int32, [S, POINTER(c_int32), c_int32, c_int32,
+                                                      c_int32, _PD, _PD, _PD])
         _sig(lib, "gs_group_step", c_int32, [POINTER(S), c_int32, c_int32])
         _sig(lib, "gs_rccl_unique_id", c_int32, [c_void_p])
         _sig(lib, "gs_stepper_comm_init", c_int32, [S, c_void_p, c_int32, c_int32])

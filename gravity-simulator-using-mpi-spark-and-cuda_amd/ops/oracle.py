@@ -250,3 +250,121 @@ def gauss_seidel_step(pos, vel, mass, dt, nranks, G=G_SI, cutoff=1e-10):
             local[i] = local[i] + v[i] * dt
             new_x[i] = local[i]
     return new_x, v
+
+
+# ---- Hermite with individual block time steps ------------------------------------------------
+def acc_jerk_rows(pos, vel, mass, idx, G: float = G_SI, cutoff: float = 1e-10,
+                  softening: float = 0.0):
+    """acc_jerk() of the bodies `idx` only, against all bodies: (len(idx), 3) each."""
+    pos = np.asarray(pos, dtype=np.float64)
+    vel = np.asarray(vel, dtype=np.float64)
+    mu = G * np.asarray(mass, dtype=np.float64)
+    idx = np.asarray(idx, dtype=np.int64)
+    acc, jerk = np.zeros((len(idx), 3)), np.zeros((len(idx), 3))
+    for b0 in range(0, len(idx), 256):
+        rows = idx[b0:b0 + 256]
+        d = pos[None, :, :] - pos[rows, None, :]
+        w = vel[None, :, :] - vel[rows, None, :]
+        r2 = (d * d).sum(-1) + softening * softening
+        ok = r2 >= cutoff * cutoff
+        inv = np.zeros_like(r2)
+        inv[ok] = 1.0 / np.sqrt(r2[ok])
+        inv2 = inv * inv
+        s = mu[None, :] * inv * inv2
+        al = 3.0 * (d * w).sum(-1) * inv2
+        acc[b0:b0 + 256] = (s[:, :, None] * d).sum(1)
+        jerk[b0:b0 + 256] = (s[:, :, None] * (w - al[:, :, None] * d)).sum(1)
+    return acc, jerk
+
+
+def hermite_dt_bodies(a0, j0, a1, j1, h, eta):
+    """hermite_dt()'s criterion per body, h (m,) each body's own step: (dt_want, valid) with
+    valid False where |j1| = 0 or the ratio is not finite."""
+    h = np.asarray(h, dtype=np.float64)[:, None]
+    da = a0 - a1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a2 = (-6.0 * da - h * (4.0 * j0 + 2.0 * j1)) / h ** 2
+        a3 = (12.0 * da + 6.0 * h * (j0 + j1)) / h ** 3
+        a2p = a2 + h * a3
+        nrm = lambda y: np.sqrt((y * y).sum(1))  # noqa: E731
+        an, jn, n2, n3 = nrm(a1), nrm(j1), nrm(a2p), nrm(a3)
+        dt = np.sqrt(eta * (an * n2 + jn * jn) / (jn * n3 + n2 * n2))
+    return dt, (jn > 0) & np.isfinite(dt)
+
+
+def block_first_levels(a, j, dt, eta, max_level):
+    """Starting level per body: the smallest k with dt 2^-k <= (eta / 2) |a| / |j|, capped at
+    max_level; level 0 where |j| = 0 or the ratio is not finite."""
+    an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        want = 0.5 * eta * an / jn
+    ok = (jn > 0) & np.isfinite(want)
+    lev = np.zeros(len(an), dtype=np.int32)
+    for i in np.nonzero(ok)[0]:
+        k = 0
+        while k < max_level and np.ldexp(dt, -k) > want[i]:
+            k += 1
+        lev[i] = k
+    return lev
+
+
+def block_new_level(k, dt_want, valid, t_next, dt, max_level):
+    """The level rule of one active body after its step to t_next (ticks): (new k, clamped)."""
+    if not valid:
+        return k, False
+    if dt_want < np.ldexp(dt, -k):
+        while k < max_level and np.ldexp(dt, -k) > dt_want:
+            k += 1
+        return k, bool(np.ldexp(dt, -k) > dt_want)
+    if k > 0 and dt_want >= 2.0 * np.ldexp(dt, -k) and t_next % (1 << (max_level - k + 1)) == 0:
+        return k - 1, False
+    return k, False
+
+
+def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI, cutoff=1e-10,
+                           softening=0.0, check=None):
+    """4th-order Hermite with individual block time steps (Makino 1991): body i steps by
+    dt 2^-k_i, time is an integer count of ticks of dt 2^-max_level, only the bodies that are due
+    are evaluated (against every body predicted to that time) and corrected. t_end must be a
+    whole multiple of dt; every multiple of dt synchronises all bodies. `check(tb, level)` is
+    called after every block step. Returns (pos, vel, levels, [(t_ticks, n_active)],
+    level_clamped)."""
+    if not eta > 0:
+        raise ValueError("block steps need eta > 0")
+    L = int(max_level)
+    if not 0 <= L <= 40:
+        raise ValueError("max_level must be in 0..40")
+    macro = int(round(t_end / dt))
+    if macro * dt != t_end:
+        raise ValueError("t_end must be a whole multiple of dt")
+    x = np.array(pos, dtype=np.float64, copy=True)
+    v = np.array(vel, dtype=np.float64, copy=True)
+    n = x.shape[0]
+    a, j = acc_jerk(x, v, mass, G, cutoff, softening)
+    tb = np.zeros(n, dtype=np.int64)
+    lev = block_first_levels(a, j, dt, eta, L)
+    end = macro << L
+    log, clamped = [], 0
+    while tb.min() < end:
+        stp = np.int64(1) << (L - lev).astype(np.int64)
+        t_next = int((tb + stp).min())
+        act = np.nonzero(tb + stp == t_next)[0]
+        h = dt * np.ldexp((t_next - tb).astype(np.float64), -L)
+        hc = h[:, None]
+        xp = x + (v * hc + (a * (hc * hc / 2) + j * (hc * hc * hc / 6)))
+        vp = v + (a * hc + j * (hc * hc / 2))
+        a1, j1 = acc_jerk_rows(xp, vp, mass, act, G, cutoff, softening)
+        ha = hc[act]
+        a0, j0, v0 = a[act], j[act], v[act]
+        v1 = v0 + ((a0 + a1) * (ha / 2) + (j0 - j1) * (ha * ha / 12))
+        x[act] = x[act] + ((v0 + v1) * (ha / 2) + (a0 - a1) * (ha * ha / 12))
+        v[act], a[act], j[act] = v1, a1, j1
+        want, valid = hermite_dt_bodies(a0, j0, a1, j1, h[act], eta)
+        tb[act] = t_next
+        for m, i in enumerate(act):
+            lev[i], c = block_new_level(int(lev[i]), want[m], bool(valid[m]), t_next, dt, L)
+            clamped += c
+        log.append((t_next, int(len(act))))
+        if check is not None:
+            check(tb, lev)
+    return x, v, lev.copy(), log, clamped

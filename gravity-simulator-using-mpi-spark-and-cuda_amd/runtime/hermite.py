@@ -13,6 +13,12 @@ a1, j1 at (xp, vp); correct v1 = v + (a + a1) h/2 + (j - j1) h^2/12,
 x1 = x + (v + v1) h/2 + (a - a1) h^2/12; a1, j1 become the next step's a, j. With eta > 0 every
 step takes h = min(dt, min_i dt_i) of Aarseth's criterion; with t_end set the last step is cut
 to reach it exactly and further steps are no-ops.
+
+Block mode (cfg.block_steps; Makino 1991): body i steps by dt 2^-k_i, time is an integer count
+of ticks of dt 2^-max_level, and a block step predicts every body to the earliest due time,
+evaluates the due bodies against all and corrects them (the rules: ops/oracle.py
+simulate_hermite_block). step(n) then advances n macro steps of dt, after each of which all
+bodies stand at the same time.
 """
 from __future__ import annotations
 
@@ -38,6 +44,13 @@ class HermiteStatus:
                       # t_end is not counted)
     steps: int        # steps taken (steps enqueued past t_end are no-ops, not counted)
     finished: bool    # t_end is set and reached
+    # block mode (`steps` then counts macro steps of dt; 0 otherwise)
+    block_steps: int = 0     # block steps taken
+    body_steps: int = 0      # sum of their active bodies
+    level_max: int = 0       # deepest level any body has had
+    level_clamped: int = 0   # times a body wanted a step below dt 2^-max_level
+
+PATH_IDS = {None: 0, "auto": 0, "narrow": 1, "wide": 2}
 
 
 def _require_one_rank(nranks: int) -> None:
@@ -69,6 +82,34 @@ class HermiteHipEngine:
         _native.check(self.lib, self.lib.gs_hermite_set_adaptive(
             self._h, float(cfg.eta), float(cfg.dt),
             -1.0 if cfg.t_end is None else float(cfg.t_end)), "set_adaptive")
+        self.block = bool(cfg.block_steps)
+        if self.block:
+            _native.check(self.lib, self.lib.gs_hermite_set_block(self._h, 1, int(cfg.max_level)),
+                          "set_block")
+
+    def set_block_tuning(self, narrow_max: int = -1) -> None:
+        """Active sets up to narrow_max bodies take the j-parallel evaluate kernel (0: never;
+        n: always; -1: the default for n and dtype). It changes the summation order."""
+        _native.check(self.lib, self.lib.gs_hermite_set_block_tuning(self._h, int(narrow_max)),
+                      "set_block_tuning")
+
+    def status_narrow_max(self) -> int:
+        s = _native.GsHermiteInfo()
+        _native.check(self.lib, self.lib.gs_hermite_status(self._h, ctypes.byref(s)), "status")
+        return int(s.narrow_max)
+
+    def levels(self) -> np.ndarray:
+        lev = np.zeros(self.cfg.n, dtype=np.int32)
+        _native.check(self.lib, self.lib.gs_hermite_get_block_state(
+            self._h, None, lev.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "get_block_state")
+        return lev
+
+    def body_times(self) -> np.ndarray:
+        """Per-body time in ticks of dt 2^-max_level."""
+        tb = np.zeros(self.cfg.n, dtype=np.int64)
+        _native.check(self.lib, self.lib.gs_hermite_get_block_state(
+            self._h, tb.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), None), "get_block_state")
+        return tb
 
     def init_ics(self, family: str, seed: int) -> None:
         if family in DEVICE_IC_IDS:
@@ -78,9 +119,11 @@ class HermiteHipEngine:
             self.load(make(family, self.cfg.n, seed, self.cfg.G))
 
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
-             dt_next: Optional[float] = None, dt_min: Optional[float] = None) -> None:
+             dt_next: Optional[float] = None, dt_min: Optional[float] = None,
+             levels=None, body_times=None) -> None:
         """Set the state at time t. acc, jerk None: evaluated from (pos, vel); given (with the
-        dt_next and dt_min a status() reported): a run continues as if never interrupted."""
+        dt_next and dt_min a status() reported): a run continues as if never interrupted.
+        Block mode: t is a whole multiple of dt; levels (and body_times, ticks) None: afresh."""
         pos = np.ascontiguousarray(b.pos, dtype=np.float64)
         vel = np.ascontiguousarray(b.vel, dtype=np.float64)
         mass = np.ascontiguousarray(b.mass, dtype=np.float64)
@@ -93,6 +136,14 @@ class HermiteHipEngine:
             float(dt_next) if dt_next is not None and math.isfinite(dt_next) else -1.0,
             float(dt_min) if dt_min is not None and math.isfinite(dt_min) else -1.0),
             "set_state")
+        if self.block and (levels is not None or body_times is not None):
+            lev = None if levels is None else np.ascontiguousarray(levels, dtype=np.int32)
+            tb = None if body_times is None else np.ascontiguousarray(body_times, dtype=np.int64)
+            _native.check(self.lib, self.lib.gs_hermite_set_block_state(
+                self._h,
+                None if tb is None else tb.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                None if lev is None else lev.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                "set_block_state")
 
     def abort(self) -> bool:
         """The run guard's abort hook: one rank holds no communicator whose collectives could
@@ -115,7 +166,8 @@ class HermiteHipEngine:
         s = _native.GsHermiteInfo()
         _native.check(self.lib, self.lib.gs_hermite_status(self._h, ctypes.byref(s)), "status")
         return HermiteStatus(s.time, s.dt_last, s.dt_next, s.dt_min, int(s.steps),
-                             bool(s.finished))
+                             bool(s.finished), int(s.block_steps), int(s.body_steps),
+                             int(s.level_max), int(s.level_clamped))
 
     def _get(self, want_deriv: bool):
         n = self.cfg.n
@@ -137,14 +189,32 @@ class HermiteHipEngine:
         _, a, j = self._get(True)
         return a, j
 
-    def derivs(self) -> tuple[np.ndarray, np.ndarray]:
+    def derivs(self, active=None, path: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
         """(n, 4) (ax, ay, az, phi) and (jx, jy, jz, 0) of the current (x, v), through the
-        step's own kernel."""
+        step's own kernel. Block mode, active = body indices: their rows only, through the block
+        path's evaluate and reduce (path "narrow", "wide" or None: by narrow_max)."""
+        if active is not None:
+            idx = np.ascontiguousarray(active, dtype=np.int32)
+            a4, j4 = np.zeros((len(idx), 4)), np.zeros((len(idx), 4))
+            _native.check(self.lib, self.lib.gs_hermite_derivs_active(
+                self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
+                PATH_IDS[path], _native.dptr(a4), _native.dptr(j4)), "derivs_active")
+            return a4, j4
         n = self.cfg.n
         a4, j4 = np.zeros((n, 4)), np.zeros((n, 4))
         _native.check(self.lib, self.lib.gs_hermite_derivs(self._h, _native.dptr(a4),
                                                            _native.dptr(j4)), "derivs")
         return a4, j4
+
+    def time_active(self, active, path: str, reps: int = 10) -> float:
+        """Milliseconds per evaluate + reduce of the listed bodies on one block path (device
+        events around `reps` back-to-back launches)."""
+        idx = np.ascontiguousarray(active, dtype=np.int32)
+        ms = ctypes.c_double(0.0)
+        _native.check(self.lib, self.lib.gs_hermite_time_active(
+            self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx), PATH_IDS[path],
+            int(reps), ctypes.byref(ms), None, None), "time_active")
+        return ms.value
 
     def accel(self, step_path: bool = False) -> np.ndarray:
         """(n_local, 4) = (ax, ay, az, phi), ghost rows zero."""
@@ -195,7 +265,15 @@ class HermiteCpuEngine:
         suf = "f64" if cfg.dtype == "fp64" else "f32"
         self._step = getattr(self.lib, f"gs_cpu_hermite_step_{suf}")
         self._accjerk = getattr(self.lib, f"gs_cpu_accjerk_{suf}")
+        self._accjerk_idx = getattr(self.lib, f"gs_cpu_accjerk_idx_{suf}")
         self._first_dt = getattr(self.lib, f"gs_cpu_hermite_first_dt_{suf}")
+        self.block = bool(cfg.block_steps)
+        self.L = int(cfg.max_level)
+        self.tb = np.zeros(n, dtype=np.int64)       # body times [ticks of dt 2^-L]
+        self.lev = np.zeros(n, dtype=np.int32)
+        self.block_log: list[tuple[int, int]] = []  # (t_ticks, n_active) per block step
+        self.body_steps = self.level_clamped = self.level_max = 0
+        self._macro0 = 0
         self._ptr = _native.dptr if cfg.dtype == "fp64" else _native.fptr
         self._cut2 = T(cfg.cutoff ** 2)
         self._eps2 = T(cfg.softening ** 2)
@@ -215,8 +293,79 @@ class HermiteCpuEngine:
         _native.check(self.lib, rc, "cpu accjerk")
         return a4, j4
 
+    def _derivs_idx(self, X, V, idx) -> tuple[np.ndarray, np.ndarray]:
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        a4, j4 = np.zeros((len(idx), 4), self.np_dtype), np.zeros((len(idx), 4), self.np_dtype)
+        rc = self._accjerk_idx(self._ptr(X), self._ptr(V), self.cfg.n,
+                               idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx),
+                               self.layout.chunk, self._cut2, self._eps2, self._ptr(a4),
+                               self._ptr(j4))
+        _native.check(self.lib, rc, "cpu accjerk_idx")
+        return a4, j4
+
+    def levels(self) -> np.ndarray:
+        return self.lev.copy()
+
+    def body_times(self) -> np.ndarray:
+        return self.tb.copy()
+
+    def _block_start(self, t: float, levels=None, body_times=None) -> None:
+        from ..ops import oracle
+
+        cfg = self.cfg
+        macro = int(round(t / cfg.dt))
+        if macro * cfg.dt != t:
+            raise ValueError("block steps: the state's time must be a whole multiple of dt")
+        self._macro0 = macro
+        self.block_log, self.body_steps, self.level_clamped = [], 0, 0
+        self.lev = (np.array(levels, dtype=np.int32) if levels is not None else
+                    oracle.block_first_levels(self.A[:, :3].astype(np.float64),
+                                              self.J[:, :3].astype(np.float64), cfg.dt, cfg.eta,
+                                              self.L))
+        self.tb = (np.array(body_times, dtype=np.int64) if body_times is not None else
+                   np.full(cfg.n, macro << self.L, dtype=np.int64))
+        if (self.lev < 0).any() or (self.lev > self.L).any() or \
+                (self.tb % (np.int64(1) << (self.L - self.lev).astype(np.int64))).any():
+            raise ValueError("block state: level out of 0..max_level, or a body time that is no "
+                             "multiple of its step")
+        self.level_max = int(self.lev.max())
+
+    def _block_step(self) -> None:
+        """One block step (the rules of oracle.simulate_hermite_block, in the run's dtype)."""
+        from ..ops import oracle
+
+        cfg, T, L = self.cfg, self.np_dtype, self.L
+        stp = np.int64(1) << (L - self.lev).astype(np.int64)
+        t_next = int((self.tb + stp).min())
+        act = np.nonzero(self.tb + stp == t_next)[0]
+        hd = cfg.dt * np.ldexp((t_next - self.tb).astype(np.float64), -L)
+        h = hd.astype(T)[:, None]
+        x, v, a, j = self.X[:, :3], self.V[:, :3], self.A[:, :3], self.J[:, :3]
+        XP, VP = self.X.copy(), np.zeros_like(self.V)
+        XP[:, :3] = x + (v * h + (a * ((h * h) / T(2)) + j * ((h * h * h) / T(6))))
+        VP[:, :3] = v + (a * h + j * ((h * h) / T(2)))
+        a4, j4 = self._derivs_idx(XP, VP, act)
+        a1, j1 = a4[:, :3], j4[:, :3]
+        ha = h[act]
+        a0, j0, v0 = a[act], j[act], v[act]
+        v1 = v0 + ((a0 + a1) * (ha / T(2)) + (j0 - j1) * ((ha * ha) / T(12)))
+        self.X[act, :3] = x[act] + ((v0 + v1) * (ha / T(2)) + (a0 - a1) * ((ha * ha) / T(12)))
+        self.V[act, :3], self.A[act, :3], self.J[act, :3] = v1, a1, j1
+        want, valid = oracle.hermite_dt_bodies(a0.astype(np.float64), j0.astype(np.float64),
+                                               a1.astype(np.float64), j1.astype(np.float64),
+                                               hd[act], cfg.eta)
+        self.tb[act] = t_next
+        for m, i in enumerate(act):
+            self.lev[i], c = oracle.block_new_level(int(self.lev[i]), want[m], bool(valid[m]),
+                                                    t_next, cfg.dt, L)
+            self.level_clamped += c
+        self.level_max = max(self.level_max, int(self.lev.max()))
+        self.body_steps += len(act)
+        self.block_log.append((t_next, len(act)))
+
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
-             dt_next: Optional[float] = None, dt_min: Optional[float] = None) -> None:
+             dt_next: Optional[float] = None, dt_min: Optional[float] = None,
+             levels=None, body_times=None) -> None:
         self.X[:, :3] = b.pos
         self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
         self.V[:] = 0
@@ -238,9 +387,22 @@ class HermiteCpuEngine:
                                                   self.cfg.n, float(self.cfg.eta)))
         self.t, self.dt_last, self.k = float(t), 0.0, 0
         self.dt_min = math.inf if dt_min is None else float(dt_min)
+        if self.block:
+            self._block_start(float(t), levels, body_times)
 
     def step(self, n: int) -> None:
         cfg = self.cfg
+        if self.block:  # n macro steps of dt
+            for _ in range(int(n)):
+                if cfg.t_end is not None and self.t >= cfg.t_end:
+                    return
+                macro = int(self.tb.min()) >> self.L
+                while int(self.tb.min()) < (macro + 1) << self.L:
+                    self._block_step()
+                self.t = cfg.dt * (macro + 1)
+                self.dt_last = cfg.dt
+                self.k += 1
+            return
         out = ctypes.c_double(math.inf)
         for _ in range(int(n)):
             if cfg.t_end is not None and self.t >= cfg.t_end:
@@ -266,6 +428,12 @@ class HermiteCpuEngine:
 
     def status(self) -> HermiteStatus:
         cfg = self.cfg
+        if self.block:
+            return HermiteStatus(self.t, self.dt_last, cfg.dt,
+                                 float(np.ldexp(cfg.dt, -self.level_max)), self.k,
+                                 cfg.t_end is not None and self.t >= cfg.t_end,
+                                 len(self.block_log), self.body_steps, self.level_max,
+                                 self.level_clamped)
         nxt = min(cfg.dt, self._next) if cfg.eta > 0 else cfg.dt
         return HermiteStatus(self.t, self.dt_last, nxt, self.dt_min, self.k,
                              cfg.t_end is not None and self.t >= cfg.t_end)
@@ -277,8 +445,8 @@ class HermiteCpuEngine:
     def carried(self) -> tuple[np.ndarray, np.ndarray]:
         return self.A[:, :3].astype(np.float64), self.J[:, :3].astype(np.float64)
 
-    def derivs(self) -> tuple[np.ndarray, np.ndarray]:
-        a4, j4 = self._derivs()
+    def derivs(self, active=None, path: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+        a4, j4 = self._derivs() if active is None else self._derivs_idx(self.X, self.V, active)
         return a4.astype(np.float64), j4.astype(np.float64)
 
     def accel(self) -> np.ndarray:

@@ -22,6 +22,9 @@ design:
   its own acceleration+jerk kernel, a fixed step or a shared adaptive one (eta) and an optional
   end time (t_end); the engine carries the time, so metrics and checkpoints report its t, and a
   checkpoint keeps the carried a, j and the next step size so that resume stays bit-exact.
+  With block_steps every body has its own step dt 2^-k and `steps` counts macro steps of dt, at
+  which all bodies stand at the same time: all periodic work lands on synchronised states, and a
+  checkpoint also keeps the levels.
 """
 from __future__ import annotations
 
@@ -144,9 +147,14 @@ class Simulation:
                     "acc" in c.extra and "jerk" in c.extra:
                 # the carried a, j (evaluated at the last predicted state) and the step size
                 # the criterion chose: the run continues bit for bit
+                kw = {}
+                if cfg.block_steps and c.meta.get("block_steps") and "level" in c.extra and \
+                        int(c.meta.get("max_level", -1)) == cfg.max_level:
+                    kw["levels"] = c.extra["level"][:, int(c.meta.get("level_column", 0))]
+                # (a shared-step checkpoint resumed with block steps starts the levels afresh)
                 self.engine.load(c.bodies, c.extra["acc"], c.extra["jerk"],
                                  t=float(c.meta.get("time", 0.0)), dt_next=c.meta.get("dt_next"),
-                                 dt_min=c.meta.get("dt_min"))
+                                 dt_min=c.meta.get("dt_min"), **kw)
             elif self.hermite:
                 self.engine.load(c.bodies, t=float(c.meta.get("time", 0.0)))  # a, j afresh
             else:
@@ -274,6 +282,11 @@ class Simulation:
             fin = lambda y: y if np.isfinite(y) else None  # noqa: E731
             meta.update(time=st.time, dt_next=fin(st.dt_next), dt_min=fin(st.dt_min),
                         eta=cfg.eta)
+            if cfg.block_steps:  # (a synchronised state: every body time is st.time)
+                lev = np.zeros((cfg.n, 3))
+                lev[:, 0] = self.engine.levels()
+                extra["level"] = lev
+                meta.update(block_steps=True, max_level=cfg.max_level, level_column=0)
         return ckpt.save(path, b, self.step, meta, extra)
 
     def run(self, steps: Optional[int] = None, log: Optional[RunLog] = None) -> RunMetrics:
@@ -298,6 +311,7 @@ class Simulation:
         ends = self.hermite and cfg.t_end is not None
         st0 = self.engine.status() if self.hermite else None
         polled = 0
+        poll = 1 if cfg.block_steps else 32  # (a macro step waits for its block steps anyway)
         comm.barrier(self.dist)
         t0 = time.perf_counter()
         s = 0
@@ -307,10 +321,10 @@ class Simulation:
                 log.progress(s, steps)
             nxt = min([steps] + [(s // p + 1) * p for p in periods])
             if ends:
-                nxt = min(nxt, polled + 32)
+                nxt = min(nxt, polled + poll)
             self.engine.step(nxt - s)
             s = nxt
-            if ends and s - polled == 32:
+            if ends and s - polled == poll:
                 polled = s
                 finished = self.engine.status().finished
             if cfg.nan_check_every and s % cfg.nan_check_every == 0:
@@ -366,6 +380,11 @@ class Simulation:
             steps = st.steps - st0.steps  # the steps this run took (none past t_end)
             herm = dict(time_reached=st.time, steps_taken=steps,
                         dt_min=st.dt_min if np.isfinite(st.dt_min) else None)
+            if cfg.block_steps:
+                body = st.body_steps - st0.body_steps
+                herm.update(block_steps=st.block_steps - st0.block_steps, body_steps=body,
+                            pair_evals=body * cfg.n, level_max=st.level_max,
+                            level_clamped=st.level_clamped - st0.level_clamped)
         return RunMetrics(n=cfg.n, steps=steps, dt=cfg.dt, dtype=cfg.dtype, device=self.device,
                           nranks=self.dist.world, wall_s=wall,
                           kernel=KERNEL_NAMES.get(lay.get("kernel", 0), "cpu"),

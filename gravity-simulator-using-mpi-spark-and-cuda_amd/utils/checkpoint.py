@@ -8,8 +8,9 @@ Format (little-endian, rank-agnostic global body order):
     vel     n*3 float64
     mass    n   float64
     extra   the arrays the header names in "extra" (a Hermite run: ["acc", "jerk"], n*3 float64
-            each, with "time" and "dt_next" in the header); readers that do not know them stop
-            after mass
+            each, with "time" and "dt_next" in the header; a block-step run appends "level",
+            the per-body level in column 0 of an n*3 array, header "level_column": 0);
+            readers that do not know them stop after mass
 State is always stored in fp64 so an fp32 run resumes exactly (fp32 -> fp64 -> fp32 is exact).
 Writes go to a temp file + rename, so a crash never leaves a torn checkpoint.
 """

@@ -32,6 +32,14 @@ class RunMetrics:
     time_reached: float | None = None
     steps_taken: int | None = None
     dt_min: float | None = None
+    # ... with block steps (`steps` then counts macro steps of dt): block steps taken, the sum
+    # of their active bodies, the pair evaluations (body_steps * n), the deepest level and the
+    # times a body wanted a step below dt 2^-max_level
+    block_steps: int | None = None
+    body_steps: int | None = None
+    pair_evals: int | None = None
+    level_max: int | None = None
+    level_clamped: int | None = None
 
     @property
     def ms_per_step(self) -> float:
@@ -54,7 +62,8 @@ class RunMetrics:
 
     def to_json(self) -> str:
         d = asdict(self)
-        for k in ("time_reached", "steps_taken", "dt_min"):
+        for k in ("time_reached", "steps_taken", "dt_min", "block_steps", "body_steps",
+                  "pair_evals", "level_max", "level_clamped"):
             if d[k] is None:
                 del d[k]
         d.update(ms_per_step=self.ms_per_step, body_updates_per_s=self.body_updates_per_s,
