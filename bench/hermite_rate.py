@@ -10,10 +10,17 @@ counts; each window ends in a device synchronise. Prints one JSON line.
 
     python bench/hermite_rate.py [--sizes 65536,262144] [--dtypes fp32,fp64] [--repeat 3]
 
+dtype mixed (fp64 state, fp32 pair kernels on double-single positions) has no KD step: its rate
+is reported alone. --compare-dtypes alternates the Hermite step of every --dtypes at each size
+(fp32, mixed, fp64, fp32, ...) and reports each median, the spread of its windows and the ratio
+to the first dtype.
+
 --drift also runs 65,536 solar+random bodies for 24 simulated hours under kd, leapfrog (dt 3600)
-and hermite --eta 0.02 and reports each run's relative energy drift.
+and hermite --eta 0.02 (in --drift-dtype) and reports each run's relative energy drift.
 --block runs the same workload (and the same at the other --sizes) with the shared adaptive step
-and with individual block time steps: wall time, steps, body-steps, energy drift and the ratio.
+and with individual block time steps: wall time, steps, body-steps, energy drift and the ratio,
+for every --block-dtypes; --tight-pairs K moves body 4 + 2k next to body 3 + 2k (k < K) as a
+circular binary of 1e6 m, the encounters far from the origin that fp32 positions cannot resolve.
 --active-sweep times one evaluate + reduce of a block step at n_act = 1, 4, 16, ..., N on both
 paths (narrow: parallel over j, up to --narrow-cap active bodies; wide: the gathered i-owned
 kernel): alternating windows of back-to-back launches between device events, median.
@@ -53,11 +60,11 @@ def rate(n: int, dtype: str, seed: int, repeat: int, min_s: float) -> dict:
     from gravsim.runtime.engines import HipEngine
     from gravsim.runtime.hermite import HermiteHipEngine
 
-    mode = _kd_mode(n, dtype)
+    mode = _kd_mode(n, dtype) if dtype != "mixed" else None
     herm = HermiteHipEngine(SimConfig(n=n, dtype=dtype, device="gpu", integrator="hermite"))
-    kd = HipEngine(SimConfig(n=n, dtype=dtype, device="gpu", mode=mode))
+    kd = HipEngine(SimConfig(n=n, dtype=dtype, device="gpu", mode=mode)) if mode else None
     try:
-        engines = {"hermite": herm, "kd": kd}
+        engines = {"hermite": herm, "kd": kd} if kd else {"hermite": herm}
         steps = {}
         for name, eng in engines.items():
             eng.init_ics("solar+random", seed)
@@ -72,22 +79,81 @@ def rate(n: int, dtype: str, seed: int, repeat: int, min_s: float) -> dict:
         out = {"n": n, "dtype": dtype, "kd_mode": mode,
                "nonfinite": sum(eng.nonfinite() for eng in engines.values()),
                "hermite_ipl": herm.native_layout["ipl"],
-               "hermite_groups": herm.native_layout["split_groups"],
-               "kd_ipl": kd.native_layout["ipl"], "kd_kernel": kd.native_layout["kernel"]}
+               "hermite_groups": herm.native_layout["split_groups"]}
+        if kd:
+            out.update(kd_ipl=kd.native_layout["ipl"], kd_kernel=kd.native_layout["kernel"])
         for name in engines:
             t = statistics.median(times[name])
             out[f"{name}_ms_per_step"] = 1e3 * t
             out[f"{name}_ms_windows"] = [round(1e3 * x, 4) for x in times[name]]
             out[f"{name}_steps_per_window"] = steps[name]
             out[f"{name}_pair_evals_per_s"] = float(n) * n / t
-        out["hermite_over_kd"] = out["hermite_ms_per_step"] / out["kd_ms_per_step"]
+        if kd:
+            out["hermite_over_kd"] = out["hermite_ms_per_step"] / out["kd_ms_per_step"]
         return out
     finally:
         herm.close()
-        kd.close()
+        if kd:
+            kd.close()
 
 
-def drift(n: int, hours: float, seed: int) -> list:
+def compare_dtypes(n: int, dtypes: list, seed: int, repeat: int, min_s: float) -> dict:
+    """The fixed Hermite step of every dtype at one size, windows alternating over the dtypes."""
+    from gravsim.config import SimConfig
+    from gravsim.runtime.hermite import HermiteHipEngine
+
+    engines = {d: HermiteHipEngine(SimConfig(n=n, dtype=d, device="gpu", integrator="hermite"))
+               for d in dtypes}
+    try:
+        steps = {}
+        for d, eng in engines.items():
+            eng.init_ics("solar+random", seed)
+            eng.sync()
+            _window(eng, 2)
+            steps[d] = max(4, int(min_s / _window(eng, 4) + 1))
+        times = {d: [] for d in engines}
+        for _ in range(repeat):
+            for d, eng in engines.items():
+                times[d].append(_window(eng, steps[d]))
+        out = {"n": n, "nonfinite": sum(eng.nonfinite() for eng in engines.values())}
+        for d, eng in engines.items():
+            t = statistics.median(times[d])
+            out[d] = {"ms_per_step": 1e3 * t, "ms_windows": [round(1e3 * x, 4) for x in times[d]],
+                      "spread": (max(times[d]) - min(times[d])) / t,
+                      "steps_per_window": steps[d], "ipl": eng.native_layout["ipl"],
+                      "groups": eng.native_layout["split_groups"],
+                      "pair_evals_per_s": float(n) * n / t}
+        for d in dtypes[1:]:
+            out[f"{d}_over_{dtypes[0]}"] = out[d]["ms_per_step"] / out[dtypes[0]]["ms_per_step"]
+        return out
+    finally:
+        for eng in engines.values():
+            eng.close()
+
+
+def tight_pairs(b, pairs: int, sep: float = 1e6):
+    """Body 4 + 2k next to body 3 + 2k (k < pairs) on a circular orbit of separation sep."""
+    import math
+
+    import numpy as np
+
+    from gravsim.config import G_SI
+
+    rng = np.random.default_rng(pairs)
+    for k in range(pairs):
+        i = 3 + 2 * k
+        if i + 1 >= b.n:
+            break
+        u = rng.normal(size=3)
+        u /= np.linalg.norm(u)
+        t = np.cross(u, (0.3, 0.5, 0.8))
+        t /= np.linalg.norm(t)
+        b.pos[i + 1] = b.pos[i] + sep * u
+        b.vel[i + 1] = b.vel[i] + math.sqrt(G_SI * (b.mass[i] + b.mass[i + 1]) / sep) * t
+    return b
+
+
+def drift(n: int, hours: float, seed: int, dtype: str = "fp32") -> list:
     from gravsim.config import SimConfig
     from gravsim.runtime.simulation import Simulation
 
@@ -97,31 +163,39 @@ def drift(n: int, hours: float, seed: int) -> list:
                      ("leapfrog", dict(integrator="leapfrog", steps=int(hours))),
                      ("hermite eta 0.02", dict(integrator="hermite", eta=0.02, t_end=t_end,
                                                steps=20000))):
-        sim = Simulation(SimConfig(n=n, dtype="fp32", device="gpu", dt=3600.0, seed=seed,
+        # (kd and leapfrog have no mixed precision: they run in fp32 beside a mixed hermite)
+        d = dtype if kw["integrator"] == "hermite" or dtype != "mixed" else "fp32"
+        sim = Simulation(SimConfig(n=n, dtype=d, device="gpu", dt=3600.0, seed=seed,
                                    diagnostics=True, **kw))
         try:
             m = sim.run()
         finally:
             sim.close()
-        out.append({"integrator": name, "steps": m.steps, "wall_s": m.wall_s,
+        out.append({"integrator": name, "dtype": d, "steps": m.steps, "wall_s": m.wall_s,
                     "time_reached": m.time_reached if m.time_reached is not None else t_end,
                     "dt_min": m.dt_min,
                     "energy_rel_drift": m.extra["conservation"]["energy_rel_drift"]})
     return out
 
 
-def block(n: int, hours: float, seed: int, dtype: str = "fp32") -> dict:
+def block(n: int, hours: float, seed: int, dtype: str = "fp32", pairs: int = 0,
+          shared: bool = True) -> dict:
     """Shared adaptive step against block steps, same build, same workload."""
     from gravsim.config import SimConfig
+    from gravsim.models.initial_conditions import make
     from gravsim.runtime.simulation import Simulation
 
-    out = {"n": n, "dtype": dtype, "hours": hours}
+    out = {"n": n, "dtype": dtype, "hours": hours, "tight_pairs": pairs}
     for name, kw in (("shared", dict(steps=10 ** 6)),
                      ("block", dict(block_steps=True, steps=int(hours)))):
+        if name == "shared" and not shared:
+            continue
         sim = Simulation(SimConfig(n=n, dtype=dtype, device="gpu", dt=3600.0, seed=seed,
                                    integrator="hermite", eta=0.02, t_end=hours * 3600.0,
                                    diagnostics=True, **kw))
         try:
+            if pairs:
+                sim.engine.load(tight_pairs(make("solar+random", n, seed, sim.cfg.G), pairs))
             m = sim.run()
         finally:
             sim.close()
@@ -136,8 +210,10 @@ def block(n: int, hours: float, seed: int, dtype: str = "fp32") -> dict:
         else:
             r.update(body_steps=m.steps * n)
         out[name] = r
-    out["shared_over_block_wall"] = out["shared"]["wall_s"] / out["block"]["wall_s"]
-    out["shared_over_block_body_steps"] = out["shared"]["body_steps"] / out["block"]["body_steps"]
+    if shared:
+        out["shared_over_block_wall"] = out["shared"]["wall_s"] / out["block"]["wall_s"]
+        out["shared_over_block_body_steps"] = \
+            out["shared"]["body_steps"] / out["block"]["body_steps"]
     return out
 
 
@@ -192,6 +268,14 @@ def main() -> int:
     ap.add_argument("--drift", action="store_true",
                     help="also the 24-hour energy drift of kd, leapfrog and hermite at 65,536")
     ap.add_argument("--drift-n", type=int, default=65536)
+    ap.add_argument("--drift-dtype", default="fp32", help="dtype of the --drift hermite run")
+    ap.add_argument("--compare-dtypes", action="store_true",
+                    help="the Hermite step of every --dtypes in alternating windows, per size")
+    ap.add_argument("--block-dtypes", default="fp32", help="dtypes of the --block runs")
+    ap.add_argument("--no-shared", action="store_true",
+                    help="--block: the block-step runs only")
+    ap.add_argument("--tight-pairs", type=int, default=0,
+                    help="--block: binaries of 1e6 m added to the workload")
     ap.add_argument("--block", action="store_true",
                     help="the 24-hour workload at every --sizes: shared adaptive step against "
                          "block steps (fp32, eta 0.02)")
@@ -212,10 +296,14 @@ def main() -> int:
            "rates": [] if a.no_rates else
                     [rate(int(n), d, a.seed, a.repeat, a.min_window_s)
                      for n in a.sizes.split(",") for d in a.dtypes.split(",")]}
+    if a.compare_dtypes:
+        res["compare_dtypes"] = [compare_dtypes(int(n), a.dtypes.split(","), a.seed, a.repeat,
+                                                a.min_window_s) for n in a.sizes.split(",")]
     if a.drift:
-        res["drift_24h"] = drift(a.drift_n, 24.0, a.seed)
+        res["drift_24h"] = drift(a.drift_n, 24.0, a.seed, a.drift_dtype)
     if a.block:
-        res["block_24h"] = [block(int(n), 24.0, a.seed) for n in a.sizes.split(",")]
+        res["block_24h"] = [block(int(n), 24.0, a.seed, d, a.tight_pairs, not a.no_shared)
+                            for n in a.sizes.split(",") for d in a.block_dtypes.split(",")]
     if a.active_sweep:
         res["active_sweep"] = [active_sweep(int(n), d, a.seed, a.repeat, a.narrow_cap)
                                for n in a.sizes.split(",") for d in a.dtypes.split(",")]

@@ -43,6 +43,13 @@ extern "C" int gs_layout_compute(const gs_config* cfg, gs_layout* out) {
     gs_set_error("layout: bad rank/nranks");
     return -1;
   }
+  if (cfg->dtype != GS_FP32 && cfg->dtype != GS_FP64) {
+    // (the shapes below are the KD stepper's; the Hermite runtime has its own: gs_hermite_layout)
+    gs_set_error(cfg->dtype == GS_MIXED
+                     ? "layout: dtype mixed (GS_MIXED) is for the hermite integrator only"
+                     : "layout: unknown dtype");
+    return -1;
+  }
   memset(out, 0, sizeof(*out));
   const int32_t chunk = cfg->chunk > 0 ? cfg->chunk : gs::auto_chunk(cfg->n);
   if (chunk % 1024 != 0) { gs_set_error("layout: chunk must be a multiple of 1024"); return -1; }

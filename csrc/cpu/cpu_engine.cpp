@@ -9,6 +9,7 @@
 
 #include <cmath>
 #include <type_traits>
+#include <vector>
 #include <stdint.h>
 #include <string.h>
 #ifdef _OPENMP
@@ -329,6 +330,100 @@ int accjerk_idx(const T* X4, const T* V4, int64_t n_real, const int32_t* idx, in
   return 0;
 }
 
+// ---- mixed precision: fp64 state, fp32 pair arithmetic on double-single positions ----------
+// The rows the GPU predictor hands its pair kernels: H = (float(x), mu), L = (float(x -
+// double(hi)), 0), W = (float(v), 0).
+struct MixedRows {
+  std::vector<float> H, L, W;
+  MixedRows(const double* X4, const double* V4, int64_t n) : H(4 * n), L(4 * n), W(4 * n) {
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+      for (int d = 0; d < 3; ++d) {
+        const float hi = (float)X4[4 * i + d];
+        H[4 * i + d] = hi;
+        L[4 * i + d] = (float)(X4[4 * i + d] - (double)hi);
+        W[4 * i + d] = (float)V4[4 * i + d];
+      }
+      H[4 * i + 3] = (float)X4[4 * i + 3];
+      L[4 * i + 3] = W[4 * i + 3] = 0.0f;
+    }
+  }
+};
+
+// accjerk_one<float> with d = (h_j - h_i) + (l_j - l_i); the chunk sums are fp32 and are added
+// in fp64 in chunk order (the GPU's reduce).
+inline void accjerk_one_mixed(const MixedRows& r, int64_t n_real, int64_t i, int32_t chunk,
+                              float cut2, float eps2, double a4[4], double j4[4]) {
+  const float *H = r.H.data(), *L = r.L.data(), *W = r.W.data();
+  const float xi = H[4 * i], yi = H[4 * i + 1], zi = H[4 * i + 2];
+  const float lx = L[4 * i], ly = L[4 * i + 1], lz = L[4 * i + 2];
+  const float ui = W[4 * i], vi = W[4 * i + 1], wi = W[4 * i + 2];
+  const int64_t n_chunks = (n_real + chunk - 1) / chunk;
+  double tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
+  for (int64_t c = 0; c < n_chunks; ++c) {
+    float ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
+    const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
+    for (int64_t j = j0; j < j1; ++j) {
+      const float dx = (H[4 * j] - xi) + (L[4 * j] - lx);
+      const float dy = (H[4 * j + 1] - yi) + (L[4 * j + 1] - ly);
+      const float dz = (H[4 * j + 2] - zi) + (L[4 * j + 2] - lz);
+      const float wx = W[4 * j] - ui, wy = W[4 * j + 1] - vi, wz = W[4 * j + 2] - wi;
+      const float r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
+      const float inv = (r2 >= cut2) ? rsqrt_ref(r2) : 0.0f;
+      const float inv2 = inv * inv;
+      const float mi = H[4 * j + 3] * inv;
+      const float s = mi * inv2;
+      const float dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
+      const float al = dw * (3.0f * inv2);
+      ax = std::fma(s, dx, ax);
+      ay = std::fma(s, dy, ay);
+      az = std::fma(s, dz, az);
+      jx = std::fma(s, std::fma(-al, dx, wx), jx);
+      jy = std::fma(s, std::fma(-al, dy, wy), jy);
+      jz = std::fma(s, std::fma(-al, dz, wz), jz);
+      ph += mi;
+    }
+    tx += ax; ty += ay; tz += az; tp += ph;
+    sx += jx; sy += jy; sz += jz;
+  }
+  a4[0] = tx; a4[1] = ty; a4[2] = tz; a4[3] = -tp;
+  j4[0] = sx; j4[1] = sy; j4[2] = sz; j4[3] = 0;
+}
+
+int accjerk_range_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0, int64_t i1,
+                        int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4) {
+  if (chunk <= 0 || i0 < 0 || i1 < i0 || i1 > n_real) {
+    gs_set_error("cpu_accjerk_mixed: bad arguments");
+    return -1;
+  }
+  const MixedRows r(X4, V4, n_real);
+#pragma omp parallel for schedule(static)
+  for (int64_t i = i0; i < i1; ++i)
+    accjerk_one_mixed(r, n_real, i, chunk, (float)cut2, (float)eps2, acc4 + 4 * (i - i0),
+                      jerk4 + 4 * (i - i0));
+  return 0;
+}
+
+int accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
+                      double* jerk4) {
+  if (chunk <= 0 || n_idx < 0 || (n_idx > 0 && !idx)) {
+    gs_set_error("cpu_accjerk_idx_mixed: bad arguments");
+    return -1;
+  }
+  for (int64_t k = 0; k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= n_real) {
+      gs_set_error("cpu_accjerk_idx_mixed: index out of range");
+      return -1;
+    }
+  const MixedRows r(X4, V4, n_real);
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < n_idx; ++k)
+    accjerk_one_mixed(r, n_real, idx[k], chunk, (float)cut2, (float)eps2, acc4 + 4 * k,
+                      jerk4 + 4 * k);
+  return 0;
+}
+
 inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
 
 template <typename T>
@@ -346,7 +441,8 @@ double hermite_first_dt(const T* A4, const T* J4, int64_t n, double eta) {
 
 // One step of size h in place (the GPU chain's predict / evaluate / correct arithmetic).
 // scratch: xp, vp, a1, j1 (n_real * 4 each).
-template <typename T>
+// MIXED (T = double): the evaluation goes through the double-single fp32 pair arithmetic.
+template <typename T, bool MIXED = false>
 int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chunk, double hd,
                  T cut2, T eps2, double eta, double* dt_min_out) {
   if (chunk <= 0 || n < 1 || !(hd > 0.0) || !scratch) {
@@ -366,7 +462,11 @@ int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chun
     XP[4 * i + 3] = X4[4 * i + 3];
     VP[4 * i + 3] = 0;
   }
-  if (accjerk_range<T>(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
+  if constexpr (MIXED) {
+    if (accjerk_range_mixed(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
+  } else {
+    if (accjerk_range<T>(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
+  }
   const T hh = h / T(2), h12 = (h * h) / T(12);
   const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
   double dtm = INFINITY;
@@ -447,6 +547,16 @@ int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, con
                            float* jerk4) {
   return accjerk_idx<float>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
 }
+int gs_cpu_accjerk_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0,
+                         int64_t i1, int32_t chunk, double cut2, double eps2, double* acc4,
+                         double* jerk4) {
+  return accjerk_range_mixed(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+}
+int gs_cpu_accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real,
+                             const int32_t* idx, int64_t n_idx, int32_t chunk, double cut2,
+                             double eps2, double* acc4, double* jerk4) {
+  return accjerk_idx_mixed(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
+}
 double gs_cpu_hermite_first_dt_f64(const double* A4, const double* J4, int64_t n_real,
                                    double eta) {
   return hermite_first_dt<double>(A4, J4, n_real, eta);
@@ -465,6 +575,12 @@ int gs_cpu_hermite_step_f32(float* X4, float* V4, float* A4, float* J4, float* s
                             double eta, double* dt_min_out) {
   return hermite_step<float>(X4, V4, A4, J4, scratch, n_real, chunk, h, cut2, eps2, eta,
                              dt_min_out);
+}
+int gs_cpu_hermite_step_mixed(double* X4, double* V4, double* A4, double* J4, double* scratch,
+                              int64_t n_real, int32_t chunk, double h, double cut2, double eps2,
+                              double eta, double* dt_min_out) {
+  return hermite_step<double, true>(X4, V4, A4, J4, scratch, n_real, chunk, h, cut2, eps2, eta,
+                                    dt_min_out);
 }
 int gs_cpu_set_threads(int32_t n) {
 #ifdef _OPENMP

@@ -7,6 +7,9 @@
 // Block mode (gs_hermite_set_block): per-body times and levels, an active list and a second
 // control block; a block step is a chain of seven launches, and gs_hermite_step advances whole
 // macro steps of dt against a device-side target time, one status read per 32 chains.
+// Three precisions: fp32 and fp64 throughout, and mixed (GS_MIXED): the state rows, the reduce
+// and the corrector in fp64, the predicted rows (position as double-single hi + lo) and the
+// partial sums of the pair kernels in fp32.
 #include <cmath>
 #include <limits>
 #include <utility>
@@ -19,9 +22,11 @@ struct gs_hermite {
   gs_config cfg;
   int64_t n = 0, n_pad = 0;
   int32_t chunk = 0, n_chunks = 0, ipl = 0, groups = 0;
-  size_t esz = 4;
+  size_t esz = 4;  // bytes per element of the state rows (x, v, a, j, the outputs)
+  size_t psz = 4;  // ... of the predicted rows and the partial sums (mixed: 4 against esz 8)
   hipStream_t stream = nullptr;
   void *X = nullptr, *V = nullptr, *A = nullptr, *J = nullptr, *XP = nullptr, *VP = nullptr;
+  void* XL = nullptr;  // mixed: lo rows of the predicted position
   void *PA = nullptr, *PJ = nullptr, *a_out = nullptr, *j_out = nullptr;
   gs::HermiteCtrl* ctrl = nullptr;
   double* wgmin = nullptr;
@@ -40,16 +45,25 @@ struct gs_hermite {
 namespace {
 
 size_t rows_bytes(const gs_hermite* h) { return (size_t)h->n_pad * 4 * h->esz; }
+size_t pair_rows_bytes(const gs_hermite* h) { return (size_t)h->n_pad * 4 * h->psz; }
+bool is_mixed(const gs_hermite* h) { return h->psz != h->esz; }
+
+// f(T pair type, S state type) for the run's precision.
+template <typename F>
+int by_dtype(const gs_hermite* h, F f) {
+  if (is_mixed(h)) return f(float(), double());
+  return h->esz == 4 ? f(float(), float()) : f(double(), double());
+}
 int nwg(const gs_hermite* h) { return (int)(h->n_pad / gs::kForceBlock); }
 
-template <typename T>
-gs::HArgs<T> make_args(const gs_hermite* h, int mode, bool phi) {
-  gs::HArgs<T> a{};
-  a.X = static_cast<T*>(h->X); a.V = static_cast<T*>(h->V);
-  a.A = static_cast<T*>(h->A); a.J = static_cast<T*>(h->J);
-  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP);
+template <typename T, typename S>
+gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
+  gs::HArgs<T, S> a{};
+  a.X = static_cast<S*>(h->X); a.V = static_cast<S*>(h->V);
+  a.A = static_cast<S*>(h->A); a.J = static_cast<S*>(h->J);
+  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.XL = static_cast<T*>(h->XL);
   a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ);
-  a.a_out = static_cast<T*>(h->a_out); a.j_out = static_cast<T*>(h->j_out);
+  a.a_out = static_cast<S*>(h->a_out); a.j_out = static_cast<S*>(h->j_out);
   a.ctrl = h->ctrl;
   a.wgmin = h->wgmin;
   a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
@@ -85,25 +99,37 @@ int read_ctrl(gs_hermite* h, gs::HermiteCtrl* c) {
   return 0;
 }
 
-// Derivatives of the current (x, v) through the step's own kernel, then the reduce in `mode`.
-template <typename T>
-int eval_current(gs_hermite* h, int mode, bool phi) {
-  gs::HArgs<T> a = make_args<T>(h, mode, phi);
-  a.XP = a.X;
-  a.VP = a.V;
-  GS_HIP(gs::launch_hermite_eval<T>(a, h->ipl, h->groups, false, h->stream));
-  GS_HIP(gs::launch_hermite_reduce<T>(a, h->stream));
+// The evaluate kernels read the current (x, v) instead of a predicted state: in place, or
+// (mixed) through the split of X, V into the fp32 rows.
+template <typename T, typename S>
+int point_at_current(gs_hermite* h, gs::HArgs<T, S>& a) {
+  if constexpr (sizeof(T) == sizeof(S)) {
+    a.XP = a.X;
+    a.VP = a.V;
+  } else {
+    GS_HIP(gs::launch_hermite_split(a, h->stream));
+  }
   return 0;
 }
 
-template <typename T>
+// Derivatives of the current (x, v) through the step's own kernel, then the reduce in `mode`.
+template <typename T, typename S>
+int eval_current(gs_hermite* h, int mode, bool phi) {
+  gs::HArgs<T, S> a = make_args<T, S>(h, mode, phi);
+  if (point_at_current(h, a)) return -1;
+  GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));
+  GS_HIP((gs::launch_hermite_reduce<T, S>(a, h->stream)));
+  return 0;
+}
+
+template <typename T, typename S>
 int step_t(gs_hermite* h, int32_t nsteps) {
-  const gs::HArgs<T> a = make_args<T>(h, gs::HM_STEP, false);
+  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
   for (int32_t k = 0; k < nsteps; ++k) {
-    GS_HIP(gs::launch_hermite_ctrl<T>(a, h->stream));
-    GS_HIP(gs::launch_hermite_predict<T>(a, h->stream));
-    GS_HIP(gs::launch_hermite_eval<T>(a, h->ipl, h->groups, true, h->stream));
-    GS_HIP(gs::launch_hermite_reduce<T>(a, h->stream));
+    GS_HIP((gs::launch_hermite_ctrl<T, S>(a, h->stream)));
+    GS_HIP((gs::launch_hermite_predict<T, S>(a, h->stream)));
+    GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, true, h->stream)));
+    GS_HIP((gs::launch_hermite_reduce<T, S>(a, h->stream)));
   }
   return 0;
 }
@@ -161,7 +187,9 @@ int32_t default_narrow_max(const gs_hermite* h) {
   // The measured crossover of the two evaluate paths, down to a power of two (docs/DESIGN.md
   // §15): 4096 (fp32) and 2048 (fp64) at 65,536 bodies, 32,768 for both at 262,144. Between and
   // beyond the measured sizes: n_pad / 8 from 262,144 up, n_pad / 16 (fp32), / 32 (fp64) below.
-  const int64_t div = h->n_pad >= 262144 ? 8 : (h->esz == 4 ? 16 : 32);
+  // Mixed (§16): 8192 at 65,536 and 32,768 at 262,144, n_pad / 8 at both and elsewhere (its wide
+  // path pays a third LDS read per j, its narrow path only one more coalesced load).
+  const int64_t div = h->n_pad >= 262144 || is_mixed(h) ? 8 : (h->esz == 4 ? 16 : 32);
   int64_t d = 1;
   while (2 * d <= h->n_pad / div) d *= 2;
   return (int32_t)d;
@@ -185,7 +213,7 @@ int set_narrow(gs_hermite* h, int32_t narrow_max) {
   h->blk.cap = narrow_max;
   h->narrow_max = narrow_max;
   if (narrow_max > 0) {
-    const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->esz;
+    const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->psz;
     GS_HIP(hipMalloc(&h->blk.NA, bytes));
     GS_HIP(hipMalloc(&h->blk.NJ, bytes));
   }
@@ -208,31 +236,33 @@ int reset_bctrl(gs_hermite* h, int64_t macro) {
   return write_bctrl(h, c);
 }
 
-template <typename T>
+template <typename T, typename S>
 int block_start_t(gs_hermite* h, int64_t macro) {
   if (reset_bctrl(h, macro)) return -1;
-  const gs::HArgs<T> a = make_args<T>(h, gs::HM_STEP, false);
-  GS_HIP(gs::launch_block_init<T>(a, macro << h->max_level, h->stream));
+  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+  GS_HIP((gs::launch_block_init<T, S>(a, macro << h->max_level, h->stream)));
   return 0;
 }
 
 // Levels afresh from the carried a, j; every body stands at `macro` steps of dt.
 int block_start(gs_hermite* h, int64_t macro) {
-  return h->esz == 4 ? block_start_t<float>(h, macro) : block_start_t<double>(h, macro);
+  return by_dtype(h, [&](auto t, auto s) {
+    return block_start_t<decltype(t), decltype(s)>(h, macro);
+  });
 }
 
-template <typename T>
-int block_chain(gs_hermite* h, const gs::HArgs<T>& a) {
-  GS_HIP(gs::launch_block_next<T>(a, h->stream));
-  GS_HIP(gs::launch_block_predict<T>(a, h->stream));
-  GS_HIP(gs::launch_block_narrow<T>(a, h->stream));
-  GS_HIP(gs::launch_block_wide<T>(a, h->ipl, h->groups, h->stream));
-  GS_HIP(gs::launch_block_correct<T>(a, h->stream));
+template <typename T, typename S>
+int block_chain(gs_hermite* h, const gs::HArgs<T, S>& a) {
+  GS_HIP((gs::launch_block_next<T, S>(a, h->stream)));
+  GS_HIP((gs::launch_block_predict<T, S>(a, h->stream)));
+  GS_HIP((gs::launch_block_narrow<T, S>(a, h->stream)));
+  GS_HIP((gs::launch_block_wide<T, S>(a, h->ipl, h->groups, h->stream)));
+  GS_HIP((gs::launch_block_correct<T, S>(a, h->stream)));
   return 0;
 }
 
 // n macro steps: chains in batches of 32 against the device-side target, one status read each.
-template <typename T>
+template <typename T, typename S>
 int block_step_t(gs_hermite* h, int32_t nsteps) {
   gs::HermiteBlockCtrl c;
   if (read_bctrl(h, &c)) return -1;
@@ -245,11 +275,11 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
   if (target <= c.t_ticks) return 0;
   c.target = target;
   if (write_bctrl(h, c)) return -1;
-  const gs::HArgs<T> a = make_args<T>(h, gs::HM_STEP, false);
+  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
   while (c.t_ticks < target) {
     const int64_t before = c.t_ticks;
     for (int k = 0; k < 32; ++k)
-      if (block_chain<T>(h, a)) return -1;
+      if (block_chain<T, S>(h, a)) return -1;
     if (read_bctrl(h, &c)) return -1;
     if (c.t_ticks == before) {
       gs_set_error("hermite block steps: no progress (body times out of step)");
@@ -259,7 +289,7 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
   return 0;
 }
 
-template <typename T>
+template <typename T, typename S>
 int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
                     double* jerk4, int32_t reps = 1, double* ms = nullptr) {
   gs::HermiteBlockCtrl keep;
@@ -271,9 +301,8 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
                         h->stream));
   if (write_bctrl(h, c)) return -1;
-  gs::HArgs<T> a = make_args<T>(h, gs::HM_OUT, true);
-  a.XP = a.X;
-  a.VP = a.V;
+  gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_OUT, true);
+  if (point_at_current(h, a)) return -1;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (ms) {
     GS_HIP(hipEventCreate(&e0));
@@ -282,10 +311,10 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   }
   for (int32_t r = 0; r < reps; ++r) {
     if (path == gs::HP_NARROW)
-      GS_HIP(gs::launch_block_narrow<T>(a, h->stream));
+      GS_HIP((gs::launch_block_narrow<T, S>(a, h->stream)));
     else
-      GS_HIP(gs::launch_block_wide<T>(a, h->ipl, h->groups, h->stream));
-    GS_HIP(gs::launch_block_correct<T>(a, h->stream));
+      GS_HIP((gs::launch_block_wide<T, S>(a, h->ipl, h->groups, h->stream)));
+    GS_HIP((gs::launch_block_correct<T, S>(a, h->stream)));
   }
   if (ms) {
     float t = 0.0f;
@@ -296,16 +325,17 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
     (void)hipEventDestroy(e1);
     *ms = (double)t / reps;
   }
-  if (download_rows<T>(h, h->a_out, n_idx, acc4, 4) ||
-      download_rows<T>(h, h->j_out, n_idx, jerk4, 4))
+  if (download_rows<S>(h, h->a_out, n_idx, acc4, 4) ||
+      download_rows<S>(h, h->j_out, n_idx, jerk4, 4))
     return -1;
   return write_bctrl(h, keep);
 }
 
 int start_from_state(gs_hermite* h) {
   if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity())) return -1;
-  if (h->esz == 4 ? eval_current<float>(h, gs::HM_INIT, false)
-                  : eval_current<double>(h, gs::HM_INIT, false))
+  if (by_dtype(h, [&](auto t, auto s) {
+        return eval_current<decltype(t), decltype(s)>(h, gs::HM_INIT, false);
+      }))
     return -1;
   return h->block ? block_start(h, 0) : 0;
 }
@@ -326,12 +356,17 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
     gs_set_error("hermite: cutoff and softening cannot both be 0 (the self term)");
     return -1;
   }
-  const int fp64 = cfg->dtype == GS_FP64;
+  if (cfg->dtype != GS_FP32 && cfg->dtype != GS_FP64 && cfg->dtype != GS_MIXED) {
+    gs_set_error("hermite: dtype must be GS_FP32, GS_FP64 or GS_MIXED");
+    return -1;
+  }
+  const int fp64 = cfg->dtype == GS_FP64;  // (the pair kernels': mixed takes fp32's launch shape)
   const int32_t chunk = cfg->chunk > 0 ? cfg->chunk : gs::auto_chunk(cfg->n);
   if (chunk % 1024) { gs_set_error("hermite: chunk must be a multiple of 1024"); return -1; }
   gs_hermite* h = new gs_hermite();
   h->cfg = *cfg;
-  h->esz = fp64 ? 8 : 4;
+  h->esz = cfg->dtype == GS_FP32 ? 4 : 8;
+  h->psz = fp64 ? 8 : 4;
   h->n = cfg->n;
   h->chunk = chunk;
   h->n_pad = gs::round_up(cfg->n, chunk);
@@ -346,7 +381,7 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
       ipl >>= 1;
   }
   if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
-    gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32)");
+    gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
     delete h;
     return -1;
   }
@@ -372,13 +407,18 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   } while (0)
   HM_TRY(hipSetDevice(cfg->device));
   HM_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  const size_t rb = rows_bytes(h);
-  for (void** p : {&h->X, &h->V, &h->A, &h->J, &h->XP, &h->VP, &h->a_out, &h->j_out}) {
+  const size_t rb = rows_bytes(h), pb = pair_rows_bytes(h);
+  for (void** p : {&h->X, &h->V, &h->A, &h->J, &h->a_out, &h->j_out}) {
     HM_TRY(hipMalloc(p, rb));
     HM_TRY(hipMemsetAsync(*p, 0, rb, h->stream));
   }
-  HM_TRY(hipMalloc(&h->PA, rb * (size_t)h->n_chunks));
-  HM_TRY(hipMalloc(&h->PJ, rb * (size_t)h->n_chunks));
+  for (void** p : {&h->XP, &h->VP, &h->XL}) {
+    if (p == &h->XL && !is_mixed(h)) continue;
+    HM_TRY(hipMalloc(p, pb));
+    HM_TRY(hipMemsetAsync(*p, 0, pb, h->stream));
+  }
+  HM_TRY(hipMalloc(&h->PA, pb * (size_t)h->n_chunks));
+  HM_TRY(hipMalloc(&h->PJ, pb * (size_t)h->n_chunks));
   HM_TRY(hipMalloc((void**)&h->ctrl, sizeof(gs::HermiteCtrl)));
   HM_TRY(hipMalloc((void**)&h->wgmin, (size_t)nwg(h) * sizeof(double)));
   HM_TRY(hipMalloc((void**)&h->mass_dev, (size_t)h->n_pad * sizeof(double)));
@@ -399,7 +439,7 @@ int gs_hermite_destroy(gs_hermite* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->cfg.device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {h->X, h->V, h->A, h->J, h->XP, h->VP, h->a_out, h->j_out, h->PA, h->PJ,
+  for (void* p : {h->X, h->V, h->A, h->J, h->XP, h->VP, h->XL, h->a_out, h->j_out, h->PA, h->PJ,
                   (void*)h->ctrl, (void*)h->wgmin, (void*)h->mass_dev, (void*)h->nonfinite})
     if (p) (void)hipFree(p);
   free_block(h);
@@ -515,7 +555,9 @@ int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, 
 int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
   GS_HIP(hipSetDevice(h->cfg.device));
   const bool f32 = h->esz == 4;
-  if (f32 ? eval_current<float>(h, gs::HM_OUT, true) : eval_current<double>(h, gs::HM_OUT, true))
+  if (by_dtype(h, [&](auto t, auto s) {
+        return eval_current<decltype(t), decltype(s)>(h, gs::HM_OUT, true);
+      }))
     return -1;
   if (f32 ? download_rows<float>(h, h->a_out, h->n, acc4, 4)
           : download_rows<double>(h, h->a_out, h->n, acc4, 4))
@@ -526,9 +568,10 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
-  if (h->block)
-    return h->esz == 4 ? block_step_t<float>(h, nsteps) : block_step_t<double>(h, nsteps);
-  return h->esz == 4 ? step_t<float>(h, nsteps) : step_t<double>(h, nsteps);
+  return by_dtype(h, [&](auto t, auto s) {
+    return h->block ? block_step_t<decltype(t), decltype(s)>(h, nsteps)
+                    : step_t<decltype(t), decltype(s)>(h, nsteps);
+  });
 }
 
 int gs_hermite_sync(gs_hermite* h) {
@@ -694,8 +737,9 @@ int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int
     return -1;
   }
   GS_HIP(hipSetDevice(h->cfg.device));
-  return h->esz == 4 ? derivs_active_t<float>(h, idx, n_idx, path, acc4, jerk4, reps, ms)
-                     : derivs_active_t<double>(h, idx, n_idx, path, acc4, jerk4, reps, ms);
+  return by_dtype(h, [&](auto t, auto s) {
+    return derivs_active_t<decltype(t), decltype(s)>(h, idx, n_idx, path, acc4, jerk4, reps, ms);
+  });
 }
 
 int64_t gs_hermite_count_nonfinite(gs_hermite* h) {

@@ -16,6 +16,10 @@
 //   * Canonical chunked summation (gs::auto_chunk): every chunk is summed from zero in j order
 //     into PA / PJ[chunk][i], and the reduce kernel adds the chunk sums in chunk order, so the
 //     bits do not depend on IPL or on how many chunk groups the grid has.
+//   * Mixed precision (HArgs<float, double>): the state, the predictor, the reduce and the
+//     corrector are fp64; the predictor hands the pair kernels the position as a double-single
+//     pair of fp32 rows, hi = float(xp) and lo = float(xp - hi), a third LDS tile, and the pair
+//     term starts from d = (hi_j - hi_i) + (lo_j - lo_i); all else is the fp32 kernel (hsep).
 // Step chain (one stream, no host round trip): control (next h from the last step's
 // per-workgroup dt minima; advances t, steps) -> predict -> evaluate -> reduce + correct.
 // Block time steps (each body on its own step dt 2^-k; second half of this file): next-time
@@ -31,13 +35,30 @@
 
 namespace gs {
 
+// Separation of a pair: plain, or (DS, mixed precision) from double-single positions hi + lo,
+// where the difference of the hi parts is exact whenever the bodies are close and the lo parts
+// restore what float(x) dropped.
+template <bool DS, typename V>
+__device__ __forceinline__ V hsep(V qh, V xh, V ql, V xl) {
+  if constexpr (DS) return (qh - xh) + (ql - xl);
+  return qh - xh;
+}
+
+// The lo rows of a lane's i-bodies (DS only).
+template <typename T, int IPL>
+struct HLo {
+  T x[IPL], y[IPL], z[IPL];
+};
+
 // One i-j interaction: 6 sub, 3 fma (r^2), rsq + select, 3 mul (r^-2, mu r^-1, s), mul + 2 fma
-// (d.w), 2 mul (alpha), 3 fma (a), 3 fma (w - alpha d), 3 fma (j).
-template <typename T, bool PHI>
+// (d.w), 2 mul (alpha), 3 fma (a), 3 fma (w - alpha d), 3 fma (j); DS: 3 sub and 3 add more.
+template <typename T, bool PHI, bool DS = false>
 __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, const V4<T>& q,
                                           const V4<T>& p, T cut2, T eps2, T& ax, T& ay, T& az,
-                                          T& ph, T& jx, T& jy, T& jz) {
-  const T dx = q.x - xi, dy = q.y - yi, dz = q.z - zi;
+                                          T& ph, T& jx, T& jy, T& jz, const V4<T>& l = V4<T>(),
+                                          T lxi = T(0), T lyi = T(0), T lzi = T(0)) {
+  const T dx = hsep<DS>(q.x, xi, l.x, lxi), dy = hsep<DS>(q.y, yi, l.y, lyi),
+          dz = hsep<DS>(q.z, zi, l.z, lzi);
   const T wx = p.x - ui, wy = p.y - vi, wz = p.z - wi;
   const T r2 = fma_(dz, dz, fma_(dy, dy, fma_(dx, dx, eps2)));
   const bool ok = r2 >= cut2;
@@ -66,12 +87,15 @@ __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, co
 // fp32, two i per lane as 2-vectors: each element sees exactly hinteract()'s arithmetic.
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-template <bool PHI>
+template <bool PHI, bool DS = false>
 __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, f2 wi,
                                              const V4<float>& q, const V4<float>& p, float cut2,
                                              float eps2, f2& ax, f2& ay, f2& az, f2& ph, f2& jx,
-                                             f2& jy, f2& jz) {
-  const f2 dx = f2(q.x) - xi, dy = f2(q.y) - yi, dz = f2(q.z) - zi;
+                                             f2& jy, f2& jz, const V4<float>& l = V4<float>(),
+                                             f2 lxi = f2(0.0f), f2 lyi = f2(0.0f),
+                                             f2 lzi = f2(0.0f)) {
+  const f2 dx = hsep<DS>(f2(q.x), xi, f2(l.x), lxi), dy = hsep<DS>(f2(q.y), yi, f2(l.y), lyi),
+           dz = hsep<DS>(f2(q.z), zi, f2(l.z), lzi);
   const f2 wx = f2(p.x) - ui, wy = f2(p.y) - vi, wz = f2(p.z) - wi;
   const f2 r2 = fma2(dz, dz, fma2(dy, dy, fma2(dx, dx, f2(eps2))));
   f2 inv;
@@ -104,18 +128,21 @@ __device__ __forceinline__ void hzero(HState<T, IPL>& s) {
     s.ax[k] = s.ay[k] = s.az[k] = s.ph[k] = s.jx[k] = s.jy[k] = s.jz[k] = T(0);
 }
 
-template <typename T, int IPL, bool PHI>
+template <typename T, int IPL, bool PHI, bool DS = false>
 __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q, const V4<T>& p,
-                                              T cut2, T eps2) {
+                                              T cut2, T eps2, const V4<T>& l = V4<T>(),
+                                              const HLo<T, IPL>& lo = HLo<T, IPL>()) {
   if constexpr (sizeof(T) == 4 && IPL % 2 == 0) {
 #pragma unroll
     for (int k = 0; k < IPL; k += 2) {
       f2 ax = {s.ax[k], s.ax[k + 1]}, ay = {s.ay[k], s.ay[k + 1]}, az = {s.az[k], s.az[k + 1]};
       f2 jx = {s.jx[k], s.jx[k + 1]}, jy = {s.jy[k], s.jy[k + 1]}, jz = {s.jz[k], s.jz[k + 1]};
       f2 ph = {s.ph[k], s.ph[k + 1]};
-      hinteract_pk<PHI>(f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
-                        f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]},
-                        q, p, cut2, eps2, ax, ay, az, ph, jx, jy, jz);
+      hinteract_pk<PHI, DS>(
+          f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
+          f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2, eps2,
+          ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]}, f2{lo.y[k], lo.y[k + 1]},
+          f2{lo.z[k], lo.z[k + 1]});
       s.ax[k] = ax.x; s.ax[k + 1] = ax.y;
       s.ay[k] = ay.x; s.ay[k + 1] = ay.y;
       s.az[k] = az.x; s.az[k + 1] = az.y;
@@ -128,19 +155,24 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
   }
 #pragma unroll
   for (int k = 0; k < IPL; ++k)
-    hinteract<T, PHI>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2, s.ax[k],
-                      s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k]);
+    hinteract<T, PHI, DS>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
+                          s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
+                          lo.x[k], lo.y[k], lo.z[k]);
 }
 
 // EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
 // stores one partial per chunk: PA[c][i] = (ax, ay, az, sum mu/r), PJ[c][i] = (jx, jy, jz, 0).
 // GATHER (a block step's wide path): lane slot s owns body list[s], the partials are stored per
 // slot and i-blocks beyond n_act exit; the j loop, hence a body's bits, is the same.
-template <typename T, int IPL, bool PHI, bool GATHER = false>
-__global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int gated) {
+// Mixed precision (S is not T): a third tile carries the lo rows XL, the lane keeps the lo rows
+// of its i-bodies, and only the separation differs (hsep).
+template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T>
+__global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int gated) {
+  constexpr bool DS = sizeof(S) != sizeof(T);
   constexpr int TB = Tile<T>::kBodies;
   __shared__ __attribute__((aligned(16))) V4<T> tx[2][TB];
   __shared__ __attribute__((aligned(16))) V4<T> tv[2][TB];
+  __shared__ __attribute__((aligned(16))) V4<T> tl[2][DS ? TB : 1];
   if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
   const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);
   int64_t n_act = 0;
@@ -160,7 +192,9 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int ga
   const V4<T>* VP = reinterpret_cast<const V4<T>*>(a.VP);
   V4<T>* PA = reinterpret_cast<V4<T>*>(a.PA);
   V4<T>* PJ = reinterpret_cast<V4<T>*>(a.PJ);
+  const V4<T>* XL = reinterpret_cast<const V4<T>*>(a.XL);
   HState<T, IPL> st;
+  HLo<T, IPL> lo;
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
     int64_t row = ib + threadIdx.x + k * kBlock;
@@ -169,11 +203,16 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int ga
     const V4<T> v = VP[row];
     st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
     st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+    if constexpr (DS) {
+      const V4<T> l = XL[row];
+      lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
+    }
   }
   auto fill = [&](int t) {
     const int64_t j0 = (int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB;
     tile_fill<T>(XP + j0, tx[t & 1]);
     tile_fill<T>(VP + j0, tv[t & 1]);
+    if constexpr (DS) tile_fill<T>(XL + j0, tl[t & 1]);
   };
   fill(0);
   hzero<T, IPL>(st);
@@ -183,10 +222,14 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T> a, int ga
     if (t + 1 < ntiles) fill(t + 1);
     const V4<T>* cx = tx[t & 1];
     const V4<T>* cv = tv[t & 1];
+    const V4<T>* cl = tl[t & 1];
 #pragma unroll 4
     for (int j = 0; j < TB; ++j) {
       const V4<T> q = cx[j], p = cv[j];  // uniform addresses: broadcast ds_reads
-      hinteract_all<T, IPL, PHI>(st, q, p, a.cut2, a.eps2);
+      if constexpr (DS)
+        hinteract_all<T, IPL, PHI, true>(st, q, p, a.cut2, a.eps2, cl[j], lo);
+      else
+        hinteract_all<T, IPL, PHI>(st, q, p, a.cut2, a.eps2);
     }
     if ((t + 1) % tpc == 0) {
       const int c = c0 + t / tpc;
@@ -250,19 +293,36 @@ __global__ __launch_bounds__(kBlock) void hermite_ctrl_kernel(HermiteCtrl* ctrl,
 }
 
 // PREDICT: xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2 (ghost rows stay zero).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T> a) {
+// Store row i of the predicted state for the evaluate kernels: as it is, or (mixed precision,
+// S is not T) the position split into XP = (float(xp), mu), XL = (float(xp - double(hi)), 0).
+template <typename T, typename S>
+__device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i, const V4<S>& xp,
+                                                const V4<S>& vp) {
+  V4<T> h, v;
+  h.x = (T)xp.x; h.y = (T)xp.y; h.z = (T)xp.z; h.w = (T)xp.w;
+  v.x = (T)vp.x; v.y = (T)vp.y; v.z = (T)vp.z; v.w = T(0);
+  reinterpret_cast<V4<T>*>(a.XP)[i] = h;
+  reinterpret_cast<V4<T>*>(a.VP)[i] = v;
+  if constexpr (sizeof(S) != sizeof(T)) {
+    V4<T> l;
+    l.x = (T)(xp.x - (S)h.x); l.y = (T)(xp.y - (S)h.y); l.z = (T)(xp.z - (S)h.z); l.w = T(0);
+    reinterpret_cast<V4<T>*>(a.XL)[i] = l;
+  }
+}
+
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) {
   if (!a.ctrl->active) return;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
-  V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp;
+  V4<S> xp = {S(0), S(0), S(0), S(0)}, vp = xp;
   if (i < a.n_real) {
-    const T h = (T)a.ctrl->h;
-    const T h2 = (h * h) / T(2), h3 = (h * h * h) / T(6);
-    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
-    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
-    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
-    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const S h = (S)a.ctrl->h;
+    const S h2 = (h * h) / S(2), h3 = (h * h * h) / S(6);
+    const V4<S> x = reinterpret_cast<const V4<S>*>(a.X)[i];
+    const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
+    const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
+    const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
     xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
     xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
     xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
@@ -271,8 +331,16 @@ __global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T> a) {
     vp.y = v.y + (ac.y * h + jk.y * h2);
     vp.z = v.z + (ac.z * h + jk.z * h2);
   }
-  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
-  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
+  store_predicted<T, S>(a, i, xp, vp);
+}
+
+// SPLIT (mixed precision): the predictor's output at h = 0, for the derivatives of the current
+// state (ghost rows of X, V are zero).
+__global__ __launch_bounds__(kBlock) void hermite_split_kernel(HArgs<float, double> a) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n_pad) return;
+  store_predicted<float, double>(a, i, reinterpret_cast<const V4<double>*>(a.X)[i],
+                                 reinterpret_cast<const V4<double>*>(a.V)[i]);
 }
 
 __device__ __forceinline__ double norm3(double x, double y, double z) {
@@ -283,14 +351,14 @@ __device__ __forceinline__ double norm3(double x, double y, double z) {
 // HM_STEP applies the corrector and Aarseth's criterion, HM_INIT starts a run from (x, v),
 // HM_OUT returns the derivatives. Per-workgroup dt minima go to wgmin (+inf when no body of the
 // workgroup takes part: ghost rows, |j| = 0, a non-finite ratio, or a fixed-step run).
-template <typename T>
-__global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T> a) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
   __shared__ double red[kBlock / 64];
   if (a.mode == HM_STEP && !a.ctrl->active) return;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad is a multiple of 256)
   const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
   const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
-  T a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
+  S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
   for (int c = 0; c < a.n_chunks; ++c) {
     const V4<T> pa = PA[(int64_t)c * a.n_pad + i];
     const V4<T> pj = PJ[(int64_t)c * a.n_pad + i];
@@ -298,24 +366,24 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T> a) {
     j1x += pj.x; j1y += pj.y; j1z += pj.z;
   }
   if (a.mode == HM_OUT) {
-    V4<T> oa, oj;
+    V4<S> oa, oj;
     oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = -sp;
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
-    reinterpret_cast<V4<T>*>(a.a_out)[i] = oa;
-    reinterpret_cast<V4<T>*>(a.j_out)[i] = oj;
+    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
+    reinterpret_cast<V4<S>*>(a.a_out)[i] = oa;
+    reinterpret_cast<V4<S>*>(a.j_out)[i] = oj;
     return;
   }
-  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
-  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
+  V4<S>* A = reinterpret_cast<V4<S>*>(a.A);
+  V4<S>* J = reinterpret_cast<V4<S>*>(a.J);
   const double eta = a.ctrl->eta;
   double dti = INFINITY;
   if (i >= a.n_real) {
-    const V4<T> z = {T(0), T(0), T(0), T(0)};
+    const V4<S> z = {S(0), S(0), S(0), S(0)};
     A[i] = z;
     J[i] = z;
     if (a.mode == HM_STEP) {
-      reinterpret_cast<V4<T>*>(a.X)[i] = z;
-      reinterpret_cast<V4<T>*>(a.V)[i] = z;
+      reinterpret_cast<V4<S>*>(a.X)[i] = z;
+      reinterpret_cast<V4<S>*>(a.V)[i] = z;
     }
   } else if (a.mode == HM_INIT) {
     if (eta > 0.0) {
@@ -325,16 +393,16 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T> a) {
     }
   } else {
     const double hd = a.ctrl->h;
-    const T h = (T)hd;
-    const T hh = h / T(2), h12 = (h * h) / T(12);
-    V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
-    V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
-    const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
-    V4<T> v1, x1;
+    const S h = (S)hd;
+    const S hh = h / S(2), h12 = (h * h) / S(12);
+    V4<S>* X = reinterpret_cast<V4<S>*>(a.X);
+    V4<S>* V = reinterpret_cast<V4<S>*>(a.V);
+    const V4<S> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
+    V4<S> v1, x1;
     v1.x = v.x + ((a0.x + a1x) * hh + (j0.x - j1x) * h12);
     v1.y = v.y + ((a0.y + a1y) * hh + (j0.y - j1y) * h12);
     v1.z = v.z + ((a0.z + a1z) * hh + (j0.z - j1z) * h12);
-    v1.w = T(0);
+    v1.w = S(0);
     x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - a1x) * h12);
     x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - a1y) * h12);
     x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - a1z) * h12);
@@ -360,9 +428,9 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T> a) {
     }
   }
   if (i < a.n_real) {
-    V4<T> oa, oj;
-    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = T(0);
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
+    V4<S> oa, oj;
+    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = S(0);
+    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
     A[i] = oa;
     J[i] = oj;
   }
@@ -397,8 +465,8 @@ __device__ __forceinline__ bool body_due(const HBlock& b, int64_t i, int L, int6
 }
 
 // NEXT, stage 1: per-workgroup minimum of tb + step over the real bodies.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void block_next_kernel(HArgs<T> a) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void block_next_kernel(HArgs<T, S> a) {
   __shared__ int64_t red[kBlock / 64];
   const HBlock& b = a.blk;
   const int L = b.bc->L;
@@ -438,24 +506,24 @@ __global__ __launch_bounds__(kBlock) void block_ctrl_kernel(HermiteBlockCtrl* bc
 
 // PREDICT-ALL + MARK: every real body from its own tb to t_next; counts the due bodies of the
 // workgroup for the compaction.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T> a) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T, S> a) {
   __shared__ int cnt[kBlock / 64];
   const HBlock& b = a.blk;
   if (!b.bc->active) return;
   const int L = b.bc->L;
   const int64_t t_next = b.bc->t_ticks;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad: a multiple of 256)
-  V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp;
+  V4<S> xp = {S(0), S(0), S(0), S(0)}, vp = xp;
   bool due = false;
   if (i < a.n_real) {
     due = body_due(b, i, L, t_next);
-    const T h = (T)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L);
-    const T h2 = (h * h) / T(2), h3 = (h * h * h) / T(6);
-    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
-    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
-    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
-    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const S h = (S)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L);
+    const S h2 = (h * h) / S(2), h3 = (h * h * h) / S(6);
+    const V4<S> x = reinterpret_cast<const V4<S>*>(a.X)[i];
+    const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
+    const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
+    const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
     xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
     xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
     xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
@@ -464,8 +532,7 @@ __global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T> a) {
     vp.y = v.y + (ac.y * h + jk.y * h2);
     vp.z = v.z + (ac.z * h + jk.z * h2);
   }
-  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
-  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
+  store_predicted<T, S>(a, i, xp, vp);
   const int c = __popcll(__ballot(due));
   if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -475,8 +542,8 @@ __global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T> a) {
 // COMPACT: the due bodies in ascending order, by a scan (workgroup offset = sum of the counts of
 // the workgroups before it; ballot prefix inside): no atomic append, so the list is the
 // oracle's. The last workgroup publishes n_act and picks the evaluate path.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T> a) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T, S> a) {
   __shared__ int red[kBlock / 64];
   __shared__ int cnt[kBlock / 64];
   const HBlock& b = a.blk;
@@ -515,8 +582,9 @@ __global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T> a) {
 // four waves in order through LDS) and one partial per (slice, slot) is stored. Slice length and
 // tree depend on n_pad only, so a body's bits depend neither on the other active bodies nor on
 // its slot. fp32 runs two i-bodies as 2-vectors (hinteract_pk).
-template <typename T, bool PHI>
-__global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T> a) {
+template <typename T, bool PHI, typename S = T>
+__global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
+  constexpr bool DS = sizeof(S) != sizeof(T);
   constexpr int G = kNarrowGroup;
   __shared__ T red[kBlock / 64][G][8];
   const HBlock& b = a.blk;
@@ -529,9 +597,11 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T> a) {
   const V4<T>* VP = reinterpret_cast<const V4<T>*>(a.VP);
   V4<T>* NA = reinterpret_cast<V4<T>*>(b.NA);
   V4<T>* NJ = reinterpret_cast<V4<T>*>(b.NJ);
+  const V4<T>* XL = reinterpret_cast<const V4<T>*>(a.XL);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int g = blockIdx.y; g < ngroups; g += (int)gridDim.y) {
     HState<T, G> st;
+    HLo<T, G> lo;
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       const int slot = min(g * G + k, n_act - 1);  // (spare slots of the last group: a copy)
@@ -540,11 +610,18 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T> a) {
       const V4<T> v = VP[row];
       st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
       st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+      if constexpr (DS) {
+        const V4<T> l = XL[row];
+        lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
+      }
     }
     hzero<T, G>(st);
     for (int64_t j = j0 + threadIdx.x; j < j1; j += kBlock) {
       const V4<T> q = XP[j], p = VP[j];
-      hinteract_all<T, G, PHI>(st, q, p, a.cut2, a.eps2);
+      if constexpr (DS)
+        hinteract_all<T, G, PHI, true>(st, q, p, a.cut2, a.eps2, XL[j], lo);
+      else
+        hinteract_all<T, G, PHI>(st, q, p, a.cut2, a.eps2);
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -577,14 +654,14 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T> a) {
 // body's own h, Aarseth's dt_want and the level rule: any number of halvings (capped at L), at
 // most one doubling and only where t_next allows the doubled step. HM_OUT: the sums go to
 // a_out / j_out [slot] and nothing else is touched.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T> a) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
   const HBlock& b = a.blk;
   HermiteBlockCtrl* bc = b.bc;
   if (!bc->active) return;
   const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= bc->n_act) return;
-  T a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
+  S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
   if (bc->path == HP_NARROW) {
     const V4<T>* NA = reinterpret_cast<const V4<T>*>(b.NA);
     const V4<T>* NJ = reinterpret_cast<const V4<T>*>(b.NJ);
@@ -606,11 +683,11 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T> a) {
     }
   }
   if (a.mode == HM_OUT) {
-    V4<T> oa, oj;
+    V4<S> oa, oj;
     oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = -sp;
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
-    reinterpret_cast<V4<T>*>(a.a_out)[s] = oa;
-    reinterpret_cast<V4<T>*>(a.j_out)[s] = oj;
+    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
+    reinterpret_cast<V4<S>*>(a.a_out)[s] = oa;
+    reinterpret_cast<V4<S>*>(a.j_out)[s] = oj;
     return;
   }
   const int64_t i = b.list[s];
@@ -618,27 +695,27 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T> a) {
   const int64_t t_next = bc->t_ticks;
   const double dt_max = bc->dt_max, eta = bc->eta;
   const double hd = ticks_seconds(dt_max, t_next - b.tb[i], L);
-  const T h = (T)hd;
-  const T hh = h / T(2), h12 = (h * h) / T(12);
-  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
-  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
-  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
-  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
-  const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
-  V4<T> v1, x1;
+  const S h = (S)hd;
+  const S hh = h / S(2), h12 = (h * h) / S(12);
+  V4<S>* X = reinterpret_cast<V4<S>*>(a.X);
+  V4<S>* V = reinterpret_cast<V4<S>*>(a.V);
+  V4<S>* A = reinterpret_cast<V4<S>*>(a.A);
+  V4<S>* J = reinterpret_cast<V4<S>*>(a.J);
+  const V4<S> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
+  V4<S> v1, x1;
   v1.x = v.x + ((a0.x + a1x) * hh + (j0.x - j1x) * h12);
   v1.y = v.y + ((a0.y + a1y) * hh + (j0.y - j1y) * h12);
   v1.z = v.z + ((a0.z + a1z) * hh + (j0.z - j1z) * h12);
-  v1.w = T(0);
+  v1.w = S(0);
   x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - a1x) * h12);
   x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - a1y) * h12);
   x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - a1z) * h12);
   x1.w = x.w;
   X[i] = x1;
   V[i] = v1;
-  V4<T> oa, oj;
-  oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = T(0);
-  oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = T(0);
+  V4<S> oa, oj;
+  oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = S(0);
+  oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
   A[i] = oa;
   J[i] = oj;
   b.tb[i] = t_next;
@@ -674,15 +751,15 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T> a) {
 // START: the level of every real body from the carried a, j (the smallest k with
 // dt_max 2^-k <= (eta / 2) |a| / |j|, capped at L; 0 where |j| = 0 or the ratio is not finite),
 // all standing at tick t0.
-template <typename T>
-__global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T> a, int64_t t0) {
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64_t t0) {
   const HBlock& b = a.blk;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
   int k = 0;
   if (i < a.n_real) {
-    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
-    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
+    const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
     const double an = norm3(ac.x, ac.y, ac.z), jn = norm3(jk.x, jk.y, jk.z);
     const double want = 0.5 * b.bc->eta * an / jn;
     if (jn > 0.0 && isfinite(want))
@@ -696,55 +773,62 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T> a, int64_t 
 // ---------------------------------------------------------------------------------------
 // Host launchers.
 
-template <typename T, int IPL>
-static hipError_t launch_eval_t(const HArgs<T>& a, int groups, bool gated, hipStream_t s) {
+template <typename T, typename S, int IPL>
+static hipError_t launch_eval_t(const HArgs<T, S>& a, int groups, bool gated, hipStream_t s) {
   const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
   if (a.phi)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true>), grid, dim3(kBlock), 0, s, a,
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S>), grid, dim3(kBlock), 0, s, a,
                        (int)gated);
   else
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false>), grid, dim3(kBlock), 0, s, a,
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S>), grid, dim3(kBlock), 0, s, a,
                        (int)gated);
   return hipGetLastError();
 }
 
 bool hermite_ipl_ok(int fp64, int ipl) { return ipl == 1 || ipl == 2 || (ipl == 4 && !fp64); }
 
-template <typename T>
-hipError_t launch_hermite_eval(const HArgs<T>& a, int ipl, int groups, bool gated,
+template <typename T, typename S>
+hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool gated,
                                hipStream_t s) {
   if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
-      (int64_t)a.n_chunks * a.chunk != a.n_pad || (gated && !a.ctrl))
+      (int64_t)a.n_chunks * a.chunk != a.n_pad || (gated && !a.ctrl) ||
+      (sizeof(S) != sizeof(T) && !a.XL))
     return hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   if (groups > a.n_chunks) groups = a.n_chunks;
   switch (ipl) {
-    case 1: return launch_eval_t<T, 1>(a, groups, gated, s);
-    case 2: return launch_eval_t<T, 2>(a, groups, gated, s);
+    case 1: return launch_eval_t<T, S, 1>(a, groups, gated, s);
+    case 2: return launch_eval_t<T, S, 2>(a, groups, gated, s);
     case 4:
-      if constexpr (sizeof(T) == 4) return launch_eval_t<T, 4>(a, groups, gated, s);
+      if constexpr (sizeof(T) == 4) return launch_eval_t<T, S, 4>(a, groups, gated, s);
       return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }
 
-template <typename T>
-hipError_t launch_hermite_ctrl(const HArgs<T>& a, hipStream_t s) {
+template <typename T, typename S>
+hipError_t launch_hermite_ctrl(const HArgs<T, S>& a, hipStream_t s) {
   hipLaunchKernelGGL(hermite_ctrl_kernel, dim3(1), dim3(kBlock), 0, s, a.ctrl, a.wgmin,
                      (int)(a.n_pad / kBlock));
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_hermite_predict(const HArgs<T>& a, hipStream_t s) {
-  hipLaunchKernelGGL((hermite_predict_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)),
+template <typename T, typename S>
+hipError_t launch_hermite_predict(const HArgs<T, S>& a, hipStream_t s) {
+  hipLaunchKernelGGL((hermite_predict_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
                      dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_hermite_reduce(const HArgs<T>& a, hipStream_t s) {
-  hipLaunchKernelGGL((hermite_reduce_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)),
+hipError_t launch_hermite_split(const HArgs<float, double>& a, hipStream_t s) {
+  hipLaunchKernelGGL(hermite_split_kernel, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0, s,
+                     a);
+  return hipGetLastError();
+}
+
+template <typename T, typename S>
+hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s) {
+  hipLaunchKernelGGL((hermite_reduce_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
                      dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
@@ -756,92 +840,96 @@ int32_t hermite_narrow_slice(int64_t n_pad) {
   return (int32_t)round_up(n_pad / 64 > 4 * kBlock ? n_pad / 64 : 4 * kBlock, kBlock);
 }
 
-template <typename T>
-hipError_t launch_block_next(const HArgs<T>& a, hipStream_t s) {
+template <typename T, typename S>
+hipError_t launch_block_next(const HArgs<T, S>& a, hipStream_t s) {
   const unsigned nwg = (unsigned)(a.n_pad / kBlock);
-  hipLaunchKernelGGL((block_next_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((block_next_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
   hipLaunchKernelGGL(block_ctrl_kernel, dim3(1), dim3(kBlock), 0, s, a.blk.bc, a.blk.wgnext,
                      (int)nwg);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_block_predict(const HArgs<T>& a, hipStream_t s) {
+template <typename T, typename S>
+hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s) {
   const unsigned nwg = (unsigned)(a.n_pad / kBlock);
-  hipLaunchKernelGGL((block_predict_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
-  hipLaunchKernelGGL((block_compact_kernel<T>), dim3(nwg), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((block_predict_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL((block_compact_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_block_narrow(const HArgs<T>& a, hipStream_t s) {
+template <typename T, typename S>
+hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s) {
   const HBlock& b = a.blk;
   if (b.cap < 1) return hipSuccess;  // (narrow_max 0: every step is wide)
   if (b.slice < kBlock || b.slice % kBlock || (int64_t)b.n_slices * b.slice < a.n_pad ||
-      !b.NA || !b.NJ)
+      !b.NA || !b.NJ || (sizeof(S) != sizeof(T) && !a.XL))
     return hipErrorInvalidValue;
   const int groups = (b.cap + kNarrowGroup - 1) / kNarrowGroup;
   const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
   if (a.phi)
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, true>), grid, dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, true, S>), grid, dim3(kBlock), 0, s, a);
   else
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, false>), grid, dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, false, S>), grid, dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
-template <typename T, int IPL>
-static hipError_t launch_wide_t(const HArgs<T>& a, int groups, hipStream_t s) {
+template <typename T, typename S, int IPL>
+static hipError_t launch_wide_t(const HArgs<T, S>& a, int groups, hipStream_t s) {
   const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
   if (a.phi)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true>), grid, dim3(kBlock), 0, s, a, 0);
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true, S>), grid, dim3(kBlock), 0, s, a,
+                       0);
   else
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true>), grid, dim3(kBlock), 0, s, a, 0);
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true, S>), grid, dim3(kBlock), 0, s, a,
+                       0);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_block_wide(const HArgs<T>& a, int ipl, int groups, hipStream_t s) {
+template <typename T, typename S>
+hipError_t launch_block_wide(const HArgs<T, S>& a, int ipl, int groups, hipStream_t s) {
   if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
-      (int64_t)a.n_chunks * a.chunk != a.n_pad || !a.blk.bc || !a.blk.list)
+      (int64_t)a.n_chunks * a.chunk != a.n_pad || !a.blk.bc || !a.blk.list ||
+      (sizeof(S) != sizeof(T) && !a.XL))
     return hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   if (groups > a.n_chunks) groups = a.n_chunks;
   switch (ipl) {
-    case 1: return launch_wide_t<T, 1>(a, groups, s);
-    case 2: return launch_wide_t<T, 2>(a, groups, s);
+    case 1: return launch_wide_t<T, S, 1>(a, groups, s);
+    case 2: return launch_wide_t<T, S, 2>(a, groups, s);
     case 4:
-      if constexpr (sizeof(T) == 4) return launch_wide_t<T, 4>(a, groups, s);
+      if constexpr (sizeof(T) == 4) return launch_wide_t<T, S, 4>(a, groups, s);
       return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }
 
-template <typename T>
-hipError_t launch_block_correct(const HArgs<T>& a, hipStream_t s) {
-  hipLaunchKernelGGL((block_correct_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
+template <typename T, typename S>
+hipError_t launch_block_correct(const HArgs<T, S>& a, hipStream_t s) {
+  hipLaunchKernelGGL((block_correct_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
                      0, s, a);
   return hipGetLastError();
 }
 
-template <typename T>
-hipError_t launch_block_init(const HArgs<T>& a, int64_t t0, hipStream_t s) {
-  hipLaunchKernelGGL((block_init_kernel<T>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0,
+template <typename T, typename S>
+hipError_t launch_block_init(const HArgs<T, S>& a, int64_t t0, hipStream_t s) {
+  hipLaunchKernelGGL((block_init_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0,
                      s, a, t0);
   return hipGetLastError();
 }
 
-#define GS_HERMITE_INSTANTIATE(T)                                                          \
-  template hipError_t launch_hermite_ctrl<T>(const HArgs<T>&, hipStream_t);                \
-  template hipError_t launch_hermite_predict<T>(const HArgs<T>&, hipStream_t);             \
-  template hipError_t launch_hermite_eval<T>(const HArgs<T>&, int, int, bool, hipStream_t); \
-  template hipError_t launch_hermite_reduce<T>(const HArgs<T>&, hipStream_t);             \
-  template hipError_t launch_block_next<T>(const HArgs<T>&, hipStream_t);                  \
-  template hipError_t launch_block_predict<T>(const HArgs<T>&, hipStream_t);               \
-  template hipError_t launch_block_narrow<T>(const HArgs<T>&, hipStream_t);                \
-  template hipError_t launch_block_wide<T>(const HArgs<T>&, int, int, hipStream_t);        \
-  template hipError_t launch_block_correct<T>(const HArgs<T>&, hipStream_t);               \
-  template hipError_t launch_block_init<T>(const HArgs<T>&, int64_t, hipStream_t);
-GS_HERMITE_INSTANTIATE(float)
-GS_HERMITE_INSTANTIATE(double)
+#define GS_HERMITE_INSTANTIATE(T, S)                                                          \
+  template hipError_t launch_hermite_ctrl<T, S>(const HArgs<T, S>&, hipStream_t);                \
+  template hipError_t launch_hermite_predict<T, S>(const HArgs<T, S>&, hipStream_t);             \
+  template hipError_t launch_hermite_eval<T, S>(const HArgs<T, S>&, int, int, bool, hipStream_t); \
+  template hipError_t launch_hermite_reduce<T, S>(const HArgs<T, S>&, hipStream_t);              \
+  template hipError_t launch_block_next<T, S>(const HArgs<T, S>&, hipStream_t);                  \
+  template hipError_t launch_block_predict<T, S>(const HArgs<T, S>&, hipStream_t);               \
+  template hipError_t launch_block_narrow<T, S>(const HArgs<T, S>&, hipStream_t);                \
+  template hipError_t launch_block_wide<T, S>(const HArgs<T, S>&, int, int, hipStream_t);        \
+  template hipError_t launch_block_correct<T, S>(const HArgs<T, S>&, hipStream_t);               \
+  template hipError_t launch_block_init<T, S>(const HArgs<T, S>&, int64_t, hipStream_t);
+GS_HERMITE_INSTANTIATE(float, float)
+GS_HERMITE_INSTANTIATE(double, double)
+GS_HERMITE_INSTANTIATE(float, double)  // mixed precision
 
 }  // namespace gs

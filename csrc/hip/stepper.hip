@@ -739,6 +739,12 @@ const char* gs_hip_kernel_info(void) {
 int gs_stepper_create(const gs_config* cfg, gs_stepper** out) {
   if (!cfg || !out) { gs_set_error("stepper_create: null argument"); return -1; }
   *out = nullptr;
+  if (cfg->dtype != GS_FP32 && cfg->dtype != GS_FP64) {
+    gs_set_error(cfg->dtype == GS_MIXED
+                     ? "stepper_create: dtype mixed (GS_MIXED) is for the hermite integrator only"
+                     : "stepper_create: unknown dtype");
+    return -1;
+  }
   gs_stepper* s = new gs_stepper();
   s->cfg = *cfg;
   if (gs_layout_compute(cfg, &s->L)) { delete s; return -1; }

@@ -21,7 +21,9 @@
 extern "C" {
 #endif
 
-enum gs_dtype { GS_FP32 = 0, GS_FP64 = 1 };
+// GS_MIXED (the Hermite integrator only): fp64 state, fp32 pair arithmetic on double-single
+// predicted positions.
+enum gs_dtype { GS_FP32 = 0, GS_FP64 = 1, GS_MIXED = 2 };
 
 // Force kernel variants (the j-body source).
 enum gs_kernel {
@@ -181,6 +183,20 @@ int gs_cpu_hermite_step_f64(double* X4, double* V4, double* A4, double* J4, doub
 int gs_cpu_hermite_step_f32(float* X4, float* V4, float* A4, float* J4, float* scratch,
                             int64_t n_real, int32_t chunk, double h, float cut2, float eps2,
                             double eta, double* dt_min_out);
+// Mixed precision (GS_MIXED): arrays fp64 in and out. The evaluation sees each position as the
+// double-single pair hi = float(x), lo = float(x - double(hi)) and forms d = (hi_j - hi_i) +
+// (lo_j - lo_i) in fp32; v, mu, cut2 and eps2 are rounded to fp32 and the rest of the pair term
+// and the chunk sums are gs_cpu_accjerk_f32's; the chunk sums are added in fp64 in chunk order.
+// The step predicts, corrects and applies the criterion as gs_cpu_hermite_step_f64.
+int gs_cpu_accjerk_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0,
+                         int64_t i1, int32_t chunk, double cut2, double eps2, double* acc4,
+                         double* jerk4);
+int gs_cpu_accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real,
+                             const int32_t* idx, int64_t n_idx, int32_t chunk, double cut2,
+                             double eps2, double* acc4, double* jerk4);
+int gs_cpu_hermite_step_mixed(double* X4, double* V4, double* A4, double* J4, double* scratch,
+                              int64_t n_real, int32_t chunk, double h, double cut2, double eps2,
+                              double eta, double* dt_min_out);
 int gs_cpu_num_threads(void);
 int gs_cpu_set_threads(int32_t n);  // OpenMP threads for the CPU engine (returns the new max)
 

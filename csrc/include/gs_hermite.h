@@ -46,7 +46,7 @@ struct HBlock {
   int32_t* list;     // [n_pad] active bodies, ascending
   int32_t* wgcount;  // [n_pad / 256] active bodies per workgroup of the predict kernel
   int64_t* wgnext;   // [n_pad / 256] per-workgroup min of tb + step
-  void *NA, *NJ;     // narrow partials [n_slices][cap] rows of 4
+  void *NA, *NJ;     // narrow partials [n_slices][cap] rows of 4 (of the pair type)
   int32_t slice;     // j rows per slice (a multiple of 256; depends on n_pad only)
   int32_t n_slices;
   int32_t cap;       // slots of the narrow partial buffer (= narrow_max)
@@ -62,12 +62,17 @@ enum { HM_STEP = 0,   // corrector: x, v, a, j <- corrected; per-workgroup min o
 // Arrays hold 4 components per body over n_pad rows: X = (x, y, z, mu), V = (vx, vy, vz, 0),
 // A = (ax, ay, az, phi), J = (jx, jy, jz, 0); XP / VP the predicted state (what the evaluate
 // kernel reads); PA / PJ the per-chunk partial sums [n_chunks][n_pad].
-template <typename T>
+// T is the type of the pair arithmetic, S the type of the state. Mixed precision is
+// HArgs<float, double>: x, v, a, j and the reduce, corrector and criterion in fp64, the predicted
+// position handed to the evaluate kernels as double-single rows XP = (float(xp), mu) and
+// XL = (float(xp - double(float(xp))), 0), so that d = (XP_j - XP_i) + (XL_j - XL_i) in fp32 is
+// free of the common part; VP and the partials are fp32 rows. XL is null where S is T.
+template <typename T, typename S = T>
 struct HArgs {
-  T *X, *V, *A, *J;
+  S *X, *V, *A, *J;
   T *XP, *VP;
   T *PA, *PJ;
-  T *a_out, *j_out;
+  S *a_out, *j_out;
   HermiteCtrl* ctrl;
   double* wgmin;     // [n_pad / 256] per-workgroup dt minima of the last reduce
   int64_t n_real, n_pad, chunk;
@@ -76,37 +81,43 @@ struct HArgs {
   int32_t phi;       // evaluate: accumulate the potential sum too
   T cut2, eps2;
   HBlock blk;        // block-step mode (all null otherwise)
+  T* XL;             // mixed precision: lo rows of the predicted position (last: the fields
+                     // above keep the offsets the fp32 and fp64 kernels were tuned with)
 };
 
-template <typename T>
-hipError_t launch_hermite_ctrl(const HArgs<T>& a, hipStream_t s);
-template <typename T>
-hipError_t launch_hermite_predict(const HArgs<T>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_hermite_ctrl(const HArgs<T, S>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_hermite_predict(const HArgs<T, S>& a, hipStream_t s);
 // Evaluate acc, jerk (and phi) of every body at (XP, VP) into PA / PJ: grid (n_pad / (256 ipl),
 // groups); always (ctrl == nullptr) or only while ctrl->active.
-template <typename T>
-hipError_t launch_hermite_eval(const HArgs<T>& a, int ipl, int groups, bool gated, hipStream_t s);
-template <typename T>
-hipError_t launch_hermite_reduce(const HArgs<T>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool gated,
+                               hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s);
 // Block-step chain (hermite.hip enqueues them in this order, all on one stream):
 // next-time minima, control, predict-all + mark, compact, narrow evaluate, wide (gathered)
 // evaluate, reduce + correct + new level. mode of the last: HM_STEP or HM_OUT.
-template <typename T>
-hipError_t launch_block_next(const HArgs<T>& a, hipStream_t s);
-template <typename T>
-hipError_t launch_block_predict(const HArgs<T>& a, hipStream_t s);
-template <typename T>
-hipError_t launch_block_narrow(const HArgs<T>& a, hipStream_t s);
-template <typename T>
-hipError_t launch_block_wide(const HArgs<T>& a, int ipl, int groups, hipStream_t s);
-template <typename T>
-hipError_t launch_block_correct(const HArgs<T>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_next(const HArgs<T, S>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_wide(const HArgs<T, S>& a, int ipl, int groups, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_correct(const HArgs<T, S>& a, hipStream_t s);
 // Levels and times of a run that starts from the carried a, j at tick t0.
-template <typename T>
-hipError_t launch_block_init(const HArgs<T>& a, int64_t t0, hipStream_t s);
+template <typename T, typename S>
+hipError_t launch_block_init(const HArgs<T, S>& a, int64_t t0, hipStream_t s);
 // j rows per narrow slice for n_pad bodies.
 int32_t hermite_narrow_slice(int64_t n_pad);
-// ipl values the evaluate kernel is compiled for (fp32: 1, 2, 4; fp64: 1, 2).
+// Mixed precision: XP, XL, VP <- the split of the current X, V (the predictor's output at h = 0),
+// for an evaluation of the derivatives of the current state.
+hipError_t launch_hermite_split(const HArgs<float, double>& a, hipStream_t s);
+// ipl values the evaluate kernel is compiled for (fp32 pairs: 1, 2, 4; fp64: 1, 2).
 bool hermite_ipl_ok(int fp64, int ipl);
 
 }  // namespace gs

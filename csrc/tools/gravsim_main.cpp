@@ -57,7 +57,12 @@ Args parse(int argc, char** argv) {
     if (k == "--n") a.cfg.n = atoll(val());
     else if (k == "--steps") a.steps = atoi(val());
     else if (k == "--dt") a.cfg.dt = atof(val());
-    else if (k == "--dtype") a.cfg.dtype = strcmp(val(), "fp64") == 0 ? GS_FP64 : GS_FP32;
+    else if (k == "--dtype") {
+      const char* v = val();
+      if (!strcmp(v, "fp64")) a.cfg.dtype = GS_FP64;
+      else if (!strcmp(v, "fp32")) a.cfg.dtype = GS_FP32;
+      else { fprintf(stderr, "--dtype %s: this driver runs fp32 or fp64 (mixed is hermite only)\n", v); exit(2); }
+    }
     else if (k == "--kernel") { const char* v = val(); a.cfg.kernel = !strcmp(v, "smem") ? GS_KERNEL_SMEM : GS_KERNEL_LDS; }
     else if (k == "--mode") { const char* v = val(); a.cfg.mode = !strcmp(v, "split") ? GS_MODE_SPLIT : GS_MODE_FUSED; }
     else if (k == "--ipl") a.cfg.ipl = atoi(val());

@@ -23,7 +23,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "whose own options make --n ambiguous)")
     p.add_argument("--dt", type=float, default=d.dt, help="time step [s]")
     p.add_argument("--steps", type=int, default=d.steps, help="number of steps")
-    p.add_argument("--dtype", choices=["fp32", "fp64"], default=d.dtype)
+    p.add_argument("--dtype", choices=["fp32", "fp64", "mixed"], default=d.dtype,
+                   help="mixed (hermite only): fp64 state, fp32 pair arithmetic on double-single "
+                        "positions")
     p.add_argument("--device", choices=["auto", "cpu", "gpu"], default=d.device)
     p.add_argument("--init", default=d.init,
                    help="IC family: solar+random | random | plummer | kepler | cold")

@@ -13,7 +13,7 @@ from typing import Optional
 
 G_SI = 6.67430e-11  # cuda.cu:11, mpi.c:9, pyspark.py:46
 
-DTYPES = ("fp32", "fp64")
+DTYPES = ("fp32", "fp64", "mixed")
 DEVICES = ("auto", "cpu", "gpu")
 KERNELS = ("auto", "lds", "smem", "mfma")
 MODES = ("auto", "fused", "split", "sym")
@@ -27,7 +27,7 @@ class SimConfig:
     n: int = 1024                 # bodies (cuda.cu:121 uses 50,000; mpi.c:107 uses 8)
     dt: float = 3600.0            # seconds (cuda.cu:123, mpi.c:148, pyspark.py:186)
     steps: int = 500              # (cuda.cu:155, mpi.c:147, pyspark.py:188)
-    dtype: str = "fp64"           # fp32 (cuda.cu) | fp64 (mpi.c, pyspark.py)
+    dtype: str = "fp64"           # fp32 (cuda.cu) | fp64 (mpi.c, pyspark.py) | mixed (hermite)
     device: str = "auto"          # auto -> gpu when a HIP device is visible
     init: str = "solar+random"    # IC family, see gravsim.models.initial_conditions
     seed: int = 20250307
@@ -113,6 +113,9 @@ class SimConfig:
             raise ValueError(f"integrator must be one of {INTEGRATORS}")
         if self.integrator != "hermite" and (self.eta != 0 or self.t_end is not None):
             raise ValueError("eta and t_end belong to integrator hermite")
+        if self.dtype == "mixed" and self.integrator != "hermite":
+            raise ValueError("dtype mixed (fp64 state, double-single fp32 pair arithmetic) "
+                             "belongs to integrator hermite")
         if self.integrator != "hermite" and self.block_steps:
             raise ValueError("block_steps belongs to integrator hermite")
         if self.block_steps:
@@ -132,8 +135,8 @@ class SimConfig:
                 raise ValueError("hermite needs dt > 0")
             if self.cutoff == 0 and self.softening == 0:
                 raise ValueError("hermite needs cutoff > 0 or softening > 0 (the self term)")
-            if self.ipl == 8 or (self.ipl == 4 and self.dtype != "fp32"):
-                raise ValueError("hermite: ipl must be 0, 1, 2 (or 4 for fp32)")
+            if self.ipl == 8 or (self.ipl == 4 and self.dtype == "fp64"):
+                raise ValueError("hermite: ipl must be 0, 1, 2 (or 4 for fp32 and mixed)")
         if self.cutoff_mode not in ("auto", "exact", "fast"):
             raise ValueError("cutoff_mode must be auto, exact or fast")
         if self.strategy not in ("allgather", "ring"):

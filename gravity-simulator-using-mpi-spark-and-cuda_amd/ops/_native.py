@@ -56,7 +56,8 @@ class GsHermiteInfo(ctypes.Structure):
     ]
 
 
-GS_FP32, GS_FP64 = 0, 1
+GS_FP32, GS_FP64, GS_MIXED = 0, 1, 2
+DTYPE_IDS = {"fp32": GS_FP32, "fp64": GS_FP64, "mixed": GS_MIXED}
 KERNEL_IDS = {"auto": 0, "lds": 1, "smem": 2, "mfma": 3}
 MODE_IDS = {"auto": 0, "fused": 1, "split": 2, "sym": 3}
 CUTOFF_IDS = {"auto": 0, "exact": 1, "fast": 2}
@@ -143,6 +144,13 @@ def cpu_lib():
             _sig(lib, f"gs_cpu_hermite_step_{t}", c_int32,
                  [P, P, P, P, P, c_int64, c_int32, c_double, T, T, c_double, _PD])
             _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, c_int64, c_double])
+        D = c_double  # mixed precision: the signatures of the f64 forms
+        _sig(lib, "gs_cpu_accjerk_mixed", c_int32,
+             [_PD, _PD, c_int64, c_int64, c_int64, c_int32, D, D, _PD, _PD])
+        _sig(lib, "gs_cpu_accjerk_idx_mixed", c_int32,
+             [_PD, _PD, c_int64, POINTER(c_int32), c_int64, c_int32, D, D, _PD, _PD])
+        _sig(lib, "gs_cpu_hermite_step_mixed", c_int32,
+             [_PD, _PD, _PD, _PD, _PD, c_int64, c_int32, D, D, D, D, _PD])
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
                                                     c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_ld", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,

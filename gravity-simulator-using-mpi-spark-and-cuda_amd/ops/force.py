@@ -70,7 +70,8 @@ def acc_jerk(pos, vel, mass, device: str = "cpu", dtype: str = "fp64", G: float 
     """One-shot Hermite derivatives: (acc (n,3), jerk (n,3), phi (n,)) as float64 arrays.
 
     device "oracle": NumPy fp64; "cpu": the native C++ engine; "gpu": the gfx950
-    acceleration+jerk kernel (raises if the HIP path is unavailable)."""
+    acceleration+jerk kernel (raises if the HIP path is unavailable). dtype "fp32", "fp64" or
+    "mixed" (fp64 inputs seen as double-single fp32 positions, fp32 pair arithmetic)."""
     pos, vel = np.asarray(pos, np.float64), np.asarray(vel, np.float64)
     mass = np.asarray(mass, np.float64)
     n = int(mass.shape[0])

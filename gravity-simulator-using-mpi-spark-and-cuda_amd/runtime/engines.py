@@ -27,7 +27,7 @@ from ..parallel.partition import Layout, layout as make_layout
 
 def _gs_config(cfg: SimConfig, rank: int, nranks: int, device: int) -> _native.GsConfig:
     return _native.GsConfig(
-        n=cfg.n, dtype=_native.GS_FP64 if cfg.dtype == "fp64" else _native.GS_FP32,
+        n=cfg.n, dtype=_native.DTYPE_IDS[cfg.dtype],
         kernel=_native.KERNEL_IDS[cfg.kernel], mode=_native.MODE_IDS[cfg.mode], ipl=cfg.ipl,
         chunk=cfg.chunk, rank=rank, nranks=nranks, device=device,
         use_graph=(2 if cfg.graph_comm else 1) if cfg.graph else 0,

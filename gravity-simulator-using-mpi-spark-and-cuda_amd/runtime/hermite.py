@@ -8,6 +8,10 @@ the next step size, so the time reached is the engine's, not step * dt.
   the acceleration+jerk kernel of csrc/hip/nbody_hermite.hip, the step size chosen on the device.
 * HermiteCpuEngine: the native C++/OpenMP step (csrc/cpu/cpu_engine.cpp gs_cpu_hermite_step_*).
 
+dtype "mixed": both engines hold x, v, a, j in fp64 and predict, correct and choose steps in fp64;
+only the pair sums are fp32, on positions handed over as double-single (hi, lo) pairs, so that
+the separation of two close bodies far from the origin keeps its digits.
+
 One step of size h: predict xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2; evaluate
 a1, j1 at (xp, vp); correct v1 = v + (a + a1) h/2 + (j - j1) h^2/12,
 x1 = x + (v + v1) h/2 + (a - a1) h^2/12; a1, j1 become the next step's a, j. With eta > 0 every
@@ -256,17 +260,18 @@ class HermiteCpuEngine:
         self.rank, self.nranks = 0, 1
         self.lib = _native.cpu_lib()
         self.layout: Layout = make_layout(cfg.n, 0, 1, cfg.chunk)
-        self.np_dtype = np.float64 if cfg.dtype == "fp64" else np.float32
+        self.np_dtype = np.float32 if cfg.dtype == "fp32" else np.float64  # (mixed: fp64 arrays)
         n, T = cfg.n, self.np_dtype
         self.X, self.V = np.zeros((n, 4), T), np.zeros((n, 4), T)
         self.A, self.J = np.zeros((n, 4), T), np.zeros((n, 4), T)
         self._scratch = np.zeros((4 * n, 4), T)
         self.mass = np.zeros(n)
-        suf = "f64" if cfg.dtype == "fp64" else "f32"
+        suf = {"fp32": "f32", "fp64": "f64", "mixed": "mixed"}[cfg.dtype]
         self._step = getattr(self.lib, f"gs_cpu_hermite_step_{suf}")
         self._accjerk = getattr(self.lib, f"gs_cpu_accjerk_{suf}")
         self._accjerk_idx = getattr(self.lib, f"gs_cpu_accjerk_idx_{suf}")
-        self._first_dt = getattr(self.lib, f"gs_cpu_hermite_first_dt_{suf}")
+        self._first_dt = getattr(
+            self.lib, "gs_cpu_hermite_first_dt_" + ("f32" if cfg.dtype == "fp32" else "f64"))
         self.block = bool(cfg.block_steps)
         self.L = int(cfg.max_level)
         self.tb = np.zeros(n, dtype=np.int64)       # body times [ticks of dt 2^-L]
@@ -274,7 +279,7 @@ class HermiteCpuEngine:
         self.block_log: list[tuple[int, int]] = []  # (t_ticks, n_active) per block step
         self.body_steps = self.level_clamped = self.level_max = 0
         self._macro0 = 0
-        self._ptr = _native.dptr if cfg.dtype == "fp64" else _native.fptr
+        self._ptr = _native.fptr if cfg.dtype == "fp32" else _native.dptr
         self._cut2 = T(cfg.cutoff ** 2)
         self._eps2 = T(cfg.softening ** 2)
         self.t, self.dt_last, self.dt_min, self.k = 0.0, 0.0, math.inf, 0
