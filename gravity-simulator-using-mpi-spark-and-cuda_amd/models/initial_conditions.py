@@ -16,6 +16,9 @@ Families:
   plummer       Plummer sphere in virial equilibrium (host-generated)
   kepler        Sun + Earth on a circular orbit (host-generated; orbit-closure tests)
   cold          uniform-density sphere at rest (host-generated; cold collapse)
+
+Not a CLI family: tracer_particles(), a few massive bodies among massless test particles, whose
+direct sums need the massive columns only (the reference of the large block-step tests).
 """
 from __future__ import annotations
 
@@ -168,6 +171,54 @@ def cold_sphere(n: int, seed: int, radius: float = 3e11, total_mass: float = 2e3
     sint = np.sqrt(1.0 - cost ** 2)
     pos = np.stack([r * sint * np.cos(phi), r * sint * np.sin(phi), r * cost], axis=1)
     return BodySet(pos, np.zeros((n, 3)), np.full(n, total_mass / n))
+
+
+AU = 1.495978707e11
+MASSIVE_AT = (0, 255, 256, 257, 65535, 65536, 65537, -1)  # (-1: the last body)
+
+
+def tracer_particles(n: int, seed: int, massive=MASSIVE_AT, moons=(), r_lo: float = 0.6 * AU,
+                     r_hi: float = 40.0 * AU, incl: float = 0.1, G: float = G_SI):
+    """A few massive bodies among massless test particles: (BodySet, indices of the massive).
+
+    A Sun at index 0 and bodies of 1e24..1e27 kg (log-spaced, in index order) at the other
+    indices of `massive` that exist (negative: from the end; by default the edges of workgroups
+    0, 1, 255 and 256 of the 256-thread kernels and the last body); every other body has mass
+    exactly 0. All circle the Sun, radius log-uniform in [r_lo, r_hi), planes tilted by up to
+    +-incl rad, so their step sizes span the ratio (r_hi / r_lo)^1.5. A direct sum over such a
+    set needs the massive columns only (ops/oracle.py `sources`), which makes a reference for
+    10^5 bodies affordable.
+
+    moons = ((host, particle, tau, speed), ...): the particle is put at the distance from the
+    massive body `host` where sqrt(d^3 / (G m_host)) = tau seconds, at `speed` times the circular
+    speed about it (phase from the seed): a body whose step is set by tau, at a chosen index."""
+    at = sorted({(n + k if k < 0 else k) for k in massive if -n <= k < n} | {0})
+    idx = np.arange(n, dtype=np.int64)
+    mu_sun = G * SOLAR[0][3]
+    r = r_lo * (r_hi / r_lo) ** uniform01(seed, idx, 0)
+    ang = 2.0 * np.pi * uniform01(seed, idx, 1)
+    vc = np.sqrt(mu_sun / r)
+    inc = _affine(-incl, incl, uniform01(seed, idx, 2))  # (the orbit's plane, tilted about x)
+    pos = np.stack([r * np.cos(ang), r * np.sin(ang) * np.cos(inc),
+                    r * np.sin(ang) * np.sin(inc)], axis=1)
+    vel = np.stack([-vc * np.sin(ang), vc * np.cos(ang) * np.cos(inc),
+                    vc * np.cos(ang) * np.sin(inc)], axis=1)
+    mass = np.zeros(n)
+    planets = at[1:]
+    mass[planets] = np.logspace(24.0, 27.0, len(planets)) if len(planets) > 1 else 1e27
+    pos[0] = vel[0] = 0.0
+    mass[0] = SOLAR[0][3]
+    for host, part, tau, speed in moons:
+        host, part = int(host) % n, int(part) % n
+        if host not in planets or part in at:
+            raise ValueError("moons: (host, particle, tau, speed) with host a massive body other "
+                             "than the Sun and particle a massless one")
+        d = np.cbrt(G * mass[host] * tau * tau)
+        ph = 2.0 * np.pi * float(uniform01(seed, np.array([part]), 3)[0])
+        c, s = np.cos(ph), np.sin(ph)
+        pos[part] = pos[host] + d * np.array([c, s, 0.0])
+        vel[part] = vel[host] + speed * (d / tau) * np.array([-s, c, 0.0])
+    return BodySet(pos, vel, mass), np.array(at, dtype=np.int64)
 
 
 def make(family: str, n: int, seed: int, G: float = G_SI) -> BodySet:

@@ -67,8 +67,26 @@ def accelerations(pos: np.ndarray, mass: np.ndarray, G: float = G_SI, cutoff: fl
     return out if len(out) > 1 else acc
 
 
+def _source_columns(mass, sources):
+    """The j bodies of a sum: all (None), or the index array `sources` when every body outside it
+    has mass exactly 0 (such a pair adds exactly zero to a, j and phi, so leaving it out changes
+    no term of the sum, only the cost)."""
+    if sources is None:
+        return slice(None)
+    src = np.asarray(sources, dtype=np.int64).ravel()
+    n = len(mass)
+    if src.size and (src.min() < 0 or src.max() >= n):
+        raise ValueError("sources: index out of range")
+    rest = np.ones(n, dtype=bool)
+    rest[src] = False
+    if np.any(np.asarray(mass)[rest] != 0):
+        raise ValueError("sources: a body outside them has mass")
+    return src
+
+
 def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: float = 0.0,
-             block: int = 256, with_potential: bool = False, with_abs: bool = False):
+             block: int = 256, with_potential: bool = False, with_abs: bool = False,
+             sources=None):
     """Direct-sum accelerations and jerks (n, 3) in fp64; optionally phi (n,) too.
 
         a_i = sum_j mu_j d / r^3,  j_i = sum_j mu_j (w - 3 (d.w) d / r^2) / r^3,
@@ -77,11 +95,16 @@ def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: 
     a pair contributing zero to all three when r^2 < cutoff^2 (the pair law of
     accelerations()). with_abs also returns the rounding scales (n, 3) of both sums:
     sum_j |a term| and, per component c,
-    sum_j mu_j r^-3 (|w_c| + 3 (sum_k |d_k w_k|) |d_c| / r^2)."""
+    sum_j mu_j r^-3 (|w_c| + 3 (sum_k |d_k w_k|) |d_c| / r^2).
+    sources: the only bodies with mass (_source_columns); the sums run over them alone."""
     pos = np.asarray(pos, dtype=np.float64)
     vel = np.asarray(vel, dtype=np.float64)
     mu = G * np.asarray(mass, dtype=np.float64)
     n = pos.shape[0]
+    cols = _source_columns(mu, sources)
+    pos_j, vel_j, mu = pos[cols], vel[cols], mu[cols]
+    if sources is not None:  # (rows x sources stays a few MB however many rows there are)
+        block = max(block, 65536 // max(1, len(mu)))
     acc, jerk = np.zeros((n, 3)), np.zeros((n, 3))
     absacc, absjerk = np.zeros((n, 3)), np.zeros((n, 3))
     phi = np.zeros(n)
@@ -89,8 +112,8 @@ def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: 
     eps2 = softening * softening
     def rows(i0: int) -> None:
         i1 = min(n, i0 + block)
-        d = pos[None, :, :] - pos[i0:i1, None, :]            # (b, n, 3)  x_j - x_i
-        w = vel[None, :, :] - vel[i0:i1, None, :]
+        d = pos_j[None, :, :] - pos[i0:i1, None, :]          # (b, n, 3)  x_j - x_i
+        w = vel_j[None, :, :] - vel[i0:i1, None, :]
         r2 = (d * d).sum(-1) + eps2
         ok = r2 >= cut2
         inv = np.zeros_like(r2)
@@ -108,7 +131,7 @@ def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: 
             absjerk[i0:i1] = (s[:, :, None] * (np.abs(w) + aal[:, :, None] * np.abs(d))).sum(1)
 
     starts = range(0, n, block)
-    if n * n >= 1 << 22 and len(starts) > 1:
+    if n * len(mu) >= 1 << 22 and len(starts) > 1:
         # (independent row blocks on a few threads, as in accelerations())
         from concurrent.futures import ThreadPoolExecutor
 
@@ -254,17 +277,22 @@ def gauss_seidel_step(pos, vel, mass, dt, nranks, G=G_SI, cutoff=1e-10):
 
 # ---- Hermite with individual block time steps ------------------------------------------------
 def acc_jerk_rows(pos, vel, mass, idx, G: float = G_SI, cutoff: float = 1e-10,
-                  softening: float = 0.0):
-    """acc_jerk() of the bodies `idx` only, against all bodies: (len(idx), 3) each."""
+                  softening: float = 0.0, sources=None):
+    """acc_jerk() of the bodies `idx` only, against all bodies: (len(idx), 3) each.
+    sources: the only bodies with mass (_source_columns); the sums run over them alone, so a
+    set of a few massive bodies and many massless test particles costs len(idx) x len(sources)."""
     pos = np.asarray(pos, dtype=np.float64)
     vel = np.asarray(vel, dtype=np.float64)
     mu = G * np.asarray(mass, dtype=np.float64)
     idx = np.asarray(idx, dtype=np.int64)
+    cols = _source_columns(mu, sources)
+    pos_j, vel_j, mu = pos[cols], vel[cols], mu[cols]
+    blk = 256 if sources is None else max(256, 65536 // max(1, len(mu)))
     acc, jerk = np.zeros((len(idx), 3)), np.zeros((len(idx), 3))
-    for b0 in range(0, len(idx), 256):
-        rows = idx[b0:b0 + 256]
-        d = pos[None, :, :] - pos[rows, None, :]
-        w = vel[None, :, :] - vel[rows, None, :]
+    for b0 in range(0, len(idx), blk):
+        rows = idx[b0:b0 + blk]
+        d = pos_j[None, :, :] - pos[rows, None, :]
+        w = vel_j[None, :, :] - vel[rows, None, :]
         r2 = (d * d).sum(-1) + softening * softening
         ok = r2 >= cutoff * cutoff
         inv = np.zeros_like(r2)
@@ -272,8 +300,8 @@ def acc_jerk_rows(pos, vel, mass, idx, G: float = G_SI, cutoff: float = 1e-10,
         inv2 = inv * inv
         s = mu[None, :] * inv * inv2
         al = 3.0 * (d * w).sum(-1) * inv2
-        acc[b0:b0 + 256] = (s[:, :, None] * d).sum(1)
-        jerk[b0:b0 + 256] = (s[:, :, None] * (w - al[:, :, None] * d)).sum(1)
+        acc[b0:b0 + blk] = (s[:, :, None] * d).sum(1)
+        jerk[b0:b0 + blk] = (s[:, :, None] * (w - al[:, :, None] * d)).sum(1)
     return acc, jerk
 
 
@@ -300,11 +328,12 @@ def block_first_levels(a, j, dt, eta, max_level):
         want = 0.5 * eta * an / jn
     ok = (jn > 0) & np.isfinite(want)
     lev = np.zeros(len(an), dtype=np.int32)
-    for i in np.nonzero(ok)[0]:
-        k = 0
-        while k < max_level and np.ldexp(dt, -k) > want[i]:
-            k += 1
-        lev[i] = k
+    want = np.where(ok, want, np.inf)
+    for k in range(max_level):  # (every body at once: one more halving where it is still wanted)
+        more = (lev == k) & (np.ldexp(dt, -k) > want)
+        if not more.any():
+            break
+        lev[more] = k + 1
     return lev
 
 
@@ -321,14 +350,55 @@ def block_new_level(k, dt_want, valid, t_next, dt, max_level):
     return k, False
 
 
+def block_new_levels(k, dt_want, valid, t_next, dt, max_level):
+    """block_new_level() of many active bodies at once (the same comparisons on arrays):
+    (new levels int32, clamped bool)."""
+    k = np.asarray(k, dtype=np.int32)
+    valid = np.asarray(valid, dtype=bool)
+    want = np.where(valid, np.asarray(dt_want, dtype=np.float64), np.inf)
+    dtk = np.ldexp(dt, -k)
+    down = valid & (want < dtk)
+    new = k.copy()
+    while True:
+        more = down & (new < max_level) & (np.ldexp(dt, -new) > want)
+        if not more.any():
+            break
+        new[more] += 1
+    clamped = down & (np.ldexp(dt, -new) > want)
+    span = np.int64(1) << (max_level - k.astype(np.int64) + 1)
+    up = valid & ~down & (k > 0) & (want >= 2.0 * dtk) & (t_next % span == 0)
+    new[up] -= 1
+    return new, clamped
+
+
+def level_lean(dt_want, valid, dt):
+    """How near a level decision came to going the other way: min over the valid bodies of
+    |log2(dt / dt_want) - nearest integer| (every threshold of the level rules is dt_want against
+    dt 2^-k for a whole k); inf when no body is valid."""
+    valid = np.asarray(valid, dtype=bool)
+    if not valid.any():
+        return float("inf")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        e = np.log2(dt / np.asarray(dt_want, dtype=np.float64)[valid])
+    e = e[np.isfinite(e)]  # (dt_want = 0: every level is too long, no threshold is near)
+    return float(np.abs(e - np.rint(e)).min()) if e.size else float("inf")
+
+
 def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI, cutoff=1e-10,
-                           softening=0.0, check=None):
+                           softening=0.0, check=None, sources=None, levels=None,
+                           body_times=None, stats=None):
     """4th-order Hermite with individual block time steps (Makino 1991): body i steps by
     dt 2^-k_i, time is an integer count of ticks of dt 2^-max_level, only the bodies that are due
     are evaluated (against every body predicted to that time) and corrected. t_end must be a
     whole multiple of dt; every multiple of dt synchronises all bodies. `check(tb, level)` is
     called after every block step. Returns (pos, vel, levels, [(t_ticks, n_active)],
-    level_clamped)."""
+    level_clamped).
+
+    sources: the only bodies with mass (acc_jerk_rows); only the due bodies and the sources are
+    then predicted, so a block step costs n_active x len(sources). levels, body_times (ticks):
+    the block state to start from (default: block_first_levels, all at 0); a body's time must be
+    a multiple of its step. stats: a dict that receives "active" (the index array of every block
+    step), "lean" (level_lean over every level decision, the first included) and "level_max"."""
     if not eta > 0:
         raise ValueError("block steps need eta > 0")
     L = int(max_level)
@@ -340,31 +410,56 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
     x = np.array(pos, dtype=np.float64, copy=True)
     v = np.array(vel, dtype=np.float64, copy=True)
     n = x.shape[0]
-    a, j = acc_jerk(x, v, mass, G, cutoff, softening)
-    tb = np.zeros(n, dtype=np.int64)
-    lev = block_first_levels(a, j, dt, eta, L)
+    mass = np.asarray(mass, dtype=np.float64)
+    src = None if sources is None else np.unique(_source_columns(mass, sources))
+    a, j = acc_jerk(x, v, mass, G, cutoff, softening, sources=src)
+    tb = (np.zeros(n, dtype=np.int64) if body_times is None else
+          np.array(body_times, dtype=np.int64))
+    lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
+           np.array(levels, dtype=np.int32))
+    if lev.shape != (n,) or tb.shape != (n,) or (lev < 0).any() or (lev > L).any() or \
+            (tb < 0).any() or (tb % (np.int64(1) << (L - lev).astype(np.int64))).any():
+        raise ValueError("block state: level out of 0..max_level, or a body time that is no "
+                         "multiple of its step")
+    lean = float("inf")
+    if stats is not None and levels is None:
+        an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            first = 0.5 * eta * an / jn
+        lean = level_lean(first, (jn > 0) & np.isfinite(first), dt)
+    level_max, active = int(lev.max()) if n else 0, []
     end = macro << L
     log, clamped = [], 0
     while tb.min() < end:
         stp = np.int64(1) << (L - lev).astype(np.int64)
         t_next = int((tb + stp).min())
         act = np.nonzero(tb + stp == t_next)[0]
-        h = dt * np.ldexp((t_next - tb).astype(np.float64), -L)
+        # the bodies whose predicted state is read: all, or the due ones and the sources
+        need = np.arange(n) if src is None else np.union1d(act, src)
+        h = dt * np.ldexp((t_next - tb[need]).astype(np.float64), -L)
         hc = h[:, None]
-        xp = x + (v * hc + (a * (hc * hc / 2) + j * (hc * hc * hc / 6)))
-        vp = v + (a * hc + j * (hc * hc / 2))
-        a1, j1 = acc_jerk_rows(xp, vp, mass, act, G, cutoff, softening)
-        ha = hc[act]
+        xn, vn, an_, jn_ = x[need], v[need], a[need], j[need]
+        xp = xn + (vn * hc + (an_ * (hc * hc / 2) + jn_ * (hc * hc * hc / 6)))
+        vp = vn + (an_ * hc + jn_ * (hc * hc / 2))
+        at = np.searchsorted(need, act)  # (the due bodies' rows of the predicted arrays)
+        a1, j1 = acc_jerk_rows(xp, vp, mass[need], at, G, cutoff, softening,
+                               sources=None if src is None else np.searchsorted(need, src))
+        ha = hc[at]
         a0, j0, v0 = a[act], j[act], v[act]
         v1 = v0 + ((a0 + a1) * (ha / 2) + (j0 - j1) * (ha * ha / 12))
         x[act] = x[act] + ((v0 + v1) * (ha / 2) + (a0 - a1) * (ha * ha / 12))
         v[act], a[act], j[act] = v1, a1, j1
-        want, valid = hermite_dt_bodies(a0, j0, a1, j1, h[act], eta)
+        want, valid = hermite_dt_bodies(a0, j0, a1, j1, h[at], eta)
         tb[act] = t_next
-        for m, i in enumerate(act):
-            lev[i], c = block_new_level(int(lev[i]), want[m], bool(valid[m]), t_next, dt, L)
-            clamped += c
+        lev[act], hit = block_new_levels(lev[act], want, valid, t_next, dt, L)
+        clamped += int(hit.sum())
         log.append((t_next, int(len(act))))
+        if stats is not None:
+            lean = min(lean, level_lean(want, valid, dt))
+            level_max = max(level_max, int(lev[act].max()))
+            active.append(act)
         if check is not None:
             check(tb, lev)
+    if stats is not None:
+        stats.update(active=active, lean=lean, level_max=level_max)
     return x, v, lev.copy(), log, clamped

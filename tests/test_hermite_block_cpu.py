@@ -25,6 +25,8 @@ from gravsim.runtime.hermite import HermiteCpuEngine
 from gravsim.runtime.simulation import Simulation
 from gravsim.utils import checkpoint as ckpt
 
+import test_hermite_block_sched_gpu as sched  # (its 700-body input and oracle run; no GPU needed)
+
 DAY = 86400.0
 DT, ETA, SOFT = 8 * DAY, 0.02, 1e9
 INPUTS = {64: 5, 200: 9}
@@ -94,7 +96,157 @@ def test_oracle_refusals():
             oracle.simulate_hermite_block(b.pos, b.vel, b.mass, softening=SOFT, **args)
 
 
+# ---- 1b. oracle: sparse sources, vectorised level rule, a given block state ----------------
+def sparse_input(n=300):
+    """Test particles (ic.tracer_particles) with the massive bodies at 0, 255, 256, 257, n - 1
+    and two moons of the last one that go deep."""
+    tau = lambda e: 2 * DT * 2.0 ** -e / np.sqrt(ETA)  # noqa: E731
+    return ic.tracer_particles(n, 5, moons=((-1, 1, tau(8.5), 1.0), (-1, n - 10, tau(6.5), 1.0)))
+
+
+def test_sparse_sources_match_the_dense_sums():
+    """A column with mu = 0 adds +-0 to every row, and NumPy adds the columns of a row in order,
+    so the sums over the sources alone may even be the same bits; the gate is what a changed
+    order could do, 4 n 2^-53 sum |terms| per component."""
+    n = 300
+    b, src = sparse_input(n)
+    assert (b.mass[src] > 0).all() and not np.delete(b.mass, src).any() and len(src) == 5
+    da, dj, dphi, sa, sj = oracle.acc_jerk(b.pos, b.vel, b.mass, with_potential=True,
+                                           with_abs=True)
+    tol = 4 * n * 2.0 ** -53
+    a, j, phi = oracle.acc_jerk(b.pos, b.vel, b.mass, with_potential=True, sources=src)
+    assert (np.abs(a - da) <= tol * sa).all() and (np.abs(j - dj) <= tol * sj).all()
+    assert (np.abs(phi - dphi) <= tol * np.abs(dphi)).all()
+    idx = np.random.default_rng(3).permutation(n)[:77]
+    ra, rj = oracle.acc_jerk_rows(b.pos, b.vel, b.mass, idx, sources=src)
+    assert (np.abs(ra - da[idx]) <= tol * sa[idx]).all()
+    assert (np.abs(rj - dj[idx]) <= tol * sj[idx]).all()
+    assert np.array_equal(ra, a[idx]) and np.array_equal(rj, j[idx])  # (same columns, same order)
+
+
+def test_sparse_block_run_matches_the_dense_run():
+    """Two macro steps of dt = 16 d with max_level 8. Positions: every evaluation may differ by
+    tol sum |terms| of the acceleration, and x answers an acceleration error e held over the
+    time T by at most e T^2 / 2, times the growth of a perturbation over the run, 58 on the moons
+    of this family (measured in tests/test_hermite_block_sched_gpu.py)."""
+    n, dt = 300, 2 * DT
+    b, src = sparse_input(n)
+    sd, ss = {}, {}
+    dense = oracle.simulate_hermite_block(b.pos, b.vel, b.mass, dt, 2 * dt, ETA, max_level=8,
+                                          stats=sd)
+    sparse = oracle.simulate_hermite_block(b.pos, b.vel, b.mass, dt, 2 * dt, ETA, max_level=8,
+                                           sources=src, stats=ss)
+    assert sparse[3] == dense[3] and sparse[4] == dense[4] > 0
+    assert np.array_equal(sparse[2], dense[2]) and len(np.unique(dense[2])) >= 4
+    assert len(dense[3]) == 512 and ss["level_max"] == sd["level_max"] == 8
+    assert all(np.array_equal(p, q) for p, q in zip(ss["active"], sd["active"]))
+    assert min(ss["lean"], sd["lean"]) >= 1e-9
+    sa = oracle.acc_jerk(b.pos, b.vel, b.mass, with_abs=True)[2]
+    tol = 4 * n * 2.0 ** -53 * sa.max() * (2 * dt) ** 2 / 2 * 58
+    err = np.abs(sparse[0] - dense[0]).max()
+    print(f"sparse against dense: {err:.3e} m, bound {tol:.3e} m")
+    assert err <= tol
+
+
+def test_sources_refuse_a_massive_body_outside_them():
+    b, src = sparse_input()
+    for bad in (src[1:], src[:-1], []):
+        with pytest.raises(ValueError, match="mass"):
+            oracle.acc_jerk_rows(b.pos, b.vel, b.mass, [0, 1], sources=bad)
+        with pytest.raises(ValueError, match="mass"):
+            oracle.acc_jerk(b.pos, b.vel, b.mass, sources=bad)
+        with pytest.raises(ValueError, match="mass"):
+            oracle.simulate_hermite_block(b.pos, b.vel, b.mass, DT, DT, ETA, sources=bad)
+    with pytest.raises(ValueError, match="range"):
+        oracle.acc_jerk(b.pos, b.vel, b.mass, sources=list(src) + [b.n])
+    # massless bodies among the sources are fine
+    a, _ = oracle.acc_jerk(b.pos, b.vel, b.mass, sources=list(src) + [7])
+    assert np.array_equal(a, oracle.acc_jerk(b.pos, b.vel, b.mass, sources=src)[0])
+
+
+def test_vectorised_level_rule_is_the_scalar_rule():
+    """Random inputs that take every branch: invalid, halvings (one, several, into the cap),
+    the doubling (allowed and not by t_next, and refused at level 0), and staying."""
+    rng = np.random.default_rng(11)
+    dt, seen = 100.0, set()
+    for L in (0, 1, 5, 24):
+        m = 4000
+        k = rng.integers(0, L + 1, m).astype(np.int32)
+        want = np.ldexp(dt, -k) * 2.0 ** rng.uniform(-4, 3, m)
+        on = rng.random(m) < 0.1  # (exactly on a threshold)
+        want[on] = np.ldexp(dt, -k[on]) * rng.choice([0.5, 1.0, 2.0], int(on.sum()))
+        want[::50], want[1::50] = np.nan, np.inf
+        valid = np.isfinite(want) & (rng.random(m) < 0.9)
+        for t_next in (1 << L, 3 << max(L - 2, 0), 5, 1 << max(L - 1, 0)):
+            new, hit = oracle.block_new_levels(k, want, valid, t_next, dt, L)
+            assert new.dtype == np.int32 and hit.dtype == bool
+            for i in range(m):
+                r = oracle.block_new_level(int(k[i]), want[i], bool(valid[i]), t_next, dt, L)
+                assert (int(new[i]), bool(hit[i])) == r, (L, i, k[i], want[i], t_next)
+                seen.add("invalid" if not valid[i] else "clamped" if r[1] else
+                         "down%d" % min(r[0] - k[i], 2) if r[0] > k[i] else
+                         "up" if r[0] < k[i] else
+                         "held" if k[i] > 0 and want[i] >= 2 * np.ldexp(dt, -int(k[i])) else "stay")
+    assert seen == {"invalid", "clamped", "down1", "down2", "up", "held", "stay"}
+    a = rng.normal(size=(500, 3))
+    j = rng.normal(size=(500, 3)) * 10.0 ** rng.uniform(-3, 3, (500, 1))
+    j[::25] = 0
+    for L in (0, 3, 24):
+        lev = oracle.block_first_levels(a, j, dt, ETA, L)
+        for i in range(500):
+            an, jn = np.sqrt((a[i] ** 2).sum()), np.sqrt((j[i] ** 2).sum())
+            k = 0
+            while jn > 0 and k < L and np.ldexp(dt, -k) > 0.5 * ETA * an / jn:
+                k += 1
+            assert lev[i] == k
+
+
+def test_oracle_starts_from_a_given_block_state():
+    """Massless bodies moving at 1 m/s, levels and body times given: the run is the integer
+    schedule, exact."""
+    n, L = 40, 3
+    i = np.arange(n)
+    lev = (i % 4).astype(np.int32)
+    tb = ((i // 4) % (1 << lev)) * (1 << (L - lev))
+    pos, vel = np.zeros((n, 3)), np.zeros((n, 3))
+    pos[:, 0], vel[:, 0] = i, 1.0
+    x, v, out_lev, log, clamped = oracle.simulate_hermite_block(
+        pos, vel, np.zeros(n), 8.0, 8.0, ETA, max_level=L, sources=[], levels=lev, body_times=tb)
+    assert np.array_equal(x[:, 0], i + (8 - tb)) and np.array_equal(v, vel)
+    assert np.array_equal(out_lev, lev) and clamped == 0
+    assert [t for t, _ in log] == list(range(1, 9))
+    assert sum(m for _, m in log) == int(((8 - tb) >> (L - lev)).sum())
+    for kw in (dict(levels=lev + 1), dict(levels=lev, body_times=tb + 1),
+               dict(levels=lev[:-1]), dict(levels=lev, body_times=-tb - 8)):
+        with pytest.raises(ValueError, match="block state"):
+            oracle.simulate_hermite_block(pos, vel, np.zeros(n), 8.0, 8.0, ETA, max_level=L, **kw)
+
+
 # ---- 2. CPU engine ------------------------------------------------------------------------
+def test_cpu_engine_matches_the_sparse_oracle():
+    """The 700-body input of tests/test_hermite_block_sched_gpu.py (active sets of 3 to 5 bodies
+    spread over the whole index range, 768 clamped steps, one macro step of 256 block steps); the
+    assertions and the gate of test_cpu_engine_matches_oracle (the oracle's response to a
+    perturbation of 1e-13 is 5.8e-12 here: within the gate's condition, see there)."""
+    n = 700
+    b, src = sched.family(n)
+    x, v, lev, log, clamped, stats = sched._oracle_run(n)
+    eng = HermiteCpuEngine(SimConfig(n=n, dt=sched.DT, steps=10, dtype="fp64", device="cpu",
+                                     integrator="hermite", eta=ETA, block_steps=True,
+                                     max_level=sched.LMAX, t_end=sched.DT).validate())
+    eng.load(b)
+    eng.step(1)
+    st, got = eng.status(), eng.state()
+    assert eng.block_log == log
+    assert np.abs(got.pos - x).max() / np.abs(x).max() <= 1e-10
+    assert np.array_equal(eng.levels(), lev) and (eng.body_times() == 1 << sched.LMAX).all()
+    assert (st.block_steps, st.body_steps) == (len(log), sum(m for _, m in log)) == (256, 3282)
+    assert st.steps == 1 and st.level_clamped == clamped == 768
+    assert st.time == sched.DT and st.finished and st.level_max == stats["level_max"] == 8
+    eng.step(3)  # past t_end: nothing happens
+    assert eng.status() == st
+
+
 @pytest.mark.parametrize("n", [64, 200])
 def test_cpu_engine_matches_oracle(n):
     """Gate 1e-10 relative: 403 block steps x the 128 eps per-evaluation gate = 6e-12, and the
