@@ -24,6 +24,9 @@ circular binary of 1e6 m, the encounters far from the origin that fp32 positions
 --active-sweep times one evaluate + reduce of a block step at n_act = 1, 4, 16, ..., N on both
 paths (narrow: parallel over j, up to --narrow-cap active bodies; wide: the gathered i-owned
 kernel): alternating windows of back-to-back launches between device events, median.
+--collisions times the fixed Hermite step with collisions off and on (detect: nearest neighbours,
+closest approaches and the overlap count from the force kernel) at every --sizes and --dtypes, in
+alternating windows (off, on, off, on, ...): each median, the spread of its windows and on / off.
 """
 from __future__ import annotations
 
@@ -125,6 +128,42 @@ def compare_dtypes(n: int, dtypes: list, seed: int, repeat: int, min_s: float) -
                       "pair_evals_per_s": float(n) * n / t}
         for d in dtypes[1:]:
             out[f"{d}_over_{dtypes[0]}"] = out[d]["ms_per_step"] / out[dtypes[0]]["ms_per_step"]
+        return out
+    finally:
+        for eng in engines.values():
+            eng.close()
+
+
+def collisions(n: int, dtype: str, seed: int, repeat: int, min_s: float) -> dict:
+    """The fixed Hermite step without and with the nearest-neighbour work, windows alternating."""
+    from gravsim.config import SimConfig
+    from gravsim.models.initial_conditions import make
+    from gravsim.runtime.hermite import HermiteHipEngine
+
+    engines = {m: HermiteHipEngine(SimConfig(n=n, dtype=dtype, device="gpu", integrator="hermite",
+                                             collisions=m)) for m in ("off", "detect")}
+    try:
+        b = make("solar+random", n, seed)
+        steps = {}
+        for m, eng in engines.items():
+            eng.load(b)  # (the same bodies through the same path; every radius 0)
+            eng.sync()
+            _window(eng, 2)
+            steps[m] = max(4, int(min_s / _window(eng, 4) + 1))
+        times = {m: [] for m in engines}
+        for _ in range(repeat):
+            for m, eng in engines.items():
+                times[m].append(_window(eng, steps[m]))
+        out = {"n": n, "dtype": dtype,
+               "nonfinite": sum(eng.nonfinite() for eng in engines.values()),
+               "overlaps": engines["detect"].status().overlaps}
+        for m in engines:
+            t = statistics.median(times[m])
+            out[m] = {"ms_per_step": 1e3 * t, "ms_windows": [round(1e3 * x, 4) for x in times[m]],
+                      "spread": (max(times[m]) - min(times[m])) / t, "steps_per_window": steps[m],
+                      "ipl": engines[m].native_layout["ipl"],
+                      "groups": engines[m].native_layout["split_groups"]}
+        out["on_over_off"] = out["detect"]["ms_per_step"] / out["off"]["ms_per_step"]
         return out
     finally:
         for eng in engines.values():
@@ -283,6 +322,8 @@ def main() -> int:
                     help="ms per evaluate of a block step at n_act = 1, 4, 16, ..., N, both paths")
     ap.add_argument("--narrow-cap", type=int, default=65536,
                     help="--active-sweep: largest n_act timed on the narrow path")
+    ap.add_argument("--collisions", action="store_true",
+                    help="the Hermite step with collisions off and on in alternating windows")
     ap.add_argument("--no-rates", action="store_true", help="skip the hermite / kd step rates")
     a = ap.parse_args()
     import torch
@@ -304,6 +345,9 @@ def main() -> int:
     if a.block:
         res["block_24h"] = [block(int(n), 24.0, a.seed, d, a.tight_pairs, not a.no_shared)
                             for n in a.sizes.split(",") for d in a.block_dtypes.split(",")]
+    if a.collisions:
+        res["collisions"] = [collisions(int(n), d, a.seed, a.repeat, a.min_window_s)
+                             for n in a.sizes.split(",") for d in a.dtypes.split(",")]
     if a.active_sweep:
         res["active_sweep"] = [active_sweep(int(n), d, a.seed, a.repeat, a.narrow_cap)
                                for n in a.sizes.split(",") for d in a.dtypes.split(",")]

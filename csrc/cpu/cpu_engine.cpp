@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include <cmath>
+#include <limits>
 #include <type_traits>
 #include <vector>
 #include <stdint.h>
@@ -424,6 +425,79 @@ int accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real, const 
   return 0;
 }
 
+// ---- nearest neighbours (the NN flag of the GPU kernels) ------------------------------------
+// q_ij = r^2 - (R_i + R_j)^2 with the pair's own r^2 (one add, one fma), the smallest over the
+// real j != i whose pair the law does not zero, the lowest j on a tie (a strict less in j order);
+// (+inf, -1) when there is none. MIXED: the separation from double-single rows (H, L).
+template <typename T, bool MIXED>
+inline void nn_one(const T* X4, const T* L4, const T* R, int64_t n_real, int64_t i, T cut2, T eps2,
+                   T* q_out, int32_t* nn_out) {
+  const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2], ri = R[i];
+  T bq = std::numeric_limits<T>::infinity();
+  int32_t bn = -1;
+  for (int64_t j = 0; j < n_real; ++j) {
+    T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+    if (MIXED) {
+      dx = dx + (L4[4 * j] - L4[4 * i]);
+      dy = dy + (L4[4 * j + 1] - L4[4 * i + 1]);
+      dz = dz + (L4[4 * j + 2] - L4[4 * i + 2]);
+    }
+    const T r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
+    const T sr = R[j] + ri;
+    const T qv = std::fma(-sr, sr, r2);
+    if (r2 >= cut2 && j != i && qv < bq) {
+      bq = qv;
+      bn = (int32_t)j;
+    }
+  }
+  *q_out = bq;
+  *nn_out = bn;
+}
+
+// Bodies idx[0..n_idx) (idx null: i0 + k). X4 rows of 4, R n_real radii, all of type T.
+template <typename T>
+int nn_rows(const T* X4, const T* R, int64_t n_real, const int32_t* idx, int64_t i0, int64_t n_idx,
+            T cut2, T eps2, T* q, int32_t* nn) {
+  if (!X4 || !R || !q || !nn || n_idx < 0 || n_real > INT32_MAX ||
+      (!idx && (i0 < 0 || i0 + n_idx > n_real))) {
+    gs_set_error("cpu_nn: bad arguments");
+    return -1;
+  }
+  for (int64_t k = 0; idx && k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= n_real) {
+      gs_set_error("cpu_nn: index out of range");
+      return -1;
+    }
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < n_idx; ++k)
+    nn_one<T, false>(X4, nullptr, R, n_real, idx ? idx[k] : i0 + k, cut2, eps2, q + k, nn + k);
+  return 0;
+}
+
+int nn_rows_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx, int64_t i0,
+                  int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
+  if (!X4 || !R || !q || !nn || n_idx < 0 || n_real > INT32_MAX ||
+      (!idx && (i0 < 0 || i0 + n_idx > n_real))) {
+    gs_set_error("cpu_nn_mixed: bad arguments");
+    return -1;
+  }
+  for (int64_t k = 0; idx && k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= n_real) {
+      gs_set_error("cpu_nn_mixed: index out of range");
+      return -1;
+    }
+  const MixedRows r(X4, X4, n_real);  // (the velocity rows are not used)
+  std::vector<float> Rf(R, R + n_real);
+#pragma omp parallel for schedule(static)
+  for (int64_t k = 0; k < n_idx; ++k) {
+    float qf;
+    nn_one<float, true>(r.H.data(), r.L.data(), Rf.data(), n_real, idx ? idx[k] : i0 + k,
+                        (float)cut2, (float)eps2, &qf, nn + k);
+    q[k] = (double)qf;
+  }
+  return 0;
+}
+
 inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
 
 template <typename T>
@@ -546,6 +620,33 @@ int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, con
                            int64_t n_idx, int32_t chunk, float cut2, float eps2, float* acc4,
                            float* jerk4) {
   return accjerk_idx<float>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
+}
+int gs_cpu_nn_f64(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                  double cut2, double eps2, double* q, int32_t* nn) {
+  return nn_rows<double>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_f32(const float* X4, const float* R, int64_t n_real, int64_t i0, int64_t i1,
+                  float cut2, float eps2, float* q, int32_t* nn) {
+  return nn_rows<float>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_mixed(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                    double cut2, double eps2, double* q, int32_t* nn) {
+  return nn_rows_mixed(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_f64(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows<double>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_f32(const float* X4, const float* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, float cut2, float eps2, float* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows<float>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                        int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows_mixed(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
 }
 int gs_cpu_accjerk_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0,
                          int64_t i1, int32_t chunk, double cut2, double eps2, double* acc4,

@@ -40,6 +40,11 @@ struct gs_hermite {
   int32_t max_level = 24, narrow_max = 0;
   gs::HBlock blk{};
   int64_t macro0 = 0;  // macro steps of dt the run stood at when its state was set
+  // collisions (gs_hermite_set_collisions): 0 off, 1 record, 2 record and stop the shared step
+  int32_t nn = 0;
+  void* R = nullptr;  // radii, state precision
+  int32_t *PN = nullptr, *NNI = nullptr, *nn_i = nullptr, *ca_i = nullptr, *nn_out = nullptr;
+  double *nn_q = nullptr, *ca_q = nullptr, *q_out = nullptr;
 };
 
 namespace {
@@ -72,12 +77,57 @@ gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
   a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
   a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
   a.blk = h->blk;
+  a.nn = h->nn ? 1 : 0;
+  a.R = static_cast<S*>(h->R);
+  a.PN = h->PN; a.NNI = h->NNI;
+  a.nn_q = h->nn_q; a.nn_i = h->nn_i; a.ca_q = h->ca_q; a.ca_i = h->ca_i;
+  a.q_out = h->q_out; a.nn_out = h->nn_out;
   return a;
 }
 
-// Write the control block for a run that stands at time t (stream-ordered).
-int write_ctrl(gs_hermite* h, double t, uint64_t steps, double dt_last, double dt_min) {
+int read_ctrl(gs_hermite* h, gs::HermiteCtrl* c);
+
+// Launch shape (any choice gives the same bits): the widest lane tile that still leaves about
+// four workgroups per CU, then as many chunk groups as reach that count. Mixed precision with
+// collisions on has no 4-body tile (it would need all 256 VGPRs): 2 bodies per lane there,
+// also where the configuration asks for 4, and the layout reports what runs.
+int launch_shape(gs_hermite* h) {
+  const int fp64 = h->cfg.dtype == GS_FP64;
+  const int top = fp64 || (is_mixed(h) && h->nn) ? 2 : 4;
+  const int64_t want = 1024;
+  int ipl = h->cfg.ipl;
+  if (ipl == 0) {
+    ipl = top;
+    while (ipl > (fp64 ? 1 : 2) && h->n_pad / (gs::kForceBlock * ipl) * h->n_chunks < want)
+      ipl >>= 1;
+  }
+  if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
+    gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
+    return -1;
+  }
+  if (ipl > top) ipl = top;
+  h->ipl = ipl;
+  const int64_t blocks = h->n_pad / (gs::kForceBlock * ipl);
+  int64_t groups =
+      h->cfg.split_groups > 0 ? h->cfg.split_groups : (2 * want + blocks - 1) / blocks;
+  if (groups > h->n_chunks) groups = h->n_chunks;
+  if (groups < 1) groups = 1;
+  h->groups = (int32_t)groups;
+  return 0;
+}
+
+// Write the control block for a run that stands at time t (stream-ordered). overlaps < 0: the
+// overlap count stays as it is.
+int write_ctrl(gs_hermite* h, double t, uint64_t steps, double dt_last, double dt_min,
+               int64_t overlaps = -1) {
   gs::HermiteCtrl c{};
+  if (overlaps < 0) {
+    if (read_ctrl(h, &c)) return -1;
+    overlaps = (int64_t)c.overlaps;
+    c = gs::HermiteCtrl{};
+  }
+  c.overlaps = (unsigned long long)overlaps;
+  c.ov_stop = h->nn == 2 ? 1 : 0;
   c.t = t;
   c.h = 0.0;
   c.dt_last = dt_last;
@@ -103,6 +153,10 @@ int read_ctrl(gs_hermite* h, gs::HermiteCtrl* c) {
 // (mixed) through the split of X, V into the fp32 rows.
 template <typename T, typename S>
 int point_at_current(gs_hermite* h, gs::HArgs<T, S>& a) {
+  if (a.nn) {  // (the radii ride in the VP rows)
+    GS_HIP((gs::launch_hermite_stage<T, S>(a, h->stream)));
+    return 0;
+  }
   if constexpr (sizeof(T) == sizeof(S)) {
     a.XP = a.X;
     a.VP = a.V;
@@ -159,6 +213,45 @@ int download_rows(gs_hermite* h, const void* src, int64_t rows, double* out, int
   return 0;
 }
 
+// q and neighbour of the first `rows` rows of the last HM_OUT reduce.
+int download_nn(gs_hermite* h, int64_t rows, double* q, int32_t* nn) {
+  if (!q && !nn) return 0;
+  if (!h->nn) { gs_set_error("hermite: collisions are off"); return -1; }
+  if (q)
+    GS_HIP(hipMemcpyAsync(q, h->q_out, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost,
+                          h->stream));
+  if (nn)
+    GS_HIP(hipMemcpyAsync(nn, h->nn_out, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The per-body records of a run that starts: no neighbour yet, no approach.
+int clear_records(gs_hermite* h, bool latest) {
+  if (!h->nn) return 0;
+  const std::vector<double> inf((size_t)h->n_pad, std::numeric_limits<double>::infinity());
+  const std::vector<int32_t> none((size_t)h->n_pad, -1);
+  for (int k = latest ? 0 : 1; k < 2; ++k) {
+    GS_HIP(hipMemcpyAsync(k ? h->ca_q : h->nn_q, inf.data(), inf.size() * sizeof(double),
+                          hipMemcpyHostToDevice, h->stream));
+    GS_HIP(hipMemcpyAsync(k ? h->ca_i : h->nn_i, none.data(), none.size() * sizeof(int32_t),
+                          hipMemcpyHostToDevice, h->stream));
+  }
+  GS_HIP(hipStreamSynchronize(h->stream));  // (the vectors are on this frame)
+  return 0;
+}
+
+void free_nn(gs_hermite* h) {
+  for (void* p : {h->R, (void*)h->PN, (void*)h->NNI, (void*)h->nn_i, (void*)h->ca_i,
+                  (void*)h->nn_out, (void*)h->nn_q, (void*)h->ca_q, (void*)h->q_out})
+    if (p) (void)hipFree(p);
+  h->R = nullptr;
+  h->PN = h->NNI = h->nn_i = h->ca_i = h->nn_out = nullptr;
+  h->nn_q = h->ca_q = h->q_out = nullptr;
+  h->nn = 0;
+}
+
 int set_wgmin(gs_hermite* h, double first) {
   std::vector<double> w((size_t)nwg(h), std::numeric_limits<double>::infinity());
   w[0] = first;
@@ -197,9 +290,11 @@ int32_t default_narrow_max(const gs_hermite* h) {
 
 void free_block(gs_hermite* h) {
   for (void* p : {(void*)h->blk.bc, (void*)h->blk.tb, (void*)h->blk.level, (void*)h->blk.list,
-                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ})
+                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ,
+                  (void*)h->NNI})
     if (p) (void)hipFree(p);
   h->blk = gs::HBlock{};
+  h->NNI = nullptr;
 }
 
 // (Re)allocate the narrow partial buffer for narrow_max slots.
@@ -209,13 +304,18 @@ int set_narrow(gs_hermite* h, int32_t narrow_max) {
   GS_HIP(hipStreamSynchronize(h->stream));
   if (h->blk.NA) GS_HIP(hipFree(h->blk.NA));
   if (h->blk.NJ) GS_HIP(hipFree(h->blk.NJ));
+  if (h->NNI) GS_HIP(hipFree(h->NNI));
   h->blk.NA = h->blk.NJ = nullptr;
+  h->NNI = nullptr;
   h->blk.cap = narrow_max;
   h->narrow_max = narrow_max;
   if (narrow_max > 0) {
     const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->psz;
     GS_HIP(hipMalloc(&h->blk.NA, bytes));
     GS_HIP(hipMalloc(&h->blk.NJ, bytes));
+    if (h->nn)
+      GS_HIP(hipMalloc((void**)&h->NNI,
+                       (size_t)h->blk.n_slices * (size_t)narrow_max * sizeof(int32_t)));
   }
   gs::HermiteBlockCtrl c;
   if (read_bctrl(h, &c)) return -1;
@@ -291,7 +391,8 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
 
 template <typename T, typename S>
 int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
-                    double* jerk4, int32_t reps = 1, double* ms = nullptr) {
+                    double* jerk4, int32_t reps = 1, double* ms = nullptr, double* q = nullptr,
+                    int32_t* nn = nullptr) {
   gs::HermiteBlockCtrl keep;
   if (read_bctrl(h, &keep)) return -1;
   gs::HermiteBlockCtrl c = keep;
@@ -326,13 +427,14 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
     *ms = (double)t / reps;
   }
   if (download_rows<S>(h, h->a_out, n_idx, acc4, 4) ||
-      download_rows<S>(h, h->j_out, n_idx, jerk4, 4))
+      download_rows<S>(h, h->j_out, n_idx, jerk4, 4) || download_nn(h, n_idx, q, nn))
     return -1;
   return write_bctrl(h, keep);
 }
 
 int start_from_state(gs_hermite* h) {
-  if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity())) return -1;
+  if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) return -1;
+  if (clear_records(h, true)) return -1;
   if (by_dtype(h, [&](auto t, auto s) {
         return eval_current<decltype(t), decltype(s)>(h, gs::HM_INIT, false);
       }))
@@ -343,6 +445,10 @@ int start_from_state(gs_hermite* h) {
 }  // namespace
 
 extern "C" {
+
+static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
+                          int32_t* nn);
 
 int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   if (!cfg || !out) { gs_set_error("hermite: null argument"); return -1; }
@@ -371,26 +477,10 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   h->chunk = chunk;
   h->n_pad = gs::round_up(cfg->n, chunk);
   h->n_chunks = (int32_t)(h->n_pad / chunk);
-  // Launch shape (any choice gives the same bits): the widest lane tile that still leaves
-  // about four workgroups per CU, then as many chunk groups as reach that count.
-  const int64_t want = 1024;
-  int ipl = cfg->ipl;
-  if (ipl == 0) {
-    ipl = fp64 ? 2 : 4;
-    while (ipl > (fp64 ? 1 : 2) && h->n_pad / (gs::kForceBlock * ipl) * h->n_chunks < want)
-      ipl >>= 1;
-  }
-  if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
-    gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
+  if (launch_shape(h)) {
     delete h;
     return -1;
   }
-  h->ipl = ipl;
-  const int64_t blocks = h->n_pad / (gs::kForceBlock * ipl);
-  int64_t groups = cfg->split_groups > 0 ? cfg->split_groups : (2 * want + blocks - 1) / blocks;
-  if (groups > h->n_chunks) groups = h->n_chunks;
-  if (groups < 1) groups = 1;
-  h->groups = (int32_t)groups;
   auto fail = [&](const char*) {
     gs_hermite_destroy(h);
     return -1;
@@ -427,7 +517,7 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
 #undef HM_TRY
   h->mass_host.assign((size_t)h->n, 0.0);
   if (set_wgmin(h, std::numeric_limits<double>::infinity()) ||
-      write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity())) {
+      write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) {
     gs_hermite_destroy(h);
     return -1;
   }
@@ -443,6 +533,7 @@ int gs_hermite_destroy(gs_hermite* h) {
                   (void*)h->ctrl, (void*)h->wgmin, (void*)h->mass_dev, (void*)h->nonfinite})
     if (p) (void)hipFree(p);
   free_block(h);
+  free_nn(h);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -525,6 +616,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
                       dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity());
   }
   // A resumed run: a, j as the last step left them, and the step size its criterion chose.
+  if (clear_records(h, true)) return -1;
   if (f32 ? upload_rows<float>(h, h->A, acc, nullptr, 0.0)
           : upload_rows<double>(h, h->A, acc, nullptr, 0.0))
     return -1;
@@ -534,7 +626,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
   if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
   if (h->block && block_start(h, macro)) return -1;  // (levels afresh until set_block_state)
   return write_ctrl(h, t, 0, 0.0,
-                    dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity());
+                    dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity(), 0);
 }
 
 int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, double* acc,
@@ -553,6 +645,11 @@ int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, 
 }
 
 int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
+  return gs_hermite_derivs_nn(h, acc4, jerk4, nullptr, nullptr);
+}
+
+int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn) {
+  if ((q || nn) && !h->nn) { gs_set_error("hermite derivs_nn: collisions are off"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
   const bool f32 = h->esz == 4;
   if (by_dtype(h, [&](auto t, auto s) {
@@ -562,8 +659,10 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
   if (f32 ? download_rows<float>(h, h->a_out, h->n, acc4, 4)
           : download_rows<double>(h, h->a_out, h->n, acc4, 4))
     return -1;
-  return f32 ? download_rows<float>(h, h->j_out, h->n, jerk4, 4)
-             : download_rows<double>(h, h->j_out, h->n, jerk4, 4);
+  if (f32 ? download_rows<float>(h, h->j_out, h->n, jerk4, 4)
+          : download_rows<double>(h, h->j_out, h->n, jerk4, 4))
+    return -1;
+  return download_nn(h, h->n, q, nn);
 }
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
@@ -599,6 +698,9 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
     out->level_clamped = (int64_t)b.level_clamped;
     out->level_max = b.level_max;
     out->narrow_max = b.narrow_max;
+    gs::HermiteCtrl c0;  // (the evaluation a run starts with counts in the shared block)
+    if (read_ctrl(h, &c0)) return -1;
+    out->overlaps = (int64_t)(b.overlaps + c0.overlaps);
     return 0;
   }
   gs::HermiteCtrl c;
@@ -621,6 +723,7 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   out->ipl = h->ipl;
   out->block_steps = out->body_steps = out->level_clamped = 0;
   out->level_max = out->narrow_max = 0;
+  out->overlaps = (int64_t)c.overlaps;
   return 0;
 }
 
@@ -720,6 +823,21 @@ int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, i
 
 int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                            int32_t reps, double* ms, double* acc4, double* jerk4) {
+  return time_active_nn(h, idx, n_idx, path, reps, ms, acc4, jerk4, nullptr, nullptr);
+}
+
+int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                                double* acc4, double* jerk4, double* q, int32_t* nn) {
+  if (h && (q || nn) && !h->nn) {
+    gs_set_error("hermite derivs_active_nn: collisions are off");
+    return -1;
+  }
+  return time_active_nn(h, idx, n_idx, path, 1, nullptr, acc4, jerk4, q, nn);
+}
+
+static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
+                          int32_t* nn) {
   if (!h || !h->block) { gs_set_error("hermite derivs_active: not in block mode"); return -1; }
   if (reps < 1) reps = 1;
   if (!idx || n_idx < 1 || n_idx > h->n || path < 0 || path > 2) {
@@ -738,8 +856,111 @@ int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int
   }
   GS_HIP(hipSetDevice(h->cfg.device));
   return by_dtype(h, [&](auto t, auto s) {
-    return derivs_active_t<decltype(t), decltype(s)>(h, idx, n_idx, path, acc4, jerk4, reps, ms);
+    return derivs_active_t<decltype(t), decltype(s)>(h, idx, n_idx, path, acc4, jerk4, reps, ms,
+                                                      q, nn);
   });
+}
+
+int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
+  if (!h || on < 0 || on > 2) { gs_set_error("hermite set_collisions: bad arguments"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  if (!on) {
+    free_nn(h);
+    if (launch_shape(h)) return -1;
+    gs::HermiteCtrl c;
+    if (read_ctrl(h, &c)) return -1;
+    return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0);
+  }
+  if (h->n_pad > (int64_t)std::numeric_limits<int32_t>::max()) {
+    gs_set_error("hermite set_collisions: too many bodies for int32 neighbour indices");
+    return -1;
+  }
+  if (!h->nn) {
+    const size_t np = (size_t)h->n_pad;
+    GS_HIP(hipMalloc(&h->R, np * h->esz));
+    GS_HIP(hipMemsetAsync(h->R, 0, np * h->esz, h->stream));
+    GS_HIP(hipMalloc((void**)&h->PN, np * (size_t)h->n_chunks * sizeof(int32_t)));
+    for (int32_t** p : {&h->nn_i, &h->ca_i, &h->nn_out}) {
+      GS_HIP(hipMalloc((void**)p, np * sizeof(int32_t)));
+      GS_HIP(hipMemsetAsync(*p, 0xff, np * sizeof(int32_t), h->stream));
+    }
+    for (double** p : {&h->nn_q, &h->ca_q, &h->q_out}) {
+      GS_HIP(hipMalloc((void**)p, np * sizeof(double)));
+      GS_HIP(hipMemsetAsync(*p, 0, np * sizeof(double), h->stream));
+    }
+    if (h->block && h->blk.cap > 0)
+      GS_HIP(hipMalloc((void**)&h->NNI,
+                       (size_t)h->blk.n_slices * (size_t)h->blk.cap * sizeof(int32_t)));
+  }
+  h->nn = on;
+  if (launch_shape(h)) return -1;
+  if (clear_records(h, true)) return -1;
+  gs::HermiteCtrl c;
+  if (read_ctrl(h, &c)) return -1;
+  return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0);
+}
+
+int gs_hermite_set_radii(gs_hermite* h, const double* r) {
+  if (!h || !r) { gs_set_error("hermite set_radii: null argument"); return -1; }
+  if (!h->nn) { gs_set_error("hermite set_radii: collisions are off"); return -1; }
+  for (int64_t i = 0; i < h->n; ++i)
+    if (!(r[i] >= 0.0) || !std::isfinite(r[i])) {
+      gs_set_error("hermite set_radii: a radius must be finite and >= 0");
+      return -1;
+    }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  std::vector<double> d((size_t)h->n_pad, 0.0);
+  std::vector<float> f;
+  for (int64_t i = 0; i < h->n; ++i) d[(size_t)i] = r[i];
+  const void* src = d.data();
+  if (h->esz == 4) {
+    f.assign(d.begin(), d.end());
+    src = f.data();
+  }
+  GS_HIP(hipMemcpyAsync(h->R, src, (size_t)h->n_pad * h->esz, hipMemcpyHostToDevice, h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+static int get_records(gs_hermite* h, const double* dq, const int32_t* di, double* q,
+                       int32_t* nn) {
+  if (q)
+    GS_HIP(hipMemcpyAsync(q, dq, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost,
+                          h->stream));
+  if (nn)
+    GS_HIP(hipMemcpyAsync(nn, di, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          h->stream));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int gs_hermite_neighbours(gs_hermite* h, double* q, int32_t* nn) {
+  if (!h || !h->nn) { gs_set_error("hermite neighbours: collisions are off"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return get_records(h, h->nn_q, h->nn_i, q, nn);
+}
+
+int gs_hermite_closest(gs_hermite* h, double* q, int32_t* nn, int32_t clear) {
+  if (!h || !h->nn) { gs_set_error("hermite closest: collisions are off"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (get_records(h, h->ca_q, h->ca_i, q, nn)) return -1;
+  return clear ? clear_records(h, false) : 0;
+}
+
+int gs_hermite_clear_overlap(gs_hermite* h) {
+  if (!h) { gs_set_error("hermite clear_overlap: null argument"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  gs::HermiteCtrl c;
+  if (read_ctrl(h, &c)) return -1;
+  if (write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0)) return -1;
+  if (h->block) {
+    gs::HermiteBlockCtrl b;
+    if (read_bctrl(h, &b)) return -1;
+    b.overlaps = 0;
+    return write_bctrl(h, b);
+  }
+  return 0;
 }
 
 int64_t gs_hermite_count_nonfinite(gs_hermite* h) {

@@ -20,6 +20,11 @@
 //     corrector are fp64; the predictor hands the pair kernels the position as a double-single
 //     pair of fp32 rows, hi = float(xp) and lo = float(xp - hi), a third LDS tile, and the pair
 //     term starts from d = (hi_j - hi_i) + (lo_j - lo_i); all else is the fp32 kernel (hsep).
+//   * Collisions (template flag NN, off by default and then compiled out): every body has a
+//     radius, carried in the spare component of the VP row, and the evaluate kernels also keep,
+//     per i-body, the j of the smallest q = r^2 - (R_i + R_j)^2 (the lowest j on an exact tie),
+//     stored per chunk or slice beside the partial sums; the reduce kernels fold them, keep
+//     the latest and the closest (q, j) per body and count the overlaps (q < eps^2).
 // Step chain (one stream, no host round trip): control (next h from the last step's
 // per-workgroup dt minima; advances t, steps) -> predict -> evaluate -> reduce + correct.
 // Block time steps (each body on its own step dt 2^-k; second half of this file): next-time
@@ -52,11 +57,17 @@ struct HLo {
 
 // One i-j interaction: 6 sub, 3 fma (r^2), rsq + select, 3 mul (r^-2, mu r^-1, s), mul + 2 fma
 // (d.w), 2 mul (alpha), 3 fma (a), 3 fma (w - alpha d), 3 fma (j); DS: 3 sub and 3 add more.
-template <typename T, bool PHI, bool DS = false>
+// NN (collisions on): also the pair measure q = r^2 - (R_i + R_j)^2 (one add, one fma on the
+// kernel's own r^2; R_j rides in p.w) and a strict-less compare-and-select against the best so
+// far, so that the lowest j keeps an exact tie. A pair the law zeroes, a ghost row j (jreal
+// false) or the body itself (with softening the law does not zero the self pair) takes no part.
+template <typename T, bool PHI, bool DS = false, bool NN = false>
 __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, const V4<T>& q,
                                           const V4<T>& p, T cut2, T eps2, T& ax, T& ay, T& az,
                                           T& ph, T& jx, T& jy, T& jz, const V4<T>& l = V4<T>(),
-                                          T lxi = T(0), T lyi = T(0), T lzi = T(0)) {
+                                          T lxi = T(0), T lyi = T(0), T lzi = T(0), T ri = T(0),
+                                          bool jreal = false, int32_t jg = 0, int32_t self = 0,
+                                          T* bq = nullptr, int32_t* bn = nullptr) {
   const T dx = hsep<DS>(q.x, xi, l.x, lxi), dy = hsep<DS>(q.y, yi, l.y, lyi),
           dz = hsep<DS>(q.z, zi, l.z, lzi);
   const T wx = p.x - ui, wy = p.y - vi, wz = p.z - wi;
@@ -82,18 +93,29 @@ __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, co
   jy = fma_(s, fma_(-al, dy, wy), jy);
   jz = fma_(s, fma_(-al, dz, wz), jz);
   if constexpr (PHI) ph += mi;
+  if constexpr (NN) {
+    const T sr = p.w + ri;
+    const T qv = fma_(-sr, sr, r2);
+    const T qe = (ok && jreal && jg != self) ? qv : T(INFINITY);
+    const bool lt = qe < *bq;
+    *bq = lt ? qe : *bq;
+    *bn = lt ? jg : *bn;
+  }
 }
 
 // fp32, two i per lane as 2-vectors: each element sees exactly hinteract()'s arithmetic.
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-template <bool PHI, bool DS = false>
+template <bool PHI, bool DS = false, bool NN = false>
 __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, f2 wi,
                                              const V4<float>& q, const V4<float>& p, float cut2,
                                              float eps2, f2& ax, f2& ay, f2& az, f2& ph, f2& jx,
                                              f2& jy, f2& jz, const V4<float>& l = V4<float>(),
                                              f2 lxi = f2(0.0f), f2 lyi = f2(0.0f),
-                                             f2 lzi = f2(0.0f)) {
+                                             f2 lzi = f2(0.0f), f2 ri = f2(0.0f),
+                                             bool jreal = false, int32_t jg = 0,
+                                             const int32_t* self = nullptr, float* bq = nullptr,
+                                             int32_t* bn = nullptr) {
   const f2 dx = hsep<DS>(f2(q.x), xi, f2(l.x), lxi), dy = hsep<DS>(f2(q.y), yi, f2(l.y), lyi),
            dz = hsep<DS>(f2(q.z), zi, f2(l.z), lzi);
   const f2 wx = f2(p.x) - ui, wy = f2(p.y) - vi, wz = f2(p.z) - wi;
@@ -113,6 +135,17 @@ __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, 
   jy = fma2(s, fma2(-al, dy, wy), jy);
   jz = fma2(s, fma2(-al, dz, wz), jz);
   if constexpr (PHI) ph += mi;
+  if constexpr (NN) {
+    const f2 sr = f2(p.w) + ri;
+    const f2 qv = fma2(-sr, sr, r2);
+    const float q0 = (r2.x >= cut2 && jreal && jg != self[0]) ? qv.x : INFINITY;
+    const float q1 = (r2.y >= cut2 && jreal && jg != self[1]) ? qv.y : INFINITY;
+    const bool l0 = q0 < bq[0], l1 = q1 < bq[1];
+    bq[0] = l0 ? q0 : bq[0];
+    bn[0] = l0 ? jg : bn[0];
+    bq[1] = l1 ? q1 : bq[1];
+    bn[1] = l1 ? jg : bn[1];
+  }
 }
 
 template <typename T, int IPL>
@@ -121,6 +154,23 @@ struct HState {
   T ax[IPL], ay[IPL], az[IPL], ph[IPL], jx[IPL], jy[IPL], jz[IPL];  // current chunk
 };
 
+// Nearest neighbour of a lane's i-bodies (NN kernels): own radius and row, the best q of the
+// current chunk or slice and its j.
+template <typename T, int IPL>
+struct HNear {
+  T r[IPL], q[IPL];
+  int32_t n[IPL], self[IPL];
+};
+
+template <typename T, int IPL>
+__device__ __forceinline__ void hnear_reset(HNear<T, IPL>& s) {
+#pragma unroll
+  for (int k = 0; k < IPL; ++k) {
+    s.q[k] = T(INFINITY);
+    s.n[k] = -1;
+  }
+}
+
 template <typename T, int IPL>
 __device__ __forceinline__ void hzero(HState<T, IPL>& s) {
 #pragma unroll
@@ -128,21 +178,31 @@ __device__ __forceinline__ void hzero(HState<T, IPL>& s) {
     s.ax[k] = s.ay[k] = s.az[k] = s.ph[k] = s.jx[k] = s.jy[k] = s.jz[k] = T(0);
 }
 
-template <typename T, int IPL, bool PHI, bool DS = false>
+template <typename T, int IPL, bool PHI, bool DS = false, bool NN = false>
 __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q, const V4<T>& p,
                                               T cut2, T eps2, const V4<T>& l = V4<T>(),
-                                              const HLo<T, IPL>& lo = HLo<T, IPL>()) {
+                                              const HLo<T, IPL>& lo = HLo<T, IPL>(),
+                                              HNear<T, IPL>* nr = nullptr, bool jreal = false,
+                                              int32_t jg = 0) {
   if constexpr (sizeof(T) == 4 && IPL % 2 == 0) {
 #pragma unroll
     for (int k = 0; k < IPL; k += 2) {
       f2 ax = {s.ax[k], s.ax[k + 1]}, ay = {s.ay[k], s.ay[k + 1]}, az = {s.az[k], s.az[k + 1]};
       f2 jx = {s.jx[k], s.jx[k + 1]}, jy = {s.jy[k], s.jy[k + 1]}, jz = {s.jz[k], s.jz[k + 1]};
       f2 ph = {s.ph[k], s.ph[k + 1]};
-      hinteract_pk<PHI, DS>(
-          f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
-          f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2, eps2,
-          ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]}, f2{lo.y[k], lo.y[k + 1]},
-          f2{lo.z[k], lo.z[k + 1]});
+      if constexpr (NN)
+        hinteract_pk<PHI, DS, true>(
+            f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
+            f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
+            eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
+            f2{lo.y[k], lo.y[k + 1]}, f2{lo.z[k], lo.z[k + 1]}, f2{nr->r[k], nr->r[k + 1]}, jreal,
+            jg, &nr->self[k], &nr->q[k], &nr->n[k]);
+      else
+        hinteract_pk<PHI, DS>(
+            f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
+            f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
+            eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
+            f2{lo.y[k], lo.y[k + 1]}, f2{lo.z[k], lo.z[k + 1]});
       s.ax[k] = ax.x; s.ax[k + 1] = ax.y;
       s.ay[k] = ay.x; s.ay[k + 1] = ay.y;
       s.az[k] = az.x; s.az[k + 1] = az.y;
@@ -154,10 +214,17 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
     return;
   }
 #pragma unroll
-  for (int k = 0; k < IPL; ++k)
-    hinteract<T, PHI, DS>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
-                          s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
-                          lo.x[k], lo.y[k], lo.z[k]);
+  for (int k = 0; k < IPL; ++k) {
+    if constexpr (NN)
+      hinteract<T, PHI, DS, true>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
+                                  s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k],
+                                  l, lo.x[k], lo.y[k], lo.z[k], nr->r[k], jreal, jg, nr->self[k],
+                                  &nr->q[k], &nr->n[k]);
+    else
+      hinteract<T, PHI, DS>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
+                            s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
+                            lo.x[k], lo.y[k], lo.z[k]);
+  }
 }
 
 // EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
@@ -166,7 +233,10 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
 // slot and i-blocks beyond n_act exit; the j loop, hence a body's bits, is the same.
 // Mixed precision (S is not T): a third tile carries the lo rows XL, the lane keeps the lo rows
 // of its i-bodies, and only the separation differs (hsep).
-template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T>
+// NN: the lane also keeps the nearest neighbour (smallest q, lowest j on a tie) of each of its
+// i-bodies over the chunk; the partial is (PJ[c][i].w, PN[c][i]). j is uniform over the wave, so
+// the ghost-row test is a scalar compare.
+template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T, bool NN = false>
 __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int gated) {
   constexpr bool DS = sizeof(S) != sizeof(T);
   constexpr int TB = Tile<T>::kBodies;
@@ -195,6 +265,7 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
   const V4<T>* XL = reinterpret_cast<const V4<T>*>(a.XL);
   HState<T, IPL> st;
   HLo<T, IPL> lo;
+  HNear<T, IPL> nr;
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
     int64_t row = ib + threadIdx.x + k * kBlock;
@@ -203,6 +274,10 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
     const V4<T> v = VP[row];
     st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
     st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+    if constexpr (NN) {
+      nr.r[k] = v.w;
+      nr.self[k] = (int32_t)row;
+    }
     if constexpr (DS) {
       const V4<T> l = XL[row];
       lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
@@ -216,6 +291,7 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
   };
   fill(0);
   hzero<T, IPL>(st);
+  if constexpr (NN) hnear_reset<T, IPL>(nr);
   for (int t = 0; t < ntiles; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile t is in LDS for every wave; buffer (t+1)&1 is free
@@ -223,13 +299,29 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
     const V4<T>* cx = tx[t & 1];
     const V4<T>* cv = tv[t & 1];
     const V4<T>* cl = tl[t & 1];
+    if constexpr (NN) {
+      const int32_t jb = (int32_t)((int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB);
+      const int32_t nreal = (int32_t)a.n_real;
 #pragma unroll 4
-    for (int j = 0; j < TB; ++j) {
-      const V4<T> q = cx[j], p = cv[j];  // uniform addresses: broadcast ds_reads
-      if constexpr (DS)
-        hinteract_all<T, IPL, PHI, true>(st, q, p, a.cut2, a.eps2, cl[j], lo);
-      else
-        hinteract_all<T, IPL, PHI>(st, q, p, a.cut2, a.eps2);
+      for (int j = 0; j < TB; ++j) {
+        const V4<T> q = cx[j], p = cv[j];
+        const int32_t jg = jb + j;
+        if constexpr (DS)
+          hinteract_all<T, IPL, PHI, true, true>(st, q, p, a.cut2, a.eps2, cl[j], lo, &nr,
+                                                 jg < nreal, jg);
+        else
+          hinteract_all<T, IPL, PHI, false, true>(st, q, p, a.cut2, a.eps2, V4<T>(),
+                                                  HLo<T, IPL>(), &nr, jg < nreal, jg);
+      }
+    } else {
+#pragma unroll 4
+      for (int j = 0; j < TB; ++j) {
+        const V4<T> q = cx[j], p = cv[j];  // uniform addresses: broadcast ds_reads
+        if constexpr (DS)
+          hinteract_all<T, IPL, PHI, true>(st, q, p, a.cut2, a.eps2, cl[j], lo);
+        else
+          hinteract_all<T, IPL, PHI>(st, q, p, a.cut2, a.eps2);
+      }
     }
     if ((t + 1) % tpc == 0) {
       const int c = c0 + t / tpc;
@@ -238,10 +330,15 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
         V4<T> oa, oj;
         oa.x = st.ax[k]; oa.y = st.ay[k]; oa.z = st.az[k]; oa.w = st.ph[k];
         oj.x = st.jx[k]; oj.y = st.jy[k]; oj.z = st.jz[k]; oj.w = T(0);
+        if constexpr (NN) {
+          oj.w = nr.q[k];
+          a.PN[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = nr.n[k];
+        }
         PA[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oa;
         PJ[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oj;
       }
       hzero<T, IPL>(st);
+      if constexpr (NN) hnear_reset<T, IPL>(nr);
     }
   }
 }
@@ -263,7 +360,8 @@ __device__ __forceinline__ double block_min(double v, double* red) {
 
 // CONTROL (one workgroup): the step the chain is about to take. h = min(dt_max, min_i dt_i)
 // from the last reduce's per-workgroup minima (adaptive) or dt_max (fixed), cut to t_end - t;
-// once t >= t_end the chain's other kernels return at once and nothing is counted.
+// once t >= t_end, or (collisions "stop") once a step has seen an overlap, the chain's other
+// kernels return at once and nothing is counted.
 __global__ __launch_bounds__(kBlock) void hermite_ctrl_kernel(HermiteCtrl* ctrl,
                                                               const double* wgmin, int nwg) {
   __shared__ double red[kBlock / 64];
@@ -272,8 +370,8 @@ __global__ __launch_bounds__(kBlock) void hermite_ctrl_kernel(HermiteCtrl* ctrl,
   m = block_min(m, red);
   if (threadIdx.x != 0) return;
   HermiteCtrl c = *ctrl;
-  if (c.has_end && c.t >= c.t_end) {
-    ctrl->active = 0;
+  if ((c.has_end && c.t >= c.t_end) || (c.ov_stop && c.overlaps != 0)) {
+    ctrl->active = 0;  // (an overlap seen by the last reduce: the run stops at that step)
     return;
   }
   double h = c.dt_max;
@@ -295,12 +393,14 @@ __global__ __launch_bounds__(kBlock) void hermite_ctrl_kernel(HermiteCtrl* ctrl,
 // PREDICT: xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2 (ghost rows stay zero).
 // Store row i of the predicted state for the evaluate kernels: as it is, or (mixed precision,
 // S is not T) the position split into XP = (float(xp), mu), XL = (float(xp - double(hi)), 0).
-template <typename T, typename S>
+// NN: the spare component of the VP row carries the body's radius (R, state precision).
+template <typename T, typename S, bool NN = false>
 __device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i, const V4<S>& xp,
                                                 const V4<S>& vp) {
   V4<T> h, v;
   h.x = (T)xp.x; h.y = (T)xp.y; h.z = (T)xp.z; h.w = (T)xp.w;
   v.x = (T)vp.x; v.y = (T)vp.y; v.z = (T)vp.z; v.w = T(0);
+  if constexpr (NN) v.w = (T)a.R[i];
   reinterpret_cast<V4<T>*>(a.XP)[i] = h;
   reinterpret_cast<V4<T>*>(a.VP)[i] = v;
   if constexpr (sizeof(S) != sizeof(T)) {
@@ -310,7 +410,7 @@ __device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i,
   }
 }
 
-template <typename T, typename S>
+template <typename T, typename S, bool NN = false>
 __global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) {
   if (!a.ctrl->active) return;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -331,7 +431,7 @@ __global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) 
     vp.y = v.y + (ac.y * h + jk.y * h2);
     vp.z = v.z + (ac.z * h + jk.z * h2);
   }
-  store_predicted<T, S>(a, i, xp, vp);
+  store_predicted<T, S, NN>(a, i, xp, vp);
 }
 
 // SPLIT (mixed precision): the predictor's output at h = 0, for the derivatives of the current
@@ -343,6 +443,30 @@ __global__ __launch_bounds__(kBlock) void hermite_split_kernel(HArgs<float, doub
                                  reinterpret_cast<const V4<double>*>(a.V)[i]);
 }
 
+// STAGE (collisions on): XP, VP (and XL) <- the current X, V with the radius in VP's spare
+// component, for an evaluation of the current state in any precision.
+template <typename T, typename S>
+__global__ __launch_bounds__(kBlock) void hermite_stage_kernel(HArgs<T, S> a) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n_pad) return;
+  store_predicted<T, S, true>(a, i, reinterpret_cast<const V4<S>*>(a.X)[i],
+                              reinterpret_cast<const V4<S>*>(a.V)[i]);
+}
+
+// The latest (q, nn) of body i, its closest-approach record since the last clear, and the
+// overlap count (q < eps2, that is |d|^2 < (R_i + R_j)^2) of the control block.
+template <typename T, typename S>
+__device__ __forceinline__ void nn_record(const HArgs<T, S>& a, int64_t i, T q, int32_t nn,
+                                          unsigned long long* overlaps) {
+  a.nn_q[i] = (double)q;
+  a.nn_i[i] = nn;
+  if ((double)q < a.ca_q[i]) {
+    a.ca_q[i] = (double)q;
+    a.ca_i[i] = nn;
+  }
+  if (q < a.eps2) atomicAdd(overlaps, 1ull);
+}
+
 __device__ __forceinline__ double norm3(double x, double y, double z) {
   return sqrt(x * x + y * y + z * z);
 }
@@ -351,7 +475,9 @@ __device__ __forceinline__ double norm3(double x, double y, double z) {
 // HM_STEP applies the corrector and Aarseth's criterion, HM_INIT starts a run from (x, v),
 // HM_OUT returns the derivatives. Per-workgroup dt minima go to wgmin (+inf when no body of the
 // workgroup takes part: ghost rows, |j| = 0, a non-finite ratio, or a fixed-step run).
-template <typename T, typename S>
+// NN: the chunks' (q, j) partials fold with a strict less in chunk order (the lowest j keeps a
+// tie); HM_OUT writes them to q_out / nn_out, the other modes record them (nn_record).
+template <typename T, typename S, bool NN = false>
 __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
   __shared__ double red[kBlock / 64];
   if (a.mode == HM_STEP && !a.ctrl->active) return;
@@ -359,11 +485,19 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
   const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
   const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
   S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
+  T bq = T(INFINITY);
+  int32_t bn = -1;
   for (int c = 0; c < a.n_chunks; ++c) {
     const V4<T> pa = PA[(int64_t)c * a.n_pad + i];
     const V4<T> pj = PJ[(int64_t)c * a.n_pad + i];
     a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
     j1x += pj.x; j1y += pj.y; j1z += pj.z;
+    if constexpr (NN) {
+      if (pj.w < bq) {
+        bq = pj.w;
+        bn = a.PN[(int64_t)c * a.n_pad + i];
+      }
+    }
   }
   if (a.mode == HM_OUT) {
     V4<S> oa, oj;
@@ -371,7 +505,14 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
     oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
     reinterpret_cast<V4<S>*>(a.a_out)[i] = oa;
     reinterpret_cast<V4<S>*>(a.j_out)[i] = oj;
+    if constexpr (NN) {
+      a.q_out[i] = (double)bq;
+      a.nn_out[i] = bn;
+    }
     return;
+  }
+  if constexpr (NN) {
+    if (i < a.n_real) nn_record<T, S>(a, i, bq, bn, &a.ctrl->overlaps);
   }
   V4<S>* A = reinterpret_cast<V4<S>*>(a.A);
   V4<S>* J = reinterpret_cast<V4<S>*>(a.J);
@@ -506,7 +647,7 @@ __global__ __launch_bounds__(kBlock) void block_ctrl_kernel(HermiteBlockCtrl* bc
 
 // PREDICT-ALL + MARK: every real body from its own tb to t_next; counts the due bodies of the
 // workgroup for the compaction.
-template <typename T, typename S>
+template <typename T, typename S, bool NN = false>
 __global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T, S> a) {
   __shared__ int cnt[kBlock / 64];
   const HBlock& b = a.blk;
@@ -532,7 +673,7 @@ __global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T, S> a) {
     vp.y = v.y + (ac.y * h + jk.y * h2);
     vp.z = v.z + (ac.z * h + jk.z * h2);
   }
-  store_predicted<T, S>(a, i, xp, vp);
+  store_predicted<T, S, NN>(a, i, xp, vp);
   const int c = __popcll(__ballot(due));
   if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -582,11 +723,15 @@ __global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T, S> a) {
 // four waves in order through LDS) and one partial per (slice, slot) is stored. Slice length and
 // tree depend on n_pad only, so a body's bits depend neither on the other active bodies nor on
 // its slot. fp32 runs two i-bodies as 2-vectors (hinteract_pk).
-template <typename T, bool PHI, typename S = T>
+// NN: a lane folds its rows with a strict less in j order; the lanes' and the waves' (q, j) fold
+// lexicographically (the smaller q, on a tie the lower j); the partial is (NJ[s][slot].w,
+// NNI[s][slot]).
+template <typename T, bool PHI, typename S = T, bool NN = false>
 __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
   constexpr bool DS = sizeof(S) != sizeof(T);
   constexpr int G = kNarrowGroup;
   __shared__ T red[kBlock / 64][G][8];
+  __shared__ int32_t redn[kBlock / 64][NN ? G : 1];
   const HBlock& b = a.blk;
   if (!b.bc->active || b.bc->path != HP_NARROW) return;
   const int n_act = min(b.bc->n_act, b.cap);
@@ -602,6 +747,7 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
   for (int g = blockIdx.y; g < ngroups; g += (int)gridDim.y) {
     HState<T, G> st;
     HLo<T, G> lo;
+    HNear<T, G> nr;
 #pragma unroll
     for (int k = 0; k < G; ++k) {
       const int slot = min(g * G + k, n_act - 1);  // (spare slots of the last group: a copy)
@@ -610,18 +756,31 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
       const V4<T> v = VP[row];
       st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
       st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+      if constexpr (NN) {
+      nr.r[k] = v.w;
+      nr.self[k] = (int32_t)row;
+    }
       if constexpr (DS) {
         const V4<T> l = XL[row];
         lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
       }
     }
     hzero<T, G>(st);
+    if constexpr (NN) hnear_reset<T, G>(nr);
     for (int64_t j = j0 + threadIdx.x; j < j1; j += kBlock) {
       const V4<T> q = XP[j], p = VP[j];
-      if constexpr (DS)
+      if constexpr (NN) {
+        if constexpr (DS)
+          hinteract_all<T, G, PHI, true, true>(st, q, p, a.cut2, a.eps2, XL[j], lo, &nr,
+                                               j < a.n_real, (int32_t)j);
+        else
+          hinteract_all<T, G, PHI, false, true>(st, q, p, a.cut2, a.eps2, V4<T>(), HLo<T, G>(),
+                                                &nr, j < a.n_real, (int32_t)j);
+      } else if constexpr (DS) {
         hinteract_all<T, G, PHI, true>(st, q, p, a.cut2, a.eps2, XL[j], lo);
-      else
+      } else {
         hinteract_all<T, G, PHI>(st, q, p, a.cut2, a.eps2);
+      }
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -630,6 +789,21 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
       for (int c = 0; c < 7; ++c) {
         for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_down(v[c], off, 64);
         if (lane == 0) red[wave][k][c] = v[c];
+      }
+      if constexpr (NN) {
+        T bq = nr.q[k];
+        int32_t bn = nr.n[k];
+        for (int off = 32; off > 0; off >>= 1) {
+          const T oq = __shfl_down(bq, off, 64);
+          const int32_t on = __shfl_down(bn, off, 64);
+          const bool take = oq < bq || (oq == bq && on < bn);
+          bq = take ? oq : bq;
+          bn = take ? on : bn;
+        }
+        if (lane == 0) {
+          red[wave][k][7] = bq;
+          redn[wave][k] = bn;
+        }
       }
     }
     __syncthreads();
@@ -642,6 +816,20 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
       oa.x = v[0]; oa.y = v[1]; oa.z = v[2]; oa.w = v[3];
       oj.x = v[4]; oj.y = v[5]; oj.z = v[6]; oj.w = T(0);
       const int64_t o = (int64_t)blockIdx.x * b.cap + (g * G + k);
+      if constexpr (NN) {
+        T bq = red[0][k][7];
+        int32_t bn = redn[0][k];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) {
+          const T oq = red[w][k][7];
+          const int32_t on = redn[w][k];
+          const bool take = oq < bq || (oq == bq && on < bn);
+          bq = take ? oq : bq;
+          bn = take ? on : bn;
+        }
+        oj.w = bq;
+        a.NNI[o] = bn;
+      }
       NA[o] = oa;
       NJ[o] = oj;
     }
@@ -654,7 +842,7 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
 // body's own h, Aarseth's dt_want and the level rule: any number of halvings (capped at L), at
 // most one doubling and only where t_next allows the doubled step. HM_OUT: the sums go to
 // a_out / j_out [slot] and nothing else is touched.
-template <typename T, typename S>
+template <typename T, typename S, bool NN = false>
 __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
   const HBlock& b = a.blk;
   HermiteBlockCtrl* bc = b.bc;
@@ -662,6 +850,8 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
   const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= bc->n_act) return;
   S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
+  T bq = T(INFINITY);
+  int32_t bn = -1;
   if (bc->path == HP_NARROW) {
     const V4<T>* NA = reinterpret_cast<const V4<T>*>(b.NA);
     const V4<T>* NJ = reinterpret_cast<const V4<T>*>(b.NJ);
@@ -671,6 +861,12 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
       const V4<T> pj = NJ[(int64_t)c * b.cap + s];
       a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
       j1x += pj.x; j1y += pj.y; j1z += pj.z;
+      if constexpr (NN) {
+        if (pj.w < bq) {
+          bq = pj.w;
+          bn = a.NNI[(int64_t)c * b.cap + s];
+        }
+      }
     }
   } else {
     const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
@@ -680,6 +876,12 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
       const V4<T> pj = PJ[(int64_t)c * a.n_pad + s];
       a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
       j1x += pj.x; j1y += pj.y; j1z += pj.z;
+      if constexpr (NN) {
+        if (pj.w < bq) {
+          bq = pj.w;
+          bn = a.PN[(int64_t)c * a.n_pad + s];
+        }
+      }
     }
   }
   if (a.mode == HM_OUT) {
@@ -688,9 +890,14 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
     oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
     reinterpret_cast<V4<S>*>(a.a_out)[s] = oa;
     reinterpret_cast<V4<S>*>(a.j_out)[s] = oj;
+    if constexpr (NN) {
+      a.q_out[s] = (double)bq;
+      a.nn_out[s] = bn;
+    }
     return;
   }
   const int64_t i = b.list[s];
+  if constexpr (NN) nn_record<T, S>(a, i, bq, bn, &bc->overlaps);
   const int L = bc->L;
   const int64_t t_next = bc->t_ticks;
   const double dt_max = bc->dt_max, eta = bc->eta;
@@ -776,6 +983,23 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64
 template <typename T, typename S, int IPL>
 static hipError_t launch_eval_t(const HArgs<T, S>& a, int groups, bool gated, hipStream_t s) {
   const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
+  // Mixed precision with collisions on would need all 256 VGPRs at 4 i-bodies per lane: that
+  // kernel is not built, and the runtime's launch shape never asks for it (hermite.hip).
+  constexpr bool kNoNN = IPL == 4 && sizeof(S) != sizeof(T);
+  if constexpr (kNoNN) {
+    if (a.nn) return hipErrorInvalidValue;
+  }
+  if constexpr (!kNoNN) {
+    if (a.nn) {
+      if (a.phi)
+        hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S, true>), grid,
+                           dim3(kBlock), 0, s, a, (int)gated);
+      else
+        hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S, true>), grid,
+                           dim3(kBlock), 0, s, a, (int)gated);
+      return hipGetLastError();
+    }
+  }
   if (a.phi)
     hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S>), grid, dim3(kBlock), 0, s, a,
                        (int)gated);
@@ -785,6 +1009,13 @@ static hipError_t launch_eval_t(const HArgs<T, S>& a, int groups, bool gated, hi
   return hipGetLastError();
 }
 
+// The arrays a collisions-on launch writes.
+template <typename T, typename S>
+static bool nn_args_ok(const HArgs<T, S>& a) {
+  return a.R && a.PN && a.nn_q && a.nn_i && a.ca_q && a.ca_i && a.q_out && a.nn_out &&
+         a.n_pad <= INT32_MAX;
+}
+
 bool hermite_ipl_ok(int fp64, int ipl) { return ipl == 1 || ipl == 2 || (ipl == 4 && !fp64); }
 
 template <typename T, typename S>
@@ -792,7 +1023,7 @@ hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool g
                                hipStream_t s) {
   if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
       (int64_t)a.n_chunks * a.chunk != a.n_pad || (gated && !a.ctrl) ||
-      (sizeof(S) != sizeof(T) && !a.XL))
+      (sizeof(S) != sizeof(T) && !a.XL) || (a.nn && !nn_args_ok(a)))
     return hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   if (groups > a.n_chunks) groups = a.n_chunks;
@@ -815,8 +1046,12 @@ hipError_t launch_hermite_ctrl(const HArgs<T, S>& a, hipStream_t s) {
 
 template <typename T, typename S>
 hipError_t launch_hermite_predict(const HArgs<T, S>& a, hipStream_t s) {
-  hipLaunchKernelGGL((hermite_predict_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
-                     dim3(kBlock), 0, s, a);
+  if (a.nn)
+    hipLaunchKernelGGL((hermite_predict_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((hermite_predict_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
@@ -827,9 +1062,21 @@ hipError_t launch_hermite_split(const HArgs<float, double>& a, hipStream_t s) {
 }
 
 template <typename T, typename S>
-hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s) {
-  hipLaunchKernelGGL((hermite_reduce_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
+hipError_t launch_hermite_stage(const HArgs<T, S>& a, hipStream_t s) {
+  if (!a.R) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((hermite_stage_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
                      dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T, typename S>
+hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s) {
+  if (a.nn)
+    hipLaunchKernelGGL((hermite_reduce_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((hermite_reduce_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
@@ -852,7 +1099,10 @@ hipError_t launch_block_next(const HArgs<T, S>& a, hipStream_t s) {
 template <typename T, typename S>
 hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s) {
   const unsigned nwg = (unsigned)(a.n_pad / kBlock);
-  hipLaunchKernelGGL((block_predict_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
+  if (a.nn)
+    hipLaunchKernelGGL((block_predict_kernel<T, S, true>), dim3(nwg), dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((block_predict_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
   hipLaunchKernelGGL((block_compact_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
@@ -862,11 +1112,16 @@ hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s) {
   const HBlock& b = a.blk;
   if (b.cap < 1) return hipSuccess;  // (narrow_max 0: every step is wide)
   if (b.slice < kBlock || b.slice % kBlock || (int64_t)b.n_slices * b.slice < a.n_pad ||
-      !b.NA || !b.NJ || (sizeof(S) != sizeof(T) && !a.XL))
+      !b.NA || !b.NJ || (sizeof(S) != sizeof(T) && !a.XL) ||
+      (a.nn && (!nn_args_ok(a) || !a.NNI)))
     return hipErrorInvalidValue;
   const int groups = (b.cap + kNarrowGroup - 1) / kNarrowGroup;
   const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
-  if (a.phi)
+  if (a.nn && a.phi)
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, true, S, true>), grid, dim3(kBlock), 0, s, a);
+  else if (a.nn)
+    hipLaunchKernelGGL((hermite_narrow_kernel<T, false, S, true>), grid, dim3(kBlock), 0, s, a);
+  else if (a.phi)
     hipLaunchKernelGGL((hermite_narrow_kernel<T, true, S>), grid, dim3(kBlock), 0, s, a);
   else
     hipLaunchKernelGGL((hermite_narrow_kernel<T, false, S>), grid, dim3(kBlock), 0, s, a);
@@ -876,7 +1131,13 @@ hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s) {
 template <typename T, typename S, int IPL>
 static hipError_t launch_wide_t(const HArgs<T, S>& a, int groups, hipStream_t s) {
   const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
-  if (a.phi)
+  if (a.nn && a.phi)
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true, S, true>), grid, dim3(kBlock), 0,
+                       s, a, 0);
+  else if (a.nn)
+    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true, S, true>), grid, dim3(kBlock), 0,
+                       s, a, 0);
+  else if (a.phi)
     hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true, S>), grid, dim3(kBlock), 0, s, a,
                        0);
   else
@@ -889,7 +1150,7 @@ template <typename T, typename S>
 hipError_t launch_block_wide(const HArgs<T, S>& a, int ipl, int groups, hipStream_t s) {
   if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
       (int64_t)a.n_chunks * a.chunk != a.n_pad || !a.blk.bc || !a.blk.list ||
-      (sizeof(S) != sizeof(T) && !a.XL))
+      (sizeof(S) != sizeof(T) && !a.XL) || (a.nn && !nn_args_ok(a)))
     return hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   if (groups > a.n_chunks) groups = a.n_chunks;
@@ -905,8 +1166,12 @@ hipError_t launch_block_wide(const HArgs<T, S>& a, int ipl, int groups, hipStrea
 
 template <typename T, typename S>
 hipError_t launch_block_correct(const HArgs<T, S>& a, hipStream_t s) {
-  hipLaunchKernelGGL((block_correct_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
-                     0, s, a);
+  if (a.nn)
+    hipLaunchKernelGGL((block_correct_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((block_correct_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
+                       dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
@@ -922,6 +1187,7 @@ hipError_t launch_block_init(const HArgs<T, S>& a, int64_t t0, hipStream_t s) {
   template hipError_t launch_hermite_predict<T, S>(const HArgs<T, S>&, hipStream_t);             \
   template hipError_t launch_hermite_eval<T, S>(const HArgs<T, S>&, int, int, bool, hipStream_t); \
   template hipError_t launch_hermite_reduce<T, S>(const HArgs<T, S>&, hipStream_t);              \
+  template hipError_t launch_hermite_stage<T, S>(const HArgs<T, S>&, hipStream_t);               \
   template hipError_t launch_block_next<T, S>(const HArgs<T, S>&, hipStream_t);                  \
   template hipError_t launch_block_predict<T, S>(const HArgs<T, S>&, hipStream_t);               \
   template hipError_t launch_block_narrow<T, S>(const HArgs<T, S>&, hipStream_t);                \

@@ -197,6 +197,23 @@ int gs_cpu_accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real,
 int gs_cpu_hermite_step_mixed(double* X4, double* V4, double* A4, double* J4, double* scratch,
                               int64_t n_real, int32_t chunk, double h, double cut2, double eps2,
                               double eta, double* dt_min_out);
+// Nearest neighbour of bodies [i0, i1) (or idx[0..n_idx)) by the pair measure
+// q_ij = r^2 - (R_i + R_j)^2 of gs_hermite_set_collisions, with the arithmetic of the GPU
+// kernels: r^2 as gs_cpu_accjerk_*, one add and one fma for q, a strict less in j order (the
+// lowest j keeps a tie), pairs with r^2 < cut2 left out; (+inf, -1) when there is none. R: n_real
+// radii. Row k of q / nn belongs to body i0 + k (idx[k]). mixed: as gs_cpu_accjerk_mixed.
+int gs_cpu_nn_f64(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                  double cut2, double eps2, double* q, int32_t* nn);
+int gs_cpu_nn_f32(const float* X4, const float* R, int64_t n_real, int64_t i0, int64_t i1,
+                  float cut2, float eps2, float* q, int32_t* nn);
+int gs_cpu_nn_mixed(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                    double cut2, double eps2, double* q, int32_t* nn);
+int gs_cpu_nn_idx_f64(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn);
+int gs_cpu_nn_idx_f32(const float* X4, const float* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, float cut2, float eps2, float* q, int32_t* nn);
+int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                        int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn);
 int gs_cpu_num_threads(void);
 int gs_cpu_set_threads(int32_t n);  // OpenMP threads for the CPU engine (returns the new max)
 
@@ -315,6 +332,8 @@ typedef struct gs_hermite_info {
   int64_t level_clamped;  // times a body wanted a step below dt 2^-max_level
   int32_t level_max;      // deepest level any body has had
   int32_t narrow_max;     // active-set size up to which the j-parallel evaluate runs
+  // collisions (0 when off)
+  int64_t overlaps;       // bodies the reduces have seen overlapping their nearest neighbour
 } gs_hermite_info;
 int gs_hermite_create(const gs_config* cfg, gs_hermite** out);
 int gs_hermite_destroy(gs_hermite* h);
@@ -365,6 +384,36 @@ int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, i
 // per evaluate + reduce (bench/hermite_rate.py --active-sweep); acc4 / jerk4 may be NULL.
 int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                            int32_t reps, double* ms, double* acc4, double* jerk4);
+
+// Nearest neighbours and collision detection, from the acceleration+jerk kernels themselves.
+// Every body has a radius R >= 0; the pair measure of bodies i and j is
+//   q_ij = r^2_ij - (R_i + R_j)^2        (r^2 the kernel's own: |d|^2 + softening^2),
+// one fma on the pair's r^2 in the pair type. The nearest neighbour of i is the real body
+// j != i of the smallest q_ij (massless bodies take part; a pair the pair law zeroes, r^2 <
+// cutoff^2, does not), the lowest j on an exact tie, and (+inf, -1) when there is none. With all
+// radii 0 it is the nearest body by distance. Body i overlaps its neighbour when
+// q_i < softening^2, that is |d|^2 < (R_i + R_j)^2. q and the neighbour of a body are
+// bit-identical across ipl, chunk groups, the block paths, active sets and slots.
+// on: 0 off (the default: the kernels of a run without collisions are unchanged), 1 record,
+// 2 record and stop: a shared-step run takes no further step once a step has seen an overlap
+// (later gs_hermite_step calls are no-ops, as past t_end) until gs_hermite_clear_overlap; a
+// block-step run always runs on to the macro boundary. Call before the state is set. The call
+// re-resolves the launch shape: a GS_MIXED run with collisions on has 2 i-bodies per lane at
+// most (gs_hermite_layout and gs_hermite_info.ipl report what runs).
+int gs_hermite_set_collisions(gs_hermite* h, int32_t on);
+int gs_hermite_set_radii(gs_hermite* h, const double* r);  // n radii [m]; before the state
+// The latest q and neighbour of every body (n each; either may be NULL): from the evaluation
+// the run started with, or the last step that corrected the body.
+int gs_hermite_neighbours(gs_hermite* h, double* q, int32_t* nn);
+// Closest approach: the smallest q over the body's evaluations since the record was last
+// cleared (by setting a state, or by clear != 0 here), and the neighbour then.
+int gs_hermite_closest(gs_hermite* h, double* q, int32_t* nn, int32_t clear);
+int gs_hermite_clear_overlap(gs_hermite* h);  // overlaps <- 0: a stopped run steps again
+// gs_hermite_derivs / gs_hermite_derivs_active with q and the neighbour of each row too
+// (either may be NULL); neither touches the records or the overlap count.
+int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn);
+int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                                double* acc4, double* jerk4, double* q, int32_t* nn);
 
 // Virtual ranks on one device: shards[r] created with rank r of P; steps all of them in
 // lockstep with the all-gather done by device copies (the RCCL schedule without RCCL).

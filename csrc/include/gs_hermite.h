@@ -19,6 +19,10 @@ struct HermiteCtrl {
   unsigned long long steps;  // steps taken (no-op launches past t_end are not counted)
   int32_t has_end;
   int32_t active;  // 1 while the chain of the current launch takes a step, 0 once t >= t_end
+  // collisions (gs_hermite_set_collisions; both 0 otherwise)
+  unsigned long long overlaps;  // bodies seen with q < eps2 by the reduces so far
+  int32_t ov_stop;              // 1: the chain takes no further step once overlaps != 0
+  int32_t pad_;
 };
 
 // Control block of a block-step run (individual steps dt_max 2^-k): time is a count of ticks of
@@ -35,6 +39,7 @@ struct HermiteBlockCtrl {
   int32_t narrow_max;  // n_act <= narrow_max: narrow path
   int32_t path;        // HP_* of the current block step
   int32_t active;      // 1 while the current chain takes a block step
+  unsigned long long overlaps;  // collisions: active bodies corrected with q < eps2 so far
 };
 enum { HP_NARROW = 1, HP_WIDE = 2 };
 
@@ -83,6 +88,20 @@ struct HArgs {
   HBlock blk;        // block-step mode (all null otherwise)
   T* XL;             // mixed precision: lo rows of the predicted position (last: the fields
                      // above keep the offsets the fp32 and fp64 kernels were tuned with)
+  // Collisions (nn != 0; all null otherwise; after XL for the same reason, and the narrow
+  // path's NNI here and not in HBlock, which sits before XL). Pair measure of bodies i, j:
+  // q = r^2 - (R_i + R_j)^2 with the kernel's own r^2; the nearest neighbour of i is the real
+  // j != i of the smallest q, the lowest j on an exact tie, (+inf, -1) when there is none.
+  S* R;              // [n_pad] radius (ghost rows 0); rides in the VP row's spare component
+  int32_t* PN;       // [n_chunks][n_pad] j of the chunk partial whose q is PJ[c][i].w
+  int32_t* NNI;      // [n_slices][cap] the same beside NJ (narrow path)
+  double* nn_q;      // [n_pad] latest q of each body, and
+  int32_t* nn_i;     //         its neighbour
+  double* ca_q;      // [n_pad] closest approach since the last clear: min of q over the body's
+  int32_t* ca_i;     //         evaluations, and the neighbour then
+  double* q_out;     // HM_OUT: q and neighbour per row of a_out / j_out
+  int32_t* nn_out;
+  int32_t nn;
 };
 
 template <typename T, typename S>
@@ -96,6 +115,10 @@ hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool g
                                hipStream_t s);
 template <typename T, typename S>
 hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s);
+// Collisions on: XP, VP (XL) <- the current X, V with the radii, in any precision (what
+// launch_hermite_split does for mixed runs without them).
+template <typename T, typename S>
+hipError_t launch_hermite_stage(const HArgs<T, S>& a, hipStream_t s);
 // Block-step chain (hermite.hip enqueues them in this order, all on one stream):
 // next-time minima, control, predict-all + mark, compact, narrow evaluate, wide (gathered)
 // evaluate, reduce + correct + new level. mode of the last: HM_STEP or HM_OUT.

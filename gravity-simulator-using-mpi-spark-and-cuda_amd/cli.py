@@ -49,6 +49,16 @@ def build_parser() -> argparse.ArgumentParser:
                    default=d.block_steps,
                    help="hermite: individual block time steps dt 2^-k per body (needs --eta > 0; "
                         "--steps then counts macro steps of --dt)")
+    p.add_argument("--collisions", choices=["off", "detect", "merge"], default=d.collisions,
+                   help="hermite: off | detect: every body's nearest neighbour by "
+                        "q = r^2 - (R_i + R_j)^2 from the force kernel, closest approaches and "
+                        "overlaps (q < softening^2) recorded and reported | merge: overlapping "
+                        "bodies become one (lowest id, summed mass, centre of mass, "
+                        "R = (sum R^3)^(1/3)) at the step that saw the overlap (shared step) or "
+                        "at the next whole multiple of dt (block steps)")
+    p.add_argument("--body-density", dest="body_density", type=float, default=d.body_density,
+                   help="hermite collisions: body radii R = (3 m / 4 pi rho)^(1/3) from this "
+                        "density [kg/m^3] (massless bodies: 0); without it every radius is 0")
     p.add_argument("--max-level", dest="max_level", type=int, default=d.max_level,
                    help="hermite block steps: the deepest level k (0..40)")
     p.add_argument("--kernel", choices=["auto", "lds", "smem", "mfma"], default=d.kernel,
@@ -127,6 +137,7 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
                      seed=a.seed, G=a.G, cutoff=a.cutoff, softening=a.softening,
                      cutoff_mode=a.cutoff_mode, integrator=a.integrator, eta=a.eta,
                      t_end=a.t_end, block_steps=a.block_steps, max_level=a.max_level,
+                     collisions=a.collisions, body_density=a.body_density,
                      kernel=a.kernel,
                      mode=a.mode, ipl=a.ipl, chunk=a.chunk, graph=a.graph, graph_comm=a.graph_comm,
                      strategy=a.strategy, step_timeout_s=a.step_timeout_s, overlap=a.overlap,

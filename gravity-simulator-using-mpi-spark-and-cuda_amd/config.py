@@ -18,6 +18,7 @@ DEVICES = ("auto", "cpu", "gpu")
 KERNELS = ("auto", "lds", "smem", "mfma")
 MODES = ("auto", "fused", "split", "sym")
 INTEGRATORS = ("kd", "leapfrog", "hermite")
+COLLISIONS = ("off", "detect", "merge")
 COMMS = ("auto", "rccl", "gloo", "none")
 LOG_FORMATS = ("mpi", "spark", "cuda", "none")
 
@@ -43,6 +44,11 @@ class SimConfig:
     block_steps: bool = False     # hermite: individual block time steps dt 2^-k per body (needs
                                   # eta > 0); `steps` then counts macro steps of dt
     max_level: int = 24           # hermite block steps: deepest level k (0..40)
+    collisions: str = "off"       # hermite: off | detect (nearest neighbours, closest approaches
+                                  # and overlaps recorded and reported) | merge (overlapping
+                                  # bodies become one at the next synchronised state)
+    body_density: Optional[float] = None  # hermite collisions: radii R = (3 m / 4 pi rho)^(1/3)
+                                  # [kg/m^3] for bodies without a given radius (massless: 0)
     kernel: str = "auto"          # GPU j-source variant: lds | smem
     mode: str = "auto"            # GPU schedule: fused | split | sym (Newton-3, fp32)
     ipl: int = 0                  # i-bodies per lane (0 = auto)
@@ -118,6 +124,13 @@ class SimConfig:
                              "belongs to integrator hermite")
         if self.integrator != "hermite" and self.block_steps:
             raise ValueError("block_steps belongs to integrator hermite")
+        if self.collisions not in COLLISIONS:
+            raise ValueError(f"collisions must be one of {COLLISIONS}")
+        if self.integrator != "hermite" and (self.collisions != "off" or
+                                             self.body_density is not None):
+            raise ValueError("collisions and body_density belong to integrator hermite")
+        if self.body_density is not None and not self.body_density > 0:
+            raise ValueError("body_density must be > 0")
         if self.block_steps:
             if not self.eta > 0:
                 raise ValueError("block steps need eta > 0")

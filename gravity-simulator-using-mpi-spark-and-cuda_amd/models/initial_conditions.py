@@ -78,13 +78,24 @@ class BodySet:
     pos: np.ndarray   # (n, 3) m
     vel: np.ndarray   # (n, 3) m/s
     mass: np.ndarray  # (n,) kg
+    radius: "np.ndarray | None" = None  # (n,) m, hermite collisions (None: all zero)
 
     @property
     def n(self) -> int:
         return int(self.mass.shape[0])
 
     def copy(self) -> "BodySet":
-        return BodySet(self.pos.copy(), self.vel.copy(), self.mass.copy())
+        return BodySet(self.pos.copy(), self.vel.copy(), self.mass.copy(),
+                       None if self.radius is None else self.radius.copy())
+
+    def radii(self, density: "float | None" = None) -> np.ndarray:
+        """The given radii, else R = (3 m / 4 pi density)^(1/3) (0 for massless bodies), else
+        zeros."""
+        if self.radius is not None:
+            return np.asarray(self.radius, dtype=np.float64)
+        if density is None:
+            return np.zeros(self.n)
+        return np.cbrt(3.0 * np.asarray(self.mass, dtype=np.float64) / (4.0 * np.pi * density))
 
 
 def uniform_bodies(seed: int, idx: np.ndarray):

@@ -53,6 +53,7 @@ class GsHermiteInfo(ctypes.Structure):
         ("steps", c_int64), ("finished", c_int32), ("ipl", c_int32),
         ("block_steps", c_int64), ("body_steps", c_int64), ("level_clamped", c_int64),
         ("level_max", c_int32), ("narrow_max", c_int32),
+        ("overlaps", c_int64),
     ]
 
 
@@ -141,6 +142,10 @@ def cpu_lib():
                  [P, P, c_int64, c_int64, c_int64, c_int32, T, T, P, P])
             _sig(lib, f"gs_cpu_accjerk_idx_{t}", c_int32,
                  [P, P, c_int64, POINTER(c_int32), c_int64, c_int32, T, T, P, P])
+            _sig(lib, f"gs_cpu_nn_{t}", c_int32,
+                 [P, P, c_int64, c_int64, c_int64, T, T, P, POINTER(c_int32)])
+            _sig(lib, f"gs_cpu_nn_idx_{t}", c_int32,
+                 [P, P, c_int64, POINTER(c_int32), c_int64, T, T, P, POINTER(c_int32)])
             _sig(lib, f"gs_cpu_hermite_step_{t}", c_int32,
                  [P, P, P, P, P, c_int64, c_int32, c_double, T, T, c_double, _PD])
             _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, c_int64, c_double])
@@ -149,6 +154,10 @@ def cpu_lib():
              [_PD, _PD, c_int64, c_int64, c_int64, c_int32, D, D, _PD, _PD])
         _sig(lib, "gs_cpu_accjerk_idx_mixed", c_int32,
              [_PD, _PD, c_int64, POINTER(c_int32), c_int64, c_int32, D, D, _PD, _PD])
+        _sig(lib, "gs_cpu_nn_mixed", c_int32,
+             [_PD, _PD, c_int64, c_int64, c_int64, D, D, _PD, POINTER(c_int32)])
+        _sig(lib, "gs_cpu_nn_idx_mixed", c_int32,
+             [_PD, _PD, c_int64, POINTER(c_int32), c_int64, D, D, _PD, POINTER(c_int32)])
         _sig(lib, "gs_cpu_hermite_step_mixed", c_int32,
              [_PD, _PD, _PD, _PD, _PD, c_int64, c_int32, D, D, D, D, _PD])
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -237,6 +246,15 @@ def hip_lib():
                                                         _PD, _PD])
         _sig(lib, "gs_hermite_time_active", c_int32, [S, POINTER(c_int32), c_int32, c_int32,
                                                       c_int32, _PD, _PD, _PD])
+        PI = POINTER(c_int32)
+        _sig(lib, "gs_hermite_set_collisions", c_int32, [S, c_int32])
+        _sig(lib, "gs_hermite_set_radii", c_int32, [S, _PD])
+        _sig(lib, "gs_hermite_neighbours", c_int32, [S, _PD, PI])
+        _sig(lib, "gs_hermite_closest", c_int32, [S, _PD, PI, c_int32])
+        _sig(lib, "gs_hermite_clear_overlap", c_int32, [S])
+        _sig(lib, "gs_hermite_derivs_nn", c_int32, [S, _PD, _PD, _PD, PI])
+        _sig(lib, "gs_hermite_derivs_active_nn", c_int32, [S, PI, c_int32, c_int32, _PD, _PD,
+                                                           _PD, PI])
         _sig(lib, "gs_group_step", c_int32, [POINTER(S), c_int32, c_int32])
         _sig(lib, "gs_rccl_unique_id", c_int32, [c_void_p])
         _sig(lib, "gs_stepper_comm_init", c_int32, [S, c_void_p, c_int32, c_int32])

@@ -148,6 +148,115 @@ def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: 
     return out
 
 
+# ---- nearest neighbours, overlaps and mergers ------------------------------------------------
+def nearest_neighbours(pos, radius, cutoff: float = 1e-10, softening: float = 0.0, rows=None,
+                       block: int = 256, second: bool = False):
+    """Nearest neighbour of every body (or of the bodies `rows`) by the pair measure
+
+        q_ij = r^2_ij - (R_i + R_j)^2,    r^2 = |x_j - x_i|^2 + softening^2,
+
+    in fp64: (q (m,), nn (m,) int32), the j of the smallest q, the lowest j on an exact tie,
+    (+inf, -1) where there is none. Every body takes part, massless ones too; a pair the pair
+    law zeroes (r^2 < cutoff^2: the self term, coincident bodies) does not. Body i overlaps its
+    neighbour when q_i < softening^2, that is |d|^2 < (R_i + R_j)^2. radius None: zeros (the
+    nearest body by distance). second: also the second smallest q (m,) (+inf when none)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    n = pos.shape[0]
+    R = np.zeros(n) if radius is None else np.asarray(radius, dtype=np.float64)
+    idx = np.arange(n) if rows is None else np.asarray(rows, dtype=np.int64)
+    q, nn = np.full(len(idx), np.inf), np.full(len(idx), -1, dtype=np.int32)
+    q2 = np.full(len(idx), np.inf)
+    cut2, eps2 = cutoff * cutoff, softening * softening
+    for b0 in range(0, len(idx), block):
+        r = idx[b0:b0 + block]
+        d = pos[None, :, :] - pos[r, None, :]
+        r2 = (d * d).sum(-1) + eps2
+        sr = R[None, :] + R[r, None]
+        qq = np.where(r2 >= cut2, r2 - sr * sr, np.inf)
+        qq[np.arange(len(r)), r] = np.inf  # (j != i: with softening the law keeps the self pair)
+        k = qq.argmin(1)  # (the first of equal minima: the lowest j)
+        best = qq[np.arange(len(r)), k]
+        q[b0:b0 + block] = best
+        nn[b0:b0 + block] = np.where(np.isfinite(best), k, -1)
+        if second and n > 1:
+            qq[np.arange(len(r)), k] = np.inf
+            q2[b0:b0 + block] = qq.min(1)
+    return (q, nn, q2) if second else (q, nn)
+
+
+def overlap_components(ca_q, ca_nn, softening: float = 0.0, eps2=None):
+    """Connected components of the pairs (i, ca_nn_i) with ca_q_i < softening^2: a label per
+    body, the lowest index of its component (its own where it overlaps nobody). eps2: the
+    threshold itself (an engine's softening^2 as its pair type rounds it)."""
+    ca_q, ca_nn = np.asarray(ca_q, dtype=np.float64), np.asarray(ca_nn, dtype=np.int64)
+    n = len(ca_q)
+    root = np.arange(n)
+
+    def find(i):
+        while root[i] != i:
+            root[i] = root[root[i]]
+            i = root[i]
+        return i
+
+    eps2 = softening * softening if eps2 is None else float(eps2)
+    for i in np.nonzero((ca_q < eps2) & (ca_nn >= 0))[0]:
+        a, b = find(int(i)), find(int(ca_nn[i]))
+        if a != b:
+            root[max(a, b)] = min(a, b)
+    return np.array([find(i) for i in range(n)], dtype=np.int64)
+
+
+def merge_overlaps(pos, vel, mass, radius, ids, ca_q, ca_nn, softening: float = 0.0, eps2=None):
+    """Perfect mergers at a synchronised state: every component of overlap_components() becomes
+    one body at the place of its lowest index, with that body's id, mass sum m, the position and
+    velocity of the centre of mass (the plain mean where the component is massless) and
+    R = (sum R^3)^(1/3); the absorbed bodies are removed and the order of the rest stays. Mass
+    and linear momentum are conserved to rounding. Returns (pos, vel, mass, radius, ids,
+    mergers), mergers the number of bodies absorbed."""
+    pos, vel = np.asarray(pos, dtype=np.float64), np.asarray(vel, dtype=np.float64)
+    mass, radius = np.asarray(mass, dtype=np.float64), np.asarray(radius, dtype=np.float64)
+    ids = np.asarray(ids, dtype=np.int64)
+    label = overlap_components(ca_q, ca_nn, softening, eps2)
+    keep = label == np.arange(len(label))
+    p, v, m, R = pos.copy(), vel.copy(), mass.copy(), radius.copy()
+    for root in np.nonzero(keep & (np.bincount(label, minlength=len(label)) > 1))[0]:
+        mem = np.nonzero(label == root)[0]
+        mt = mass[mem].sum()
+        w = mass[mem] / mt if mt > 0 else np.full(len(mem), 1.0 / len(mem))
+        p[root] = (w[:, None] * pos[mem]).sum(0)
+        v[root] = (w[:, None] * vel[mem]).sum(0)
+        m[root] = mt
+        R[root] = np.cbrt((radius[mem] ** 3).sum())
+    return p[keep], v[keep], m[keep], R[keep], ids[keep], int((~keep).sum())
+
+
+class _Closest:
+    """The closest-approach record of the engines: min of q per body and the neighbour then,
+    the latest (q, nn), and the number of (body, evaluation) overlaps seen."""
+
+    def __init__(self, n, radius, cutoff, softening):
+        self.R = np.zeros(n) if radius is None else np.asarray(radius, dtype=np.float64)
+        self.cutoff, self.softening = cutoff, softening
+        self.q, self.nn = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        self.ca_q, self.ca_nn = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        self.overlaps = 0
+
+    def see(self, xp, rows=None):
+        q, nn = nearest_neighbours(xp, self.R, self.cutoff, self.softening, rows)
+        r = slice(None) if rows is None else rows
+        self.q[r], self.nn[r] = q, nn
+        less = q < self.ca_q[r]
+        self.ca_q[r] = np.where(less, q, self.ca_q[r])
+        self.ca_nn[r] = np.where(less, nn, self.ca_nn[r])
+        hit = int((q < self.softening * self.softening).sum())
+        self.overlaps += hit
+        return hit
+
+    def export(self, out):
+        out.update(q=self.q.copy(), nn=self.nn.copy(), ca_q=self.ca_q.copy(),
+                   ca_nn=self.ca_nn.copy(), overlaps=self.overlaps)
+
+
 def hermite_dt(a0, j0, a1, j1, h, eta):
     """Aarseth's criterion after a Hermite step of size h from (a0, j0) to (a1, j1):
     min over the bodies of sqrt(eta (|a1||a2'| + |j1|^2) / (|j1||a3| + |a2'|^2)) with the 2nd
@@ -175,17 +284,31 @@ def hermite_first_dt(a, j, eta):
 
 
 def simulate_hermite(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=0.0, eta=0.0,
-                     t_end=None, record_every=0):
+                     t_end=None, record_every=0, radius=None, collisions="off", record=None):
     """4th-order Hermite predictor-corrector (Makino & Aarseth 1992), one evaluation per step at
     the predicted state. eta > 0: one shared step h = min(dt, min_i dt_i) chosen each step
     (hermite_dt; the first from hermite_first_dt); t_end: the step is cut to reach it exactly and
-    the run stops there (`steps` caps the count). Returns (pos, vel, traj, t, list of steps)."""
+    the run stops there (`steps` caps the count). Returns (pos, vel, traj, t, list of steps).
+
+    collisions "detect" | "merge" (radius: per body, None zeros): every evaluation (the one the
+    run starts with, then each step's at the predicted state) also gives each body's nearest
+    neighbour (nearest_neighbours); `record` (a dict) receives the latest q and nn, the
+    closest-approach record ca_q, ca_nn and the overlap count. "merge": the run takes no further
+    step once an evaluation has seen an overlap (merging itself is merge_overlaps, the
+    caller's)."""
+    if collisions not in ("off", "detect", "merge"):
+        raise ValueError("collisions must be off, detect or merge")
     x = np.array(pos, dtype=np.float64, copy=True)
     v = np.array(vel, dtype=np.float64, copy=True)
     a, j = acc_jerk(x, v, mass, G, cutoff, softening)
+    near = None if collisions == "off" else _Closest(len(x), radius, cutoff, softening)
+    if near is not None:
+        near.see(x)
     t, taken, traj = 0.0, [], []
     nxt = hermite_first_dt(a, j, eta) if eta > 0 else dt
     while len(taken) < steps and (t_end is None or t < t_end):
+        if collisions == "merge" and near.overlaps:
+            break
         h = min(dt, nxt)
         cut = t_end is not None and h >= t_end - t
         if cut:
@@ -193,6 +316,8 @@ def simulate_hermite(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=
         xp = x + (v * h + (a * (h * h / 2) + j * (h * h * h / 6)))
         vp = v + (a * h + j * (h * h / 2))
         a1, j1 = acc_jerk(xp, vp, mass, G, cutoff, softening)
+        if near is not None:
+            near.see(xp)
         v1 = v + ((a + a1) * (h / 2) + (j - j1) * (h * h / 12))
         x = x + ((v + v1) * (h / 2) + (a - a1) * (h * h / 12))
         if eta > 0:
@@ -202,6 +327,8 @@ def simulate_hermite(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=
         taken.append(h)
         if record_every and len(taken) % record_every == 0:
             traj.append(x.copy())
+    if near is not None and record is not None:
+        near.export(record)
     return x, v, traj, t, taken
 
 
@@ -386,7 +513,8 @@ def level_lean(dt_want, valid, dt):
 
 def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI, cutoff=1e-10,
                            softening=0.0, check=None, sources=None, levels=None,
-                           body_times=None, stats=None):
+                           body_times=None, stats=None, radius=None, collisions="off",
+                           record=None):
     """4th-order Hermite with individual block time steps (Makino 1991): body i steps by
     dt 2^-k_i, time is an integer count of ticks of dt 2^-max_level, only the bodies that are due
     are evaluated (against every body predicted to that time) and corrected. t_end must be a
@@ -398,7 +526,16 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
     then predicted, so a block step costs n_active x len(sources). levels, body_times (ticks):
     the block state to start from (default: block_first_levels, all at 0); a body's time must be
     a multiple of its step. stats: a dict that receives "active" (the index array of every block
-    step), "lean" (level_lean over every level decision, the first included) and "level_max"."""
+    step), "lean" (level_lean over every level decision, the first included) and "level_max".
+
+    collisions "detect" | "merge" (radius per body; not with sources): as simulate_hermite, the
+    active bodies of each block step against all bodies predicted to its time; the run never
+    stops inside a macro step, `record` carries what happened (merging at the boundary is the
+    caller's, merge_overlaps)."""
+    if collisions not in ("off", "detect", "merge"):
+        raise ValueError("collisions must be off, detect or merge")
+    if collisions != "off" and sources is not None:
+        raise ValueError("collisions need every body's predicted state (no sources)")
     if not eta > 0:
         raise ValueError("block steps need eta > 0")
     L = int(max_level)
@@ -413,6 +550,9 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
     mass = np.asarray(mass, dtype=np.float64)
     src = None if sources is None else np.unique(_source_columns(mass, sources))
     a, j = acc_jerk(x, v, mass, G, cutoff, softening, sources=src)
+    near = None if collisions == "off" else _Closest(n, radius, cutoff, softening)
+    if near is not None:
+        near.see(x)
     tb = (np.zeros(n, dtype=np.int64) if body_times is None else
           np.array(body_times, dtype=np.int64))
     lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
@@ -444,6 +584,8 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
         at = np.searchsorted(need, act)  # (the due bodies' rows of the predicted arrays)
         a1, j1 = acc_jerk_rows(xp, vp, mass[need], at, G, cutoff, softening,
                                sources=None if src is None else np.searchsorted(need, src))
+        if near is not None:
+            near.see(xp, act)
         ha = hc[at]
         a0, j0, v0 = a[act], j[act], v[act]
         v1 = v0 + ((a0 + a1) * (ha / 2) + (j0 - j1) * (ha * ha / 12))
@@ -462,4 +604,6 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
             check(tb, lev)
     if stats is not None:
         stats.update(active=active, lean=lean, level_max=level_max)
+    if near is not None and record is not None:
+        near.export(record)
     return x, v, lev.copy(), log, clamped

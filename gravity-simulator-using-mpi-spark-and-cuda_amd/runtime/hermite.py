@@ -53,8 +53,18 @@ class HermiteStatus:
     body_steps: int = 0      # sum of their active bodies
     level_max: int = 0       # deepest level any body has had
     level_clamped: int = 0   # times a body wanted a step below dt 2^-max_level
+    overlaps: int = 0        # collisions: bodies the evaluations have seen overlapping their
+                             # nearest neighbour
 
 PATH_IDS = {None: 0, "auto": 0, "narrow": 1, "wide": 2}
+# native collision modes: record only, or record and stop the shared step at the first overlap
+# (what a merge needs: the bodies of a shared-step run all stand at that step's time)
+COLLISION_IDS = {"off": 0, "detect": 1, "merge": 2}
+_PI32 = ctypes.POINTER(ctypes.c_int32)
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(_PI32)
 
 
 def _require_one_rank(nranks: int) -> None:
@@ -90,6 +100,58 @@ class HermiteHipEngine:
         if self.block:
             _native.check(self.lib, self.lib.gs_hermite_set_block(self._h, 1, int(cfg.max_level)),
                           "set_block")
+        self.collisions = cfg.collisions != "off"
+        if self.collisions:
+            _native.check(self.lib, self.lib.gs_hermite_set_collisions(
+                self._h, COLLISION_IDS[cfg.collisions]), "set_collisions")
+            # (mixed runs 2 bodies per lane with collisions on: the layout says what runs)
+            _native.check(self.lib, self.lib.gs_hermite_layout(self._h, ctypes.byref(L)), "layout")
+            self.native_layout = L.as_dict()
+        self.radius = np.zeros(cfg.n)
+
+    def _need_collisions(self) -> None:
+        if not self.collisions:
+            raise ValueError("collisions are off (SimConfig.collisions)")
+
+    def neighbours(self) -> tuple[np.ndarray, np.ndarray]:
+        """(q, nn) of every body from its latest evaluation: q = r^2 - (R_i + R_nn)^2 of the
+        nearest neighbour nn ((+inf, -1): none). Waits for the enqueued steps."""
+        self._need_collisions()
+        q, nn = np.zeros(self.cfg.n), np.zeros(self.cfg.n, dtype=np.int32)
+        _native.check(self.lib, self.lib.gs_hermite_neighbours(self._h, _native.dptr(q),
+                                                               _i32ptr(nn)), "neighbours")
+        return q, nn
+
+    def closest(self, clear: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        """The closest-approach record (min q per body, the neighbour then) since the state was
+        set or the record last cleared."""
+        self._need_collisions()
+        q, nn = np.zeros(self.cfg.n), np.zeros(self.cfg.n, dtype=np.int32)
+        _native.check(self.lib, self.lib.gs_hermite_closest(self._h, _native.dptr(q), _i32ptr(nn),
+                                                            int(bool(clear))), "closest")
+        return q, nn
+
+    def clear_overlap(self) -> None:
+        _native.check(self.lib, self.lib.gs_hermite_clear_overlap(self._h), "clear_overlap")
+
+    def derivs_nn(self, active=None, path: Optional[str] = None):
+        """derivs() with (q, nn) of each row as well: (a4, j4, q, nn). It touches neither the
+        records nor the overlap count."""
+        self._need_collisions()
+        if active is not None:
+            idx = np.ascontiguousarray(active, dtype=np.int32)
+            m = len(idx)
+            a4, j4, q, nn = np.zeros((m, 4)), np.zeros((m, 4)), np.zeros(m), np.zeros(m, np.int32)
+            _native.check(self.lib, self.lib.gs_hermite_derivs_active_nn(
+                self._h, _i32ptr(idx), m, PATH_IDS[path], _native.dptr(a4), _native.dptr(j4),
+                _native.dptr(q), _i32ptr(nn)), "derivs_active_nn")
+            return a4, j4, q, nn
+        n = self.cfg.n
+        a4, j4, q, nn = np.zeros((n, 4)), np.zeros((n, 4)), np.zeros(n), np.zeros(n, np.int32)
+        _native.check(self.lib, self.lib.gs_hermite_derivs_nn(
+            self._h, _native.dptr(a4), _native.dptr(j4), _native.dptr(q), _i32ptr(nn)),
+            "derivs_nn")
+        return a4, j4, q, nn
 
     def set_block_tuning(self, narrow_max: int = -1) -> None:
         """Active sets up to narrow_max bodies take the j-parallel evaluate kernel (0: never;
@@ -116,7 +178,7 @@ class HermiteHipEngine:
         return tb
 
     def init_ics(self, family: str, seed: int) -> None:
-        if family in DEVICE_IC_IDS:
+        if family in DEVICE_IC_IDS and not self.collisions:
             _native.check(self.lib, self.lib.gs_hermite_init_ics(self._h, DEVICE_IC_IDS[family],
                                                                  seed), "init_ics")
         else:
@@ -134,6 +196,10 @@ class HermiteHipEngine:
         have = acc is not None and jerk is not None
         a = np.ascontiguousarray(acc, dtype=np.float64) if have else None
         j = np.ascontiguousarray(jerk, dtype=np.float64) if have else None
+        if self.collisions:
+            self.radius = np.ascontiguousarray(b.radii(self.cfg.body_density), dtype=np.float64)
+            _native.check(self.lib, self.lib.gs_hermite_set_radii(
+                self._h, _native.dptr(self.radius)), "set_radii")
         _native.check(self.lib, self.lib.gs_hermite_set_state(
             self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
             _native.dptr(a) if have else None, _native.dptr(j) if have else None, float(t),
@@ -171,7 +237,7 @@ class HermiteHipEngine:
         _native.check(self.lib, self.lib.gs_hermite_status(self._h, ctypes.byref(s)), "status")
         return HermiteStatus(s.time, s.dt_last, s.dt_next, s.dt_min, int(s.steps),
                              bool(s.finished), int(s.block_steps), int(s.body_steps),
-                             int(s.level_max), int(s.level_clamped))
+                             int(s.level_max), int(s.level_clamped), int(s.overlaps))
 
     def _get(self, want_deriv: bool):
         n = self.cfg.n
@@ -182,7 +248,7 @@ class HermiteHipEngine:
             self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
             _native.dptr(acc) if want_deriv else None, _native.dptr(jerk) if want_deriv else None),
             "get_state")
-        return BodySet(pos, vel, mass), acc, jerk
+        return BodySet(pos, vel, mass, self.radius.copy() if self.collisions else None), acc, jerk
 
     def state(self) -> BodySet:
         return self._get(False)[0]
@@ -284,11 +350,77 @@ class HermiteCpuEngine:
         self._eps2 = T(cfg.softening ** 2)
         self.t, self.dt_last, self.dt_min, self.k = 0.0, 0.0, math.inf, 0
         self._next = math.inf  # min_i dt_i of the last step (adaptive)
+        # collisions: the records of the GPU engine (latest and closest (q, nn), overlap count)
+        self.collisions = cfg.collisions != "off"
+        self._nn = getattr(self.lib, f"gs_cpu_nn_{suf}")
+        self._nn_idx = getattr(self.lib, f"gs_cpu_nn_idx_{suf}")
+        self.radius = np.zeros(n)
+        self._R = np.zeros(n, T)
+        self._clear_records()
         if cfg.threads:
             self.lib.gs_cpu_set_threads(int(cfg.threads))
 
     def init_ics(self, family: str, seed: int) -> None:
         self.load(make(family, self.cfg.n, seed, self.cfg.G))
+
+    def _need_collisions(self) -> None:
+        if not self.collisions:
+            raise ValueError("collisions are off (SimConfig.collisions)")
+
+    def _clear_records(self) -> None:
+        n = self.cfg.n
+        self.q, self.nn = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        self.ca_q, self.ca_nn = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        self.overlaps = 0
+
+    def _nearest(self, X, idx=None) -> tuple[np.ndarray, np.ndarray]:
+        """(q, nn) of all bodies (or of idx) at the rows X, in the run's pair arithmetic."""
+        n, T = self.cfg.n, self.np_dtype
+        m = n if idx is None else len(idx)
+        q, nn = np.zeros(m, T), np.zeros(m, dtype=np.int32)
+        if idx is None:
+            rc = self._nn(self._ptr(X), self._ptr(self._R), n, 0, n, self._cut2, self._eps2,
+                          self._ptr(q), _i32ptr(nn))
+        else:
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            rc = self._nn_idx(self._ptr(X), self._ptr(self._R), n, _i32ptr(idx), m, self._cut2,
+                              self._eps2, self._ptr(q), _i32ptr(nn))
+        _native.check(self.lib, rc, "cpu nn")
+        return q, nn
+
+    def _see(self, X, idx=None) -> None:
+        """Record an evaluation at the rows X (of every body, or of the bodies idx)."""
+        q, nn = self._nearest(X, idx)
+        r = slice(None) if idx is None else idx
+        # the overlap test in the pair type (fp32 runs: q and eps2 in fp32; mixed: q is an fp32
+        # value and eps2 rounds to fp32 as on the GPU)
+        eps2 = np.float32(self._eps2) if self.cfg.dtype != "fp64" else self._eps2
+        self.overlaps += int((q < eps2).sum())
+        q = q.astype(np.float64)
+        self.q[r], self.nn[r] = q, nn
+        less = q < self.ca_q[r]
+        self.ca_q[r] = np.where(less, q, self.ca_q[r])
+        self.ca_nn[r] = np.where(less, nn, self.ca_nn[r])
+
+    def neighbours(self) -> tuple[np.ndarray, np.ndarray]:
+        self._need_collisions()
+        return self.q.copy(), self.nn.copy()
+
+    def closest(self, clear: bool = False) -> tuple[np.ndarray, np.ndarray]:
+        self._need_collisions()
+        out = self.ca_q.copy(), self.ca_nn.copy()
+        if clear:
+            self.ca_q[:], self.ca_nn[:] = np.inf, -1
+        return out
+
+    def clear_overlap(self) -> None:
+        self.overlaps = 0
+
+    def derivs_nn(self, active=None, path: Optional[str] = None):
+        self._need_collisions()
+        a4, j4 = self.derivs(active)
+        q, nn = self._nearest(self.X, active)
+        return a4, j4, q.astype(np.float64), nn
 
     def _derivs(self) -> tuple[np.ndarray, np.ndarray]:
         n, T = self.cfg.n, self.np_dtype
@@ -350,6 +482,8 @@ class HermiteCpuEngine:
         XP[:, :3] = x + (v * h + (a * ((h * h) / T(2)) + j * ((h * h * h) / T(6))))
         VP[:, :3] = v + (a * h + j * ((h * h) / T(2)))
         a4, j4 = self._derivs_idx(XP, VP, act)
+        if self.collisions:
+            self._see(XP, act)
         a1, j1 = a4[:, :3], j4[:, :3]
         ha = h[act]
         a0, j0, v0 = a[act], j[act], v[act]
@@ -378,6 +512,10 @@ class HermiteCpuEngine:
         self.mass = np.array(b.mass, dtype=np.float64)
         self.A[:] = 0
         self.J[:] = 0
+        self._clear_records()
+        if self.collisions:
+            self.radius = np.array(b.radii(self.cfg.body_density), dtype=np.float64)
+            self._R = self.radius.astype(self.np_dtype)
         if acc is not None and jerk is not None:
             self.A[:, :3] = acc
             self.J[:, :3] = jerk
@@ -386,6 +524,8 @@ class HermiteCpuEngine:
             a4, j4 = self._derivs()
             self.A[:, :3] = a4[:, :3]
             self.J[:, :3] = j4[:, :3]
+            if self.collisions:
+                self._see(self.X)
             self._next = math.inf
             if self.cfg.eta > 0:
                 self._next = float(self._first_dt(self._ptr(self.A), self._ptr(self.J),
@@ -412,6 +552,8 @@ class HermiteCpuEngine:
         for _ in range(int(n)):
             if cfg.t_end is not None and self.t >= cfg.t_end:
                 return
+            if cfg.collisions == "merge" and self.overlaps:
+                return  # (the run stops at the step that first saw an overlap)
             h = min(cfg.dt, self._next) if cfg.eta > 0 else cfg.dt
             cut = cfg.t_end is not None and h >= cfg.t_end - self.t
             if cut:
@@ -421,6 +563,8 @@ class HermiteCpuEngine:
                             self.layout.chunk, h, self._cut2, self._eps2, float(cfg.eta),
                             ctypes.byref(out))
             _native.check(self.lib, rc, "cpu hermite step")
+            if self.collisions:  # (the step leaves its predicted rows at the scratch's head)
+                self._see(self._scratch[: cfg.n])
             self._next = out.value
             self.t = cfg.t_end if cut else self.t + h
             self.dt_last = h
@@ -438,14 +582,15 @@ class HermiteCpuEngine:
                                  float(np.ldexp(cfg.dt, -self.level_max)), self.k,
                                  cfg.t_end is not None and self.t >= cfg.t_end,
                                  len(self.block_log), self.body_steps, self.level_max,
-                                 self.level_clamped)
+                                 self.level_clamped, self.overlaps)
         nxt = min(cfg.dt, self._next) if cfg.eta > 0 else cfg.dt
         return HermiteStatus(self.t, self.dt_last, nxt, self.dt_min, self.k,
-                             cfg.t_end is not None and self.t >= cfg.t_end)
+                             cfg.t_end is not None and self.t >= cfg.t_end,
+                             overlaps=self.overlaps)
 
     def state(self) -> BodySet:
         return BodySet(self.X[:, :3].astype(np.float64), self.V[:, :3].astype(np.float64),
-                       self.mass.copy())
+                       self.mass.copy(), self.radius.copy() if self.collisions else None)
 
     def carried(self) -> tuple[np.ndarray, np.ndarray]:
         return self.A[:, :3].astype(np.float64), self.J[:, :3].astype(np.float64)

@@ -25,6 +25,11 @@ design:
   With block_steps every body has its own step dt 2^-k and `steps` counts macro steps of dt, at
   which all bodies stand at the same time: all periodic work lands on synchronised states, and a
   checkpoint also keeps the levels.
+  collisions "detect" reports the nearest-neighbour records of the engine; "merge" also replaces
+  overlapping bodies by one (ops/oracle.py merge_overlaps) at synchronised states: the step at
+  which a shared-step run stopped itself, or each macro boundary of a block-step run. The engine
+  is rebuilt on the survivors at the same time (a, j evaluated afresh, levels re-initialised);
+  `ids` keeps their original indices, and checkpoints carry radius and id.
 """
 from __future__ import annotations
 
@@ -104,6 +109,7 @@ class Simulation:
             raise RuntimeError("device=gpu requested but no HIP device / native library")
         d = self.dist
         stage = guard.stage if guard else (lambda *_a, **_k: None)
+        ecfg = self._engine_cfg()
         if use_gpu:
             import torch
 
@@ -111,7 +117,8 @@ class Simulation:
 
             dev = d.local_rank % max(1, torch.cuda.device_count())
             stage("engine", INIT_TIMEOUT_S)
-            self.engine = (HermiteHipEngine(cfg, device=dev) if self.hermite else
+            self._hermite_engine = lambda c: HermiteHipEngine(c, device=dev)
+            self.engine = (HermiteHipEngine(ecfg, device=dev) if self.hermite else
                            HipEngine(cfg, d.rank, d.world, device=dev, dist=d))
             if guard:
                 guard.on_abort(self.engine.abort)
@@ -134,14 +141,15 @@ class Simulation:
             # instead of killing a slow but healthy start; gloo's own timeouts
             # bound its collectives.
             stage("cpu_setup", None)
-            self.engine = (HermiteCpuEngine(cfg) if self.hermite else
+            self._hermite_engine = HermiteCpuEngine
+            self.engine = (HermiteCpuEngine(ecfg) if self.hermite else
                            CpuEngine(cfg, d.rank, d.world, dist=d))
         self.step0 = 0
         self.trajectory: list[np.ndarray] = []
         self.staggered = False  # velocities held as v_{k-1/2} (leapfrog)
         if cfg.resume:
-            c = ckpt.load(cfg.resume)
-            if c.bodies.n != cfg.n:
+            c = self._resume
+            if c.bodies.n != ecfg.n:
                 raise ValueError(f"checkpoint has n={c.bodies.n}, config n={cfg.n}")
             if self.hermite and c.meta.get("integrator") == "hermite" and \
                     "acc" in c.extra and "jerk" in c.extra:
@@ -180,6 +188,67 @@ class Simulation:
             self._half_kick(+1.0)
             self.staggered = False
 
+    def _engine_cfg(self) -> SimConfig:
+        """The engine's configuration: cfg, but for the bodies a resumed merge run has left.
+        Reads the checkpoint (self._resume) and the collision bookkeeping it carries."""
+        cfg = self.cfg
+        self.ids = np.arange(cfg.n, dtype=np.int64)  # original index of every body left
+        self.mergers = self.overlaps_seen = 0
+        self.closest_q_min = float("inf")
+        self._resume = ckpt.load(cfg.resume) if cfg.resume else None
+        c = self._resume
+        if c is None or not self.hermite or "collide" not in c.extra:
+            return cfg
+        cols = list(c.meta.get("collide_columns", ["radius", "id"]))
+        c.bodies.radius = c.extra["collide"][:, cols.index("radius")].copy()
+        if cfg.collisions == "off":
+            return cfg
+        ids = c.extra["collide"][:, cols.index("id")].astype(np.int64)
+        if c.bodies.n > cfg.n or (ids >= cfg.n).any():
+            raise ValueError(f"checkpoint has n={c.bodies.n}, config n={cfg.n}")
+        self.ids = ids
+        self.mergers = int(c.meta.get("mergers", cfg.n - c.bodies.n))
+        return cfg.replace(n=c.bodies.n, resume=None)
+
+    def _eps2(self) -> float:
+        """softening^2 as the engine's pair type holds it (the overlap threshold)."""
+        e = self.cfg.softening * self.cfg.softening
+        return float(e) if self.cfg.dtype == "fp64" else float(np.float32(e))
+
+    def _note_collisions(self) -> None:
+        """Fold the engine's records into the run's figures (before the engine goes)."""
+        q = self.engine.closest()[0]
+        if len(q):
+            self.closest_q_min = min(self.closest_q_min, float(q.min()))
+
+    def _merge(self, st) -> int:
+        """Replace every set of overlapping bodies by one body and restart the engine on the
+        survivors at the time reached. Returns the number of bodies absorbed."""
+        from ..ops import oracle
+
+        eng = self.engine
+        b = eng.state()
+        ca_q, ca_nn = eng.closest()
+        self._note_collisions()
+        self.overlaps_seen += st.overlaps
+        pos, vel, mass, rad, ids, k = oracle.merge_overlaps(
+            b.pos, b.vel, b.mass, b.radii(), self.ids, ca_q, ca_nn, eps2=self._eps2())
+        if k == 0:  # (an overlap of the predicted state that the record does not hold)
+            eng.clear_overlap()
+            return 0
+        self._steps_gone += eng.steps_done
+        for key in ("block_steps", "body_steps", "level_clamped"):
+            self._counts_gone[key] += getattr(st, key)
+        # (pair evaluations: each engine's body-steps against the bodies it had)
+        self._counts_gone["pair_evals"] += (st.body_steps - self._body_base) * eng.cfg.n
+        self._body_base = 0
+        self._counts_gone["level_max"] = max(self._counts_gone["level_max"], st.level_max)
+        eng.close()
+        self.ids, self.mergers = ids, self.mergers + k
+        self.engine = self._hermite_engine(eng.cfg.replace(n=len(ids), resume=None))
+        self.engine.load(BodySet(pos, vel, mass, rad), t=st.time)
+        return k
+
     def _self_check(self) -> float:
         """Multi-rank GPU start-up (collective): the gated launch's bitwise self-check
         against the ungated schedule (runtime/selfcheck.py; the CLI's default picks overlap 3
@@ -209,9 +278,11 @@ class Simulation:
     def device(self) -> str:
         return self.engine.kind
 
+    _steps_gone = 0  # steps of the engines a merger has replaced
+
     @property
     def step(self) -> int:
-        return self.step0 + self.engine.steps_done
+        return self.step0 + self._steps_gone + self.engine.steps_done
 
     def _own_accel(self) -> np.ndarray:
         """(n, 3) accelerations with this rank's rows filled (others zero)."""
@@ -282,8 +353,13 @@ class Simulation:
             fin = lambda y: y if np.isfinite(y) else None  # noqa: E731
             meta.update(time=st.time, dt_next=fin(st.dt_next), dt_min=fin(st.dt_min),
                         eta=cfg.eta)
+            if cfg.collisions != "off":
+                col = np.zeros((b.n, 3))
+                col[:, 0], col[:, 1] = b.radii(), self.ids
+                extra["collide"] = col
+                meta.update(collide_columns=["radius", "id"], mergers=self.mergers)
             if cfg.block_steps:  # (a synchronised state: every body time is st.time)
-                lev = np.zeros((cfg.n, 3))
+                lev = np.zeros((b.n, 3))
                 lev[:, 0] = self.engine.levels()
                 extra["level"] = lev
                 meta.update(block_steps=True, max_level=cfg.max_level, level_column=0)
@@ -309,7 +385,14 @@ class Simulation:
         # the host asks whether it has finished once per 32 enqueued steps and then stops
         # enqueueing; `steps` caps the count.
         ends = self.hermite and cfg.t_end is not None
+        merging = self.hermite and cfg.collisions == "merge"
+        self._counts_gone = dict(block_steps=0, body_steps=0, level_clamped=0, level_max=0,
+                                 pair_evals=0)
+        steps_gone0 = self._steps_gone
         st0 = self.engine.status() if self.hermite else None
+        self._body_base = st0.body_steps if self.hermite else 0  # (of the engine now running)
+        if merging and st0.overlaps:  # (bodies that overlap as the run starts: merged at once)
+            self._merge(st0)
         polled = 0
         poll = 1 if cfg.block_steps else 32  # (a macro step waits for its block steps anyway)
         comm.barrier(self.dist)
@@ -320,13 +403,22 @@ class Simulation:
             if log and cfg.progress_every and s % cfg.progress_every == 0 and self.dist.is_root:
                 log.progress(s, steps)
             nxt = min([steps] + [(s // p + 1) * p for p in periods])
-            if ends:
+            if ends or merging:
                 nxt = min(nxt, polled + poll)
             self.engine.step(nxt - s)
             s = nxt
-            if ends and s - polled == poll:
+            # (a merge run reads the status after every chunk, so that no periodic work below
+            # ever sees a loop counter ahead of an engine that has stopped at an overlap)
+            if merging or (ends and s - polled == poll):
                 polled = s
-                finished = self.engine.status().finished
+                st = self.engine.status()
+                finished = ends and st.finished
+                if merging and st.overlaps:
+                    # the engine stopped at the step that saw the overlap (shared step; further
+                    # steps were no-ops) or stands at a macro boundary: merge there
+                    # (st0.steps: what the first engine had taken before this run)
+                    s = polled = self._steps_gone - steps_gone0 + st.steps - st0.steps
+                    self._merge(st)
             if cfg.nan_check_every and s % cfg.nan_check_every == 0:
                 self.check_finite()
             if cfg.record_every and s % cfg.record_every == 0:
@@ -377,14 +469,26 @@ class Simulation:
         herm = {}
         if self.hermite:
             st = self.engine.status()
-            steps = st.steps - st0.steps  # the steps this run took (none past t_end)
+            gone = self._counts_gone  # (of the engines that mergers have replaced)
+            # the steps this run took (none past t_end or past an overlap)
+            steps = self._steps_gone - steps_gone0 + st.steps - st0.steps
             herm = dict(time_reached=st.time, steps_taken=steps,
                         dt_min=st.dt_min if np.isfinite(st.dt_min) else None)
             if cfg.block_steps:
-                body = st.body_steps - st0.body_steps
-                herm.update(block_steps=st.block_steps - st0.block_steps, body_steps=body,
-                            pair_evals=body * cfg.n, level_max=st.level_max,
-                            level_clamped=st.level_clamped - st0.level_clamped)
+                body = gone["body_steps"] + st.body_steps - st0.body_steps
+                herm.update(block_steps=gone["block_steps"] + st.block_steps - st0.block_steps,
+                            body_steps=body,
+                            pair_evals=gone["pair_evals"] +
+                            (st.body_steps - self._body_base) * self.engine.cfg.n,
+                            level_max=max(gone["level_max"], st.level_max),
+                            level_clamped=gone["level_clamped"] + st.level_clamped -
+                            st0.level_clamped)
+            if cfg.collisions != "off":
+                self._note_collisions()
+                herm.update(mergers=self.mergers, bodies_left=len(self.ids),
+                            closest_q_min=self.closest_q_min
+                            if np.isfinite(self.closest_q_min) else None,
+                            overlaps_seen=self.overlaps_seen + st.overlaps)
         return RunMetrics(n=cfg.n, steps=steps, dt=cfg.dt, dtype=cfg.dtype, device=self.device,
                           nranks=self.dist.world, wall_s=wall,
                           kernel=KERNEL_NAMES.get(lay.get("kernel", 0), "cpu"),

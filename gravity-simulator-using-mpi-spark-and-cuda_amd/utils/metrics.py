@@ -40,6 +40,13 @@ class RunMetrics:
     pair_evals: int | None = None
     level_max: int | None = None
     level_clamped: int | None = None
+    # ... with collisions detect | merge: bodies absorbed by mergers, bodies left, the smallest
+    # pair measure q = r^2 - (R_i + R_j)^2 any evaluation has seen (< softening^2: an overlap;
+    # None when no pair was seen) and the overlaps the evaluations counted
+    mergers: int | None = None
+    bodies_left: int | None = None
+    closest_q_min: float | None = None
+    overlaps_seen: int | None = None
 
     @property
     def ms_per_step(self) -> float:
@@ -63,7 +70,8 @@ class RunMetrics:
     def to_json(self) -> str:
         d = asdict(self)
         for k in ("time_reached", "steps_taken", "dt_min", "block_steps", "body_steps",
-                  "pair_evals", "level_max", "level_clamped"):
+                  "pair_evals", "level_max", "level_clamped", "mergers", "bodies_left",
+                  "closest_q_min", "overlaps_seen"):
             if d[k] is None:
                 del d[k]
         d.update(ms_per_step=self.ms_per_step, body_updates_per_s=self.body_updates_per_s,
