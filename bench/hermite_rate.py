@@ -27,6 +27,11 @@ kernel): alternating windows of back-to-back launches between device events, med
 --collisions times the fixed Hermite step with collisions off and on (detect: nearest neighbours,
 closest approaches and the overlap count from the force kernel) at every --sizes and --dtypes, in
 alternating windows (off, on, off, on, ...): each median, the spread of its windows and on / off.
+--ranks P[,P...] runs the shared step on P virtual ranks (HermiteVirtualGroup: the shards of a
+multi-rank run in one process on this device, the gathers as device copies) at every --sizes and
+--dtypes: each shard's evaluate launch alone on the device (events), the whole group step (the
+shards take turns on the one device, so it is about their sum) in windows alternating with the
+one-rank step, and the bytes a rank gathers per step.
 """
 from __future__ import annotations
 
@@ -164,6 +169,48 @@ def collisions(n: int, dtype: str, seed: int, repeat: int, min_s: float) -> dict
                       "ipl": engines[m].native_layout["ipl"],
                       "groups": engines[m].native_layout["split_groups"]}
         out["on_over_off"] = out["detect"]["ms_per_step"] / out["off"]["ms_per_step"]
+        return out
+    finally:
+        for eng in engines.values():
+            eng.close()
+
+
+def ranks(n: int, dtype: str, P: int, seed: int, repeat: int, min_s: float) -> dict:
+    """P virtual ranks beside one rank: per-shard evaluate, group step, gathered bytes."""
+    from gravsim.config import SimConfig
+    from gravsim.runtime.hermite import HermiteHipEngine, HermiteVirtualGroup
+
+    cfg = SimConfig(n=n, dtype=dtype, device="gpu", integrator="hermite")
+    engines = {"one": HermiteHipEngine(cfg), "group": HermiteVirtualGroup(cfg, P)}
+    try:
+        steps = {}
+        for name, eng in engines.items():
+            eng.init_ics("solar+random", seed)
+            eng.sync()
+            _window(eng, 2)
+            steps[name] = max(4, int(min_s / _window(eng, 4) + 1))
+        times = {name: [] for name in engines}
+        for _ in range(repeat):
+            for name, eng in engines.items():
+                times[name].append(_window(eng, steps[name]))
+        grp = engines["group"]
+        ev = grp.time_eval(max(2, steps["one"] // 2))
+        lay = [e.native_layout for e in grp.shards]
+        n_pad, psz = lay[0]["n_pad"], 8 if dtype == "fp64" else 4
+        rows = (3 if dtype == "mixed" else 2) * n_pad * 4 * psz + n_pad // 256 * 8
+        one, group = (statistics.median(times[k]) for k in ("one", "group"))
+        out = {"n": n, "dtype": dtype, "ranks": P, "n_pad": n_pad,
+               "rows": [x["n_local"] for x in lay], "ipl": [x["ipl"] for x in lay],
+               "groups": [x["split_groups"] for x in lay],
+               "workgroups": [x["n_local"] // (256 * x["ipl"]) * x["split_groups"] for x in lay],
+               "shard_eval_ms": [round(x, 4) for x in ev],
+               "one_rank_ms_per_step": 1e3 * one,
+               "one_rank_ms_windows": [round(1e3 * x, 4) for x in times["one"]],
+               "group_ms_per_step": 1e3 * group,
+               "group_ms_windows": [round(1e3 * x, 4) for x in times["group"]],
+               "max_shard_eval_over_one_rank_step": max(ev) / (1e3 * one),
+               "gathered_bytes_per_step": rows,  # (what every rank holds after the gathers)
+               "received_bytes_per_step_rank0": rows - rows * lay[0]["n_local"] // n_pad}
         return out
     finally:
         for eng in engines.values():
@@ -324,6 +371,9 @@ def main() -> int:
                     help="--active-sweep: largest n_act timed on the narrow path")
     ap.add_argument("--collisions", action="store_true",
                     help="the Hermite step with collisions off and on in alternating windows")
+    ap.add_argument("--ranks", default="",
+                    help="P[,P...]: the shared step on P virtual ranks of this device beside one "
+                         "rank (per-shard evaluate, group step, gathered bytes)")
     ap.add_argument("--no-rates", action="store_true", help="skip the hermite / kd step rates")
     a = ap.parse_args()
     import torch
@@ -348,6 +398,10 @@ def main() -> int:
     if a.collisions:
         res["collisions"] = [collisions(int(n), d, a.seed, a.repeat, a.min_window_s)
                              for n in a.sizes.split(",") for d in a.dtypes.split(",")]
+    if a.ranks:
+        res["ranks"] = [ranks(int(n), d, int(P), a.seed, a.repeat, a.min_window_s)
+                        for n in a.sizes.split(",") for d in a.dtypes.split(",")
+                        for P in a.ranks.split(",")]
     if a.active_sweep:
         res["active_sweep"] = [active_sweep(int(n), d, a.seed, a.repeat, a.narrow_cap)
                                for n in a.sizes.split(",") for d in a.dtypes.split(",")]

@@ -206,6 +206,30 @@ extern "C" int gs_sym_rank_rows(int64_t n_pad, int32_t nranks, int32_t rank, int
   return 0;
 }
 
+// Rows [row_begin, row_begin + row_count) of rank `rank` of `nranks` in a Hermite run of n
+// bodies: n_pad = n rounded up to the chunk, cut into units of 1024 rows (256 x the widest lane
+// tile, so a slice is whole i-blocks for every IPL); a rank owns a contiguous range of units by
+// mpi.c's remainder rule (the first `units mod P` ranks hold one more).
+extern "C" int gs_hermite_partition(int64_t n, int32_t chunk, int32_t nranks, int32_t rank,
+                                    int64_t* row_begin, int64_t* row_count) {
+  if (n < 1) { gs_set_error("hermite partition: n must be >= 1"); return -1; }
+  if (chunk <= 0) chunk = gs::auto_chunk(n);
+  if (chunk % 1024) { gs_set_error("hermite partition: chunk must be a multiple of 1024"); return -1; }
+  const int64_t units = gs::round_up(n, chunk) / 1024;
+  if (nranks < 1 || rank < 0 || rank >= nranks) {
+    gs_set_error("hermite partition: bad rank/nranks");
+    return -1;
+  }
+  if (nranks > units) {
+    gs_set_error("hermite partition: more ranks than units of 1024 rows");
+    return -1;
+  }
+  const int64_t base = units / nranks, rem = units % nranks;
+  if (row_begin) *row_begin = 1024 * (rank * base + (rank < rem ? rank : rem));
+  if (row_count) *row_count = 1024 * (base + (rank < rem ? 1 : 0));
+  return 0;
+}
+
 // Row blocks and reduction-tree nodes: B blocks of RB rows; rank `rank` sends nn maximal
 // dyadic nodes (sub-trees of its block range; one per rank for P dividing 64); nodes of lower
 // ranks come first (nb of them); NN nodes in all. (Splitting one rank's range into 8 nodes,

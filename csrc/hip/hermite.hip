@@ -1,4 +1,4 @@
-// Runtime of the 4th-order Hermite integrator on one GPU (gs_hermite_* in gravsim.h).
+// Runtime of the 4th-order Hermite integrator (gs_hermite_* in gravsim.h).
 //
 // Device-resident state x, v, a, j (4 components per body, n_pad rows, ghost rows zero) and a
 // control block (t, h, steps; gs_hermite.h). A step is four launches on one stream: control,
@@ -10,7 +10,16 @@
 // Three precisions: fp32 and fp64 throughout, and mixed (GS_MIXED): the state rows, the reduce
 // and the corrector in fp64, the predicted rows (position as double-single hi + lo) and the
 // partial sums of the pair kernels in fp32.
+// Ranks (shared steps only): rank r owns whole units of 1024 rows (gs_hermite_partition) and runs
+// the slice forms of predict, evaluate and reduce + correct on them; every array but the
+// partials keeps its full length. A step is control -> predict (slice) -> gather of XP, VP (XL)
+// -> evaluate (slice) -> reduce + correct (slice) -> gather of wgmin, all on the engine's one
+// stream; every rank runs the control kernel on the gathered wgmin and so holds the same h, t
+// and steps. The gathers are RCCL collectives (gs_hermite_comm_init) or, for the shards of a
+// virtual group in one process, device copies ordered by events (gs_hermite_group_*).
+#include <chrono>
 #include <cmath>
+#include <initializer_list>
 #include <limits>
 #include <utility>
 #include <vector>
@@ -45,6 +54,19 @@ struct gs_hermite {
   void* R = nullptr;  // radii, state precision
   int32_t *PN = nullptr, *NNI = nullptr, *nn_i = nullptr, *ca_i = nullptr, *nn_out = nullptr;
   double *nn_q = nullptr, *ca_q = nullptr, *q_out = nullptr;
+  // ranks: the rows this one owns, and every rank's (in units of 1024 rows)
+  int64_t row0 = 0, n_loc = 0;
+  std::vector<int64_t> ubeg, ucnt;
+  bool uniform = true;        // equal slices: in-place ncclAllGather
+  bool wgmin_open = false;    // the first step minima wait for a gather (a shard of a group)
+  hipEvent_t ev = nullptr;    // this shard's rows are ready (virtual group)
+  ncclComm_t comm = nullptr;
+  std::atomic<ncclComm_t> comm_live{nullptr};
+  int32_t comm_count = 0, comm_user_rank = -1, comm_cu_device = -1;
+  double step_timeout_s = 0.0;
+  // bounded waits (RCCL runs): an event per chain in a ring; `seen` of `rec` have completed
+  std::vector<hipEvent_t> ring;
+  int64_t rec = 0, seen = 0;
 };
 
 namespace {
@@ -60,6 +82,8 @@ int by_dtype(const gs_hermite* h, F f) {
   return h->esz == 4 ? f(float(), float()) : f(double(), double());
 }
 int nwg(const gs_hermite* h) { return (int)(h->n_pad / gs::kForceBlock); }
+bool multi(const gs_hermite* h) { return h->cfg.nranks > 1; }
+constexpr int64_t kUnit = 1024;  // rows per ownership unit (gs_hermite_partition)
 
 template <typename T, typename S>
 gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
@@ -82,6 +106,7 @@ gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
   a.PN = h->PN; a.NNI = h->NNI;
   a.nn_q = h->nn_q; a.nn_i = h->nn_i; a.ca_q = h->ca_q; a.ca_i = h->ca_i;
   a.q_out = h->q_out; a.nn_out = h->nn_out;
+  a.row0 = h->row0; a.n_loc = h->n_loc;
   return a;
 }
 
@@ -98,16 +123,16 @@ int launch_shape(gs_hermite* h) {
   int ipl = h->cfg.ipl;
   if (ipl == 0) {
     ipl = top;
-    while (ipl > (fp64 ? 1 : 2) && h->n_pad / (gs::kForceBlock * ipl) * h->n_chunks < want)
+    while (ipl > (fp64 ? 1 : 2) && h->n_loc / (gs::kForceBlock * ipl) * h->n_chunks < want)
       ipl >>= 1;
   }
-  if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
+  if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_loc % (gs::kForceBlock * ipl)) {
     gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
     return -1;
   }
   if (ipl > top) ipl = top;
   h->ipl = ipl;
-  const int64_t blocks = h->n_pad / (gs::kForceBlock * ipl);
+  const int64_t blocks = h->n_loc / (gs::kForceBlock * ipl);  // (of the rows this rank owns)
   int64_t groups =
       h->cfg.split_groups > 0 ? h->cfg.split_groups : (2 * want + blocks - 1) / blocks;
   if (groups > h->n_chunks) groups = h->n_chunks;
@@ -176,14 +201,152 @@ int eval_current(gs_hermite* h, int mode, bool phi) {
   return 0;
 }
 
+// ---- ranks -----------------------------------------------------------------------------
+// The arrays a multi-rank run gathers: base address and bytes per ownership unit.
+enum { G_XP, G_VP, G_XL, G_X, G_V, G_A, G_J, G_AOUT, G_JOUT, G_WGMIN };
+
+char* gbuf(gs_hermite* h, int w, size_t* ub) {
+  const size_t rs = (size_t)kUnit * 4 * h->esz, rp = (size_t)kUnit * 4 * h->psz;
+  void* p = nullptr;
+  switch (w) {
+    case G_XP: *ub = rp; p = h->XP; break;
+    case G_VP: *ub = rp; p = h->VP; break;
+    case G_XL: *ub = rp; p = h->XL; break;
+    case G_X: *ub = rs; p = h->X; break;
+    case G_V: *ub = rs; p = h->V; break;
+    case G_A: *ub = rs; p = h->A; break;
+    case G_J: *ub = rs; p = h->J; break;
+    case G_AOUT: *ub = rs; p = h->a_out; break;
+    case G_JOUT: *ub = rs; p = h->j_out; break;
+    default: *ub = (size_t)(kUnit / gs::kForceBlock) * sizeof(double); p = h->wgmin; break;
+  }
+  return static_cast<char*>(p);
+}
+
+bool abort_comm(gs_hermite* h) {
+  ncclComm_t c = h->comm_live.exchange(nullptr);
+  if (!c) return false;
+  (void)ncclCommAbort(c);
+  return true;
+}
+
+// One rank's gather over RCCL, in place on the engine's stream: ncclAllGather for equal slices,
+// else every rank broadcasts its own slice, all P in one group call (as gather() of the stepper).
+int gather_comm(gs_hermite* h, int w) {
+  if (h->comm_live.load() == nullptr) {
+    gs_set_error("hermite: this rank of a multi-rank run has no live communicator "
+                 "(gs_hermite_comm_init) and is no shard of a gs_hermite_group_* call");
+    return -1;
+  }
+  size_t ub = 0;
+  char* buf = gbuf(h, w, &ub);
+  const int P = h->cfg.nranks, r = h->cfg.rank;
+  if (h->uniform) {
+    GS_NCCL(ncclAllGather(buf + (size_t)h->ubeg[r] * ub, buf, (size_t)h->ucnt[r] * ub, ncclChar,
+                          h->comm, h->stream));
+    return 0;
+  }
+  GS_NCCL(ncclGroupStart());
+  for (int q = 0; q < P; ++q) {
+    char* sl = buf + (size_t)h->ubeg[q] * ub;
+    GS_NCCL(ncclBroadcast(sl, sl, (size_t)h->ucnt[q] * ub, ncclChar, q, h->comm, h->stream));
+  }
+  GS_NCCL(ncclGroupEnd());
+  return 0;
+}
+
+// The shards of a virtual group: every shard's stream waits until the others' rows are ready,
+// then copies their slices into its own arrays.
+int gather_group(gs_hermite* const* sh, int P, std::initializer_list<int> ws) {
+  for (int r = 0; r < P; ++r) GS_HIP(hipEventRecord(sh[r]->ev, sh[r]->stream));
+  for (int d = 0; d < P; ++d)
+    for (int q = 0; q < P; ++q)
+      if (q != d) GS_HIP(hipStreamWaitEvent(sh[d]->stream, sh[q]->ev, 0));
+  for (int w : ws)
+    for (int d = 0; d < P; ++d)
+      for (int q = 0; q < P; ++q) {
+        if (q == d) continue;
+        size_t ub = 0;
+        char* dst = gbuf(sh[d], w, &ub);
+        const char* src = gbuf(sh[q], w, &ub);
+        const size_t off = (size_t)sh[d]->ubeg[q] * ub;
+        GS_HIP(hipMemcpyAsync(dst + off, src + off, (size_t)sh[d]->ucnt[q] * ub,
+                              hipMemcpyDeviceToDevice, sh[d]->stream));
+      }
+  return 0;
+}
+
+// Gather the listed arrays: nothing on one rank, RCCL for a lone rank of P, copies for a group.
+int gather(gs_hermite* const* sh, int P, std::initializer_list<int> ws) {
+  if (P > 1) return gather_group(sh, P, ws);
+  if (!multi(sh[0])) return 0;
+  for (int w : ws)
+    if (gather_comm(sh[0], w)) return -1;
+  return 0;
+}
+
+// shards[r] is rank r of P of one run on one device (or: one engine, whatever its rank).
+int check_group(gs_hermite* const* sh, int P) {
+  if (!sh || P < 1) { gs_set_error("hermite group: bad arguments"); return -1; }
+  for (int r = 0; r < P; ++r)
+    if (!sh[r]) { gs_set_error("hermite group: null shard"); return -1; }
+  if (P == 1) return 0;
+  for (int r = 0; r < P; ++r) {
+    const gs_hermite* h = sh[r];
+    if (h->cfg.nranks != P || h->cfg.rank != r) {
+      gs_set_error("hermite group: shards[r] must be rank r of P (shards out of order, or "
+                   "created for another P)");
+      return -1;
+    }
+    if (h->n != sh[0]->n || h->chunk != sh[0]->chunk || h->cfg.dtype != sh[0]->cfg.dtype ||
+        h->cfg.device != sh[0]->cfg.device || h->comm_live.load() != nullptr) {
+      gs_set_error("hermite group: the shards differ in n, chunk, dtype or device, or hold a "
+                   "communicator");
+      return -1;
+    }
+  }
+  return 0;
+}
+
+// The first step minima of a group whose shards had their states set one by one.
+int close_wgmin(gs_hermite* const* sh, int P) {
+  bool open = false;
+  for (int r = 0; r < P; ++r) open = open || sh[r]->wgmin_open;
+  if (!open) return 0;
+  if (gather(sh, P, {G_WGMIN})) return -1;
+  for (int r = 0; r < P; ++r) sh[r]->wgmin_open = false;
+  return 0;
+}
+
+int wait_seen(gs_hermite* h, int64_t target);
+
 template <typename T, typename S>
-int step_t(gs_hermite* h, int32_t nsteps) {
-  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+int step_t(gs_hermite* const* sh, int P, int32_t nsteps) {
+  if (close_wgmin(sh, P)) return -1;
+  std::vector<gs::HArgs<T, S>> a;
+  for (int r = 0; r < P; ++r) a.push_back(make_args<T, S>(sh[r], gs::HM_STEP, false));
+  const bool mixed = is_mixed(sh[0]);
   for (int32_t k = 0; k < nsteps; ++k) {
-    GS_HIP((gs::launch_hermite_ctrl<T, S>(a, h->stream)));
-    GS_HIP((gs::launch_hermite_predict<T, S>(a, h->stream)));
-    GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, true, h->stream)));
-    GS_HIP((gs::launch_hermite_reduce<T, S>(a, h->stream)));
+    for (int r = 0; r < P; ++r) {
+      GS_HIP((gs::launch_hermite_ctrl<T, S>(a[r], sh[r]->stream)));
+      GS_HIP((gs::launch_hermite_predict<T, S>(a[r], sh[r]->stream)));
+    }
+    // (the same collectives on every rank whatever ctrl->active is: a chain past t_end gathers
+    // stale rows and changes nothing)
+    if (mixed ? gather(sh, P, {G_XP, G_VP, G_XL}) : gather(sh, P, {G_XP, G_VP})) return -1;
+    for (int r = 0; r < P; ++r) {
+      GS_HIP((gs::launch_hermite_eval<T, S>(a[r], sh[r]->ipl, sh[r]->groups, true,
+                                            sh[r]->stream)));
+      GS_HIP((gs::launch_hermite_reduce<T, S>(a[r], sh[r]->stream)));
+    }
+    if (gather(sh, P, {G_WGMIN})) return -1;
+    gs_hermite* h = sh[0];
+    if (P == 1 && !h->ring.empty()) {  // (an RCCL run: the progress record of the bounded waits)
+      const int64_t cap = (int64_t)h->ring.size();
+      if (h->rec - h->seen == cap && wait_seen(h, h->seen + 1)) return -1;
+      GS_HIP(hipEventRecord(h->ring[(size_t)(h->rec % cap)], h->stream));
+      h->rec += 1;
+    }
   }
   return 0;
 }
@@ -439,7 +602,103 @@ int start_from_state(gs_hermite* h) {
         return eval_current<decltype(t), decltype(s)>(h, gs::HM_INIT, false);
       }))
     return -1;
+  if (multi(h)) {
+    // every rank holds all of x, v (uploaded or generated whole), so only the step minima of
+    // the other ranks' rows are missing: gathered now (RCCL), or by the group's next call
+    if (h->comm_live.load() != nullptr) {
+      if (gather_comm(h, G_WGMIN)) return -1;
+    } else {
+      h->wgmin_open = true;
+    }
+  }
   return h->block ? block_start(h, 0) : 0;
+}
+
+// Bounded wait of an RCCL run for its chain number `target` (see gs_hermite_sync).
+int wait_seen(gs_hermite* h, int64_t target) {
+  using clock = std::chrono::steady_clock;
+  auto last = clock::now();
+  const int64_t cap = (int64_t)h->ring.size();
+  while (h->seen < target) {
+    const hipError_t e = hipEventQuery(h->ring[(size_t)(h->seen % cap)]);
+    if (e == hipSuccess) {
+      h->seen += 1;
+      last = clock::now();
+      continue;
+    }
+    if (e != hipErrorNotReady) GS_HIP(e);
+    if (gs_hermite_comm_check(h)) return -1;
+    if (h->step_timeout_s > 0.0 &&
+        std::chrono::duration<double>(clock::now() - last).count() > h->step_timeout_s) {
+      abort_comm(h);
+      gs_set_error("hermite: no step completed within the step timeout; RCCL communicator "
+                   "aborted");
+      return -1;
+    }
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+  }
+  return 0;
+}
+
+int get_state_group(gs_hermite* const* sh, int P, double* pos, double* vel, double* mass,
+                    double* acc, double* jerk) {
+  gs_hermite* h = sh[0];
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (gather(sh, P, {G_X, G_V, G_A, G_J})) return -1;
+  const bool f32 = h->esz == 4;
+  const std::pair<const void*, double*> rows[4] = {{h->X, pos}, {h->V, vel}, {h->A, acc},
+                                                   {h->J, jerk}};
+  for (const auto& r : rows)
+    if (f32 ? download_rows<float>(h, r.first, h->n, r.second, 3)
+            : download_rows<double>(h, r.first, h->n, r.second, 3))
+      return -1;
+  if (mass)
+    for (int64_t i = 0; i < h->n; ++i) mass[i] = h->mass_host[(size_t)i];
+  for (int r = 1; r < P; ++r) GS_HIP(hipStreamSynchronize(sh[r]->stream));
+  return 0;
+}
+
+int derivs_group(gs_hermite* const* sh, int P, double* acc4, double* jerk4, double* q,
+                 int32_t* nn) {
+  gs_hermite* h = sh[0];
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (gather(sh, P, {G_X, G_V})) return -1;  // (each rank's corrector moved its own rows only)
+  for (int r = 0; r < P; ++r)
+    if (by_dtype(sh[r], [&](auto t, auto s) {
+          return eval_current<decltype(t), decltype(s)>(sh[r], gs::HM_OUT, true);
+        }))
+      return -1;
+  if (gather(sh, P, {G_AOUT, G_JOUT})) return -1;
+  const bool f32 = h->esz == 4;
+  if (f32 ? download_rows<float>(h, h->a_out, h->n, acc4, 4)
+          : download_rows<double>(h, h->a_out, h->n, acc4, 4))
+    return -1;
+  if (f32 ? download_rows<float>(h, h->j_out, h->n, jerk4, 4)
+          : download_rows<double>(h, h->j_out, h->n, jerk4, 4))
+    return -1;
+  for (int r = 1; r < P; ++r) GS_HIP(hipStreamSynchronize(sh[r]->stream));
+  return download_nn(h, h->n, q, nn);
+}
+
+// Milliseconds per evaluate launch at the engine's current predicted rows.
+template <typename T, typename S>
+int time_eval_t(gs_hermite* h, int32_t reps, double* ms) {
+  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  GS_HIP(hipEventCreate(&e0));
+  GS_HIP(hipEventCreate(&e1));
+  GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));  // warm
+  GS_HIP(hipEventRecord(e0, h->stream));
+  for (int32_t k = 0; k < reps; ++k)
+    GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));
+  GS_HIP(hipEventRecord(e1, h->stream));
+  GS_HIP(hipEventSynchronize(e1));
+  float t = 0.0f;
+  GS_HIP(hipEventElapsedTime(&t, e0, e1));
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  *ms = (double)t / reps;
+  return 0;
 }
 
 }  // namespace
@@ -452,8 +711,8 @@ static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int3
 
 int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   if (!cfg || !out) { gs_set_error("hermite: null argument"); return -1; }
-  if (cfg->nranks != 1 || cfg->rank != 0) {
-    gs_set_error("hermite runs on one rank (nranks must be 1)");
+  if (cfg->nranks < 1 || cfg->rank < 0 || cfg->rank >= cfg->nranks) {
+    gs_set_error("hermite: bad rank/nranks");
     return -1;
   }
   if (cfg->n < 1) { gs_set_error("hermite: n must be >= 1"); return -1; }
@@ -477,6 +736,24 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   h->chunk = chunk;
   h->n_pad = gs::round_up(cfg->n, chunk);
   h->n_chunks = (int32_t)(h->n_pad / chunk);
+  for (int32_t q = 0; q < cfg->nranks; ++q) {
+    int64_t b = 0, c = 0;
+    if (gs_hermite_partition(cfg->n, chunk, cfg->nranks, q, &b, &c)) {
+      delete h;
+      return -1;
+    }
+    if (b >= cfg->n) {
+      gs_set_error("hermite: more ranks than units of 1024 rows that hold a body (a rank would "
+                   "own ghost rows only)");
+      delete h;
+      return -1;
+    }
+    h->ubeg.push_back(b / kUnit);
+    h->ucnt.push_back(c / kUnit);
+    if (c != h->n_pad / cfg->nranks) h->uniform = false;
+  }
+  h->row0 = h->ubeg[(size_t)cfg->rank] * kUnit;
+  h->n_loc = h->ucnt[(size_t)cfg->rank] * kUnit;
   if (launch_shape(h)) {
     delete h;
     return -1;
@@ -497,15 +774,16 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   } while (0)
   HM_TRY(hipSetDevice(cfg->device));
   HM_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  const size_t rb = rows_bytes(h), pb = pair_rows_bytes(h);
+  HM_TRY(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
+  const size_t rb = rows_bytes(h), pb = (size_t)h->n_loc * 4 * h->psz;  // (partials: own rows)
   for (void** p : {&h->X, &h->V, &h->A, &h->J, &h->a_out, &h->j_out}) {
     HM_TRY(hipMalloc(p, rb));
     HM_TRY(hipMemsetAsync(*p, 0, rb, h->stream));
   }
   for (void** p : {&h->XP, &h->VP, &h->XL}) {
     if (p == &h->XL && !is_mixed(h)) continue;
-    HM_TRY(hipMalloc(p, pb));
-    HM_TRY(hipMemsetAsync(*p, 0, pb, h->stream));
+    HM_TRY(hipMalloc(p, pair_rows_bytes(h)));
+    HM_TRY(hipMemsetAsync(*p, 0, pair_rows_bytes(h), h->stream));
   }
   HM_TRY(hipMalloc(&h->PA, pb * (size_t)h->n_chunks));
   HM_TRY(hipMalloc(&h->PJ, pb * (size_t)h->n_chunks));
@@ -529,6 +807,9 @@ int gs_hermite_destroy(gs_hermite* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->cfg.device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (ncclComm_t c = h->comm_live.exchange(nullptr)) (void)ncclCommDestroy(c);
+  for (hipEvent_t e : h->ring) (void)hipEventDestroy(e);
+  if (h->ev) (void)hipEventDestroy(h->ev);
   for (void* p : {h->X, h->V, h->A, h->J, h->XP, h->VP, h->XL, h->a_out, h->j_out, h->PA, h->PJ,
                   (void*)h->ctrl, (void*)h->wgmin, (void*)h->mass_dev, (void*)h->nonfinite})
     if (p) (void)hipFree(p);
@@ -544,8 +825,8 @@ int gs_hermite_layout(gs_hermite* h, gs_layout* out) {
   *out = gs_layout{};
   out->n = h->n;
   out->n_pad = h->n_pad;
-  out->n_local = h->n_pad;
-  out->local_begin = 0;
+  out->n_local = h->n_loc;
+  out->local_begin = h->row0;
   out->chunk = h->chunk;
   out->n_chunks = h->n_chunks;
   out->ipl = h->ipl;
@@ -631,17 +912,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
 
 int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, double* acc,
                          double* jerk) {
-  GS_HIP(hipSetDevice(h->cfg.device));
-  const bool f32 = h->esz == 4;
-  const std::pair<const void*, double*> rows[4] = {{h->X, pos}, {h->V, vel}, {h->A, acc},
-                                                   {h->J, jerk}};
-  for (const auto& r : rows)
-    if (f32 ? download_rows<float>(h, r.first, h->n, r.second, 3)
-            : download_rows<double>(h, r.first, h->n, r.second, 3))
-      return -1;
-  if (mass)
-    for (int64_t i = 0; i < h->n; ++i) mass[i] = h->mass_host[(size_t)i];
-  return 0;
+  return get_state_group(&h, 1, pos, vel, mass, acc, jerk);
 }
 
 int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
@@ -650,31 +921,26 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
 
 int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn) {
   if ((q || nn) && !h->nn) { gs_set_error("hermite derivs_nn: collisions are off"); return -1; }
-  GS_HIP(hipSetDevice(h->cfg.device));
-  const bool f32 = h->esz == 4;
-  if (by_dtype(h, [&](auto t, auto s) {
-        return eval_current<decltype(t), decltype(s)>(h, gs::HM_OUT, true);
-      }))
-    return -1;
-  if (f32 ? download_rows<float>(h, h->a_out, h->n, acc4, 4)
-          : download_rows<double>(h, h->a_out, h->n, acc4, 4))
-    return -1;
-  if (f32 ? download_rows<float>(h, h->j_out, h->n, jerk4, 4)
-          : download_rows<double>(h, h->j_out, h->n, jerk4, 4))
-    return -1;
-  return download_nn(h, h->n, q, nn);
+  return derivs_group(&h, 1, acc4, jerk4, q, nn);
 }
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
   return by_dtype(h, [&](auto t, auto s) {
     return h->block ? block_step_t<decltype(t), decltype(s)>(h, nsteps)
-                    : step_t<decltype(t), decltype(s)>(h, nsteps);
+                    : step_t<decltype(t), decltype(s)>(&h, 1, nsteps);
   });
 }
 
 int gs_hermite_sync(gs_hermite* h) {
   GS_HIP(hipSetDevice(h->cfg.device));
+  if (!h->ring.empty()) {
+    // An RCCL run: a peer that never arrives must not block this rank for ever. Wait for the
+    // recorded chains one by one, watching the communicator's async error; when none completes
+    // for the step timeout the communicator is aborted, which releases the stream.
+    if (wait_seen(h, h->rec)) return -1;
+    if (h->comm_live.load() == nullptr) { gs_set_error("hermite: communicator aborted"); return -1; }
+  }
   GS_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -682,6 +948,7 @@ int gs_hermite_sync(gs_hermite* h) {
 int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   if (!h || !out) { gs_set_error("hermite status: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
+  if (!h->ring.empty() && wait_seen(h, h->rec)) return -1;  // (an RCCL run: a bounded wait)
   if (h->block) {
     gs::HermiteBlockCtrl b;
     if (read_bctrl(h, &b)) return -1;
@@ -735,6 +1002,10 @@ int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
     free_block(h);
     h->block = false;
     return 0;
+  }
+  if (multi(h)) {
+    gs_set_error("hermite block steps (block_steps) run on one rank");
+    return -1;
   }
   if (max_level < 0 || max_level > 40) {
     gs_set_error("hermite block steps: max_level must be in 0..40");
@@ -872,6 +1143,10 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
     if (read_ctrl(h, &c)) return -1;
     return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0);
   }
+  if (multi(h)) {
+    gs_set_error("hermite collisions run on one rank");
+    return -1;
+  }
   if (h->n_pad > (int64_t)std::numeric_limits<int32_t>::max()) {
     gs_set_error("hermite set_collisions: too many bodies for int32 neighbour indices");
     return -1;
@@ -970,11 +1245,12 @@ int64_t gs_hermite_count_nonfinite(gs_hermite* h) {
     return -1;
   }
   hipError_t e = h->esz == 4
-      ? gs::launch_count_nonfinite<float>(static_cast<const float*>(h->X), 0, h->n_pad,
-                                          static_cast<const float*>(h->V), h->nonfinite, h->stream)
-      : gs::launch_count_nonfinite<double>(static_cast<const double*>(h->X), 0, h->n_pad,
-                                           static_cast<const double*>(h->V), h->nonfinite,
-                                           h->stream);
+      ? gs::launch_count_nonfinite<float>(static_cast<const float*>(h->X), h->row0, h->n_loc,
+                                          static_cast<const float*>(h->V) + 4 * h->row0,
+                                          h->nonfinite, h->stream)
+      : gs::launch_count_nonfinite<double>(static_cast<const double*>(h->X), h->row0, h->n_loc,
+                                           static_cast<const double*>(h->V) + 4 * h->row0,
+                                           h->nonfinite, h->stream);  // (the rows this rank owns)
   unsigned long long cnt = 0;
   if (e != hipSuccess ||
       hipMemcpyAsync(&cnt, h->nonfinite, sizeof(cnt), hipMemcpyDeviceToHost, h->stream) !=
@@ -984,6 +1260,107 @@ int64_t gs_hermite_count_nonfinite(gs_hermite* h) {
     return -1;
   }
   return (int64_t)cnt;
+}
+
+// ---- ranks: virtual group and RCCL -----------------------------------------------------
+
+int gs_hermite_group_step(gs_hermite** shards, int32_t P, int32_t nsteps) {
+  if (check_group(shards, P)) return -1;
+  for (int r = 0; r < P; ++r)
+    if (shards[r]->block) { gs_set_error("hermite group: block steps run on one rank"); return -1; }
+  GS_HIP(hipSetDevice(shards[0]->cfg.device));
+  return by_dtype(shards[0], [&](auto t, auto s) {
+    return step_t<decltype(t), decltype(s)>(shards, P, nsteps);
+  });
+}
+
+int gs_hermite_group_get_state(gs_hermite** shards, int32_t P, double* pos, double* vel,
+                               double* mass, double* acc, double* jerk) {
+  if (check_group(shards, P)) return -1;
+  return get_state_group(shards, P, pos, vel, mass, acc, jerk);
+}
+
+int gs_hermite_group_derivs(gs_hermite** shards, int32_t P, double* acc4, double* jerk4) {
+  if (check_group(shards, P)) return -1;
+  return derivs_group(shards, P, acc4, jerk4, nullptr, nullptr);
+}
+
+int gs_hermite_group_time_eval(gs_hermite** shards, int32_t P, int32_t reps, double* ms) {
+  if (check_group(shards, P) || !ms) return -1;
+  if (reps < 1) reps = 1;
+  GS_HIP(hipSetDevice(shards[0]->cfg.device));
+  for (int r = 0; r < P; ++r) GS_HIP(hipStreamSynchronize(shards[r]->stream));
+  for (int r = 0; r < P; ++r)  // (one shard at a time: each has the device to itself)
+    if (by_dtype(shards[r], [&](auto t, auto s) {
+          return time_eval_t<decltype(t), decltype(s)>(shards[r], reps, ms + r);
+        }))
+      return -1;
+  return 0;
+}
+
+int gs_hermite_comm_init(gs_hermite* h, const void* id128, int32_t rank, int32_t nranks) {
+  if (!h || !id128) { gs_set_error("hermite comm_init: null argument"); return -1; }
+  if (rank != h->cfg.rank || nranks != h->cfg.nranks) {
+    gs_set_error("hermite comm_init: rank/nranks differ from the engine's");
+    return -1;
+  }
+  if (h->comm) { gs_set_error("hermite comm_init: called twice"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (nranks == 1) return 0;  // (one rank gathers nothing: no communicator is kept)
+  ncclUniqueId id;
+  memcpy(&id, id128, sizeof(id));
+  GS_NCCL(ncclCommInitRank(&h->comm, nranks, id, rank));
+  h->comm_live.store(h->comm);
+  int32_t info[3] = {0, -1, -1};
+  const int bad = gs::rt::comm_verify(h->comm, nranks, rank, h->cfg.device, info,
+                                      "hermite comm_init");
+  h->comm_count = info[0];
+  h->comm_user_rank = info[1];
+  h->comm_cu_device = info[2];
+  if (bad) {
+    const std::string why = gs_last_error();  // (kept across the abort)
+    abort_comm(h);
+    gs_set_error(why.c_str());
+    return -1;
+  }
+  h->ring.resize(32);
+  for (hipEvent_t& e : h->ring) GS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  // Warm-up (RCCL builds its transports on the first collective): the gather of the step minima,
+  // which are all +inf before a state is set, waited for like a step.
+  if (gather_comm(h, G_WGMIN)) return -1;
+  GS_HIP(hipEventRecord(h->ring[0], h->stream));
+  h->rec = 1;
+  h->seen = 0;
+  return wait_seen(h, 1);
+}
+
+int gs_hermite_comm_info(gs_hermite* h, int32_t* count, int32_t* user_rank, int32_t* cu_device) {
+  if (!h) return -1;
+  if (count) *count = h->comm_live.load() != nullptr ? h->comm_count : 0;
+  if (user_rank) *user_rank = h->comm_user_rank;
+  if (cu_device) *cu_device = h->comm_cu_device;
+  return 0;
+}
+
+int gs_hermite_comm_check(gs_hermite* h) {
+  if (!h || !h->comm) return 0;
+  ncclComm_t c = h->comm_live.load();
+  if (!c) { gs_set_error("RCCL communicator aborted (timeout or async error)"); return -1; }
+  if (gs::rt::comm_async_check(c)) {
+    const std::string why = gs_last_error();
+    abort_comm(h);
+    gs_set_error(why.c_str());
+    return -1;
+  }
+  return 0;
+}
+
+int32_t gs_hermite_abort(gs_hermite* h) { return h && abort_comm(h) ? 1 : 0; }
+
+int gs_hermite_set_step_timeout(gs_hermite* h, double timeout_s) {
+  if (!h || !(timeout_s >= 0.0)) { gs_set_error("hermite: bad step timeout"); return -1; }
+  h->step_timeout_s = timeout_s;
+  return 0;
 }
 
 }  // extern "C"

@@ -236,7 +236,11 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
 // NN: the lane also keeps the nearest neighbour (smallest q, lowest j on a tie) of each of its
 // i-bodies over the chunk; the partial is (PJ[c][i].w, PN[c][i]). j is uniform over the wave, so
 // the ghost-row test is a scalar compare.
-template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T, bool NN = false>
+// SLICE (a rank of a multi-rank run): the i-rows are the rank's own, a.row0 + [0, a.n_loc), which
+// the grid's x extent covers; the partials are indexed by local row with stride a.n_loc. The j
+// sweep is the same, so a body's bits are those of the one-rank run.
+template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T, bool NN = false,
+          bool SLICE = false>
 __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int gated) {
   constexpr bool DS = sizeof(S) != sizeof(T);
   constexpr int TB = Tile<T>::kBodies;
@@ -244,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
   __shared__ __attribute__((aligned(16))) V4<T> tv[2][TB];
   __shared__ __attribute__((aligned(16))) V4<T> tl[2][DS ? TB : 1];
   if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
-  const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);
+  const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);  // (SLICE: counted from a.row0)
   int64_t n_act = 0;
   if constexpr (GATHER) {
     const HermiteBlockCtrl* bc = a.blk.bc;
@@ -269,6 +273,7 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
     int64_t row = ib + threadIdx.x + k * kBlock;
+    if constexpr (SLICE) row += a.row0;
     if constexpr (GATHER) row = a.blk.list[row < n_act ? row : n_act - 1];  // (spare slots: a copy)
     const V4<T> x = XP[row];
     const V4<T> v = VP[row];
@@ -334,8 +339,13 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
           oj.w = nr.q[k];
           a.PN[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = nr.n[k];
         }
-        PA[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oa;
-        PJ[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oj;
+        if constexpr (SLICE) {
+          PA[(int64_t)c * a.n_loc + ib + threadIdx.x + k * kBlock] = oa;
+          PJ[(int64_t)c * a.n_loc + ib + threadIdx.x + k * kBlock] = oj;
+        } else {
+          PA[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oa;
+          PJ[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oj;
+        }
       }
       hzero<T, IPL>(st);
       if constexpr (NN) hnear_reset<T, IPL>(nr);
@@ -410,10 +420,11 @@ __device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i,
   }
 }
 
-template <typename T, typename S, bool NN = false>
+// SLICE: the grid covers the rank's rows a.row0 + [0, a.n_loc) of the full-length XP, VP (XL).
+template <typename T, typename S, bool NN = false, bool SLICE = false>
 __global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) {
   if (!a.ctrl->active) return;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = (SLICE ? a.row0 : 0) + (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
   V4<S> xp = {S(0), S(0), S(0), S(0)}, vp = xp;
   if (i < a.n_real) {
@@ -477,25 +488,33 @@ __device__ __forceinline__ double norm3(double x, double y, double z) {
 // workgroup takes part: ghost rows, |j| = 0, a non-finite ratio, or a fixed-step run).
 // NN: the chunks' (q, j) partials fold with a strict less in chunk order (the lowest j keeps a
 // tie); HM_OUT writes them to q_out / nn_out, the other modes record them (nn_record).
-template <typename T, typename S, bool NN = false>
+// SLICE: the grid covers the rank's rows; it reads the rank's partials [n_chunks][n_loc] and
+// writes the rows' entries of the full-length X, V, A, J, outputs and wgmin.
+template <typename T, typename S, bool NN = false, bool SLICE = false>
 __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
   __shared__ double red[kBlock / 64];
   if (a.mode == HM_STEP && !a.ctrl->active) return;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad is a multiple of 256)
+  int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad is a multiple of 256)
+  const int64_t li = i;  // the row's slot in the partials
+  int64_t pstride = a.n_pad;
+  if constexpr (SLICE) {
+    i += a.row0;
+    pstride = a.n_loc;
+  }
   const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
   const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
   S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
   T bq = T(INFINITY);
   int32_t bn = -1;
   for (int c = 0; c < a.n_chunks; ++c) {
-    const V4<T> pa = PA[(int64_t)c * a.n_pad + i];
-    const V4<T> pj = PJ[(int64_t)c * a.n_pad + i];
+    const V4<T> pa = PA[(int64_t)c * pstride + li];
+    const V4<T> pj = PJ[(int64_t)c * pstride + li];
     a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
     j1x += pj.x; j1y += pj.y; j1z += pj.z;
     if constexpr (NN) {
       if (pj.w < bq) {
         bq = pj.w;
-        bn = a.PN[(int64_t)c * a.n_pad + i];
+        bn = a.PN[(int64_t)c * pstride + li];
       }
     }
   }
@@ -576,7 +595,7 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
     J[i] = oj;
   }
   dti = block_min(dti, red);
-  if (threadIdx.x == 0) a.wgmin[blockIdx.x] = dti;
+  if (threadIdx.x == 0) a.wgmin[(SLICE ? a.row0 / kBlock : 0) + blockIdx.x] = dti;
 }
 
 
@@ -980,8 +999,22 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64
 // ---------------------------------------------------------------------------------------
 // Host launchers.
 
+// A rank's slice of a multi-rank run (never with collisions or block steps).
+template <typename T, typename S>
+static bool is_slice(const HArgs<T, S>& a) { return a.n_loc != a.n_pad; }
+
 template <typename T, typename S, int IPL>
 static hipError_t launch_eval_t(const HArgs<T, S>& a, int groups, bool gated, hipStream_t s) {
+  if (is_slice(a)) {
+    const dim3 grid((unsigned)(a.n_loc / (kBlock * IPL)), (unsigned)groups);
+    if (a.phi)
+      hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S, false, true>), grid,
+                         dim3(kBlock), 0, s, a, (int)gated);
+    else
+      hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S, false, true>), grid,
+                         dim3(kBlock), 0, s, a, (int)gated);
+    return hipGetLastError();
+  }
   const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
   // Mixed precision with collisions on would need all 256 VGPRs at 4 i-bodies per lane: that
   // kernel is not built, and the runtime's launch shape never asks for it (hermite.hip).
@@ -1025,6 +1058,9 @@ hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool g
       (int64_t)a.n_chunks * a.chunk != a.n_pad || (gated && !a.ctrl) ||
       (sizeof(S) != sizeof(T) && !a.XL) || (a.nn && !nn_args_ok(a)))
     return hipErrorInvalidValue;
+  if (a.row0 < 0 || a.n_loc < 1 || a.row0 + a.n_loc > a.n_pad || a.n_loc % (kBlock * ipl) ||
+      a.row0 % kBlock || (is_slice(a) && (a.nn || a.blk.bc)))
+    return hipErrorInvalidValue;
   if (groups < 1) groups = 1;
   if (groups > a.n_chunks) groups = a.n_chunks;
   switch (ipl) {
@@ -1046,6 +1082,13 @@ hipError_t launch_hermite_ctrl(const HArgs<T, S>& a, hipStream_t s) {
 
 template <typename T, typename S>
 hipError_t launch_hermite_predict(const HArgs<T, S>& a, hipStream_t s) {
+  if (is_slice(a)) {
+    if (a.nn || a.row0 < 0 || a.row0 % kBlock || a.n_loc % kBlock || a.row0 + a.n_loc > a.n_pad)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL((hermite_predict_kernel<T, S, false, true>),
+                       dim3((unsigned)(a.n_loc / kBlock)), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.nn)
     hipLaunchKernelGGL((hermite_predict_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
                        dim3(kBlock), 0, s, a);
@@ -1071,6 +1114,13 @@ hipError_t launch_hermite_stage(const HArgs<T, S>& a, hipStream_t s) {
 
 template <typename T, typename S>
 hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s) {
+  if (is_slice(a)) {
+    if (a.nn || a.row0 < 0 || a.row0 % kBlock || a.n_loc % kBlock || a.row0 + a.n_loc > a.n_pad)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL((hermite_reduce_kernel<T, S, false, true>),
+                       dim3((unsigned)(a.n_loc / kBlock)), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.nn)
     hipLaunchKernelGGL((hermite_reduce_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
                        dim3(kBlock), 0, s, a);

@@ -114,6 +114,35 @@ bool abort_comm(gs_stepper* s) {
   return true;
 }
 
+int comm_verify(ncclComm_t c, int nranks, int rank, int device, int32_t info[3],
+                const char* who) {
+  int cnt = 0, ur = -1, dev = -1;
+  GS_NCCL(ncclCommCount(c, &cnt));
+  GS_NCCL(ncclCommUserRank(c, &ur));
+  GS_NCCL(ncclCommCuDevice(c, &dev));
+  info[0] = cnt;
+  info[1] = ur;
+  info[2] = dev;
+  if (cnt == nranks && ur == rank && dev == device) return 0;
+  char b[256];
+  snprintf(b, sizeof(b),
+           "%s: RCCL formed %d rank(s), this one rank %d on device %d; expected %d "
+           "rank(s), rank %d on device %d",
+           who, cnt, ur, dev, nranks, rank, device);
+  gs_set_error(b);
+  return -1;
+}
+
+int comm_async_check(ncclComm_t c) {
+  ncclResult_t async = ncclSuccess;
+  GS_NCCL(ncclCommGetAsyncError(c, &async));
+  if (async == ncclSuccess || async == ncclInProgress) return 0;
+  char b[256];
+  snprintf(b, sizeof(b), "RCCL async error: %s; communicator aborted", ncclGetErrorString(async));
+  gs_set_error(b);
+  return -1;
+}
+
 // A communicator the watchdog thread (or a timeout / async error) aborted must not be used
 // again: have_comm stays true on the main thread until it notices, but s->comm is freed once
 // comm_live is null. Every RCCL call site checks this first.
@@ -357,21 +386,15 @@ int gs_stepper_comm_init(gs_stepper* s, const void* id128, int32_t rank, int32_t
   // What RCCL actually formed: the rank count, this rank's place in it and the
   // device its kernels run on must be the ones the layout and the stepper were built for.
   {
-    int cnt = 0, ur = -1, dev = -1;
-    GS_NCCL(ncclCommCount(s->comm, &cnt));
-    GS_NCCL(ncclCommUserRank(s->comm, &ur));
-    GS_NCCL(ncclCommCuDevice(s->comm, &dev));
-    s->comm_count = cnt;
-    s->comm_user_rank = ur;
-    s->comm_cu_device = dev;
-    if (cnt != nranks || ur != rank || dev != s->cfg.device) {
-      char b[256];
-      snprintf(b, sizeof(b),
-               "comm_init: RCCL formed %d rank(s), this one rank %d on device %d; expected %d "
-               "rank(s), rank %d on device %d",
-               cnt, ur, dev, nranks, rank, s->cfg.device);
+    int32_t info[3] = {0, -1, -1};
+    const int bad = comm_verify(s->comm, nranks, rank, s->cfg.device, info, "comm_init");
+    s->comm_count = info[0];
+    s->comm_user_rank = info[1];
+    s->comm_cu_device = info[2];
+    if (bad) {
+      const std::string why = gs_last_error();  // (kept across the abort)
       abort_comm(s);
-      gs_set_error(b);
+      gs_set_error(why.c_str());
       return -1;
     }
   }
@@ -440,14 +463,11 @@ int gs_stepper_comm_check(gs_stepper* s) {
     s->have_comm = false;
     return -1;
   }
-  ncclResult_t async = ncclSuccess;
-  GS_NCCL(ncclCommGetAsyncError(s->comm, &async));
-  if (async != ncclSuccess && async != ncclInProgress) {
-    char b[256];
-    snprintf(b, sizeof(b), "RCCL async error: %s; communicator aborted", ncclGetErrorString(async));
+  if (comm_async_check(s->comm)) {
+    const std::string why = gs_last_error();
     abort_comm(s);
     s->have_comm = false;
-    gs_set_error(b);
+    gs_set_error(why.c_str());
     return -1;
   }
   return 0;

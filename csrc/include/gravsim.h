@@ -99,6 +99,11 @@ int64_t gs_sym_bytes(int64_t n_pad, int32_t nranks, int32_t esz);
 // reduction-tree nodes: B blocks of RB rows, nn nodes sent by this rank, nb by lower ranks,
 // NN in all (gs_common.h).
 int gs_sym_rank_rows(int64_t n_pad, int32_t nranks, int32_t rank, int32_t* a0, int32_t* rows);
+// Rows a rank of a multi-rank Hermite run owns: n_pad = n rounded up to the chunk (0: auto), in
+// units of 1024 rows dealt out contiguously by mpi.c's remainder rule (the first `units mod
+// nranks` ranks hold one more). Refuses nranks above the unit count.
+int gs_hermite_partition(int64_t n, int32_t chunk, int32_t nranks, int32_t rank,
+                         int64_t* row_begin, int64_t* row_count);
 int gs_sym_nodes(int64_t n_pad, int32_t nranks, int32_t rank, int32_t* B, int32_t* RB,
                  int32_t* nn, int32_t* nb, int32_t* NN);
 // Busiest rank's work over the mean of the sym schedule's whole-row-block ownership
@@ -312,11 +317,17 @@ int gs_stepper_force_mode(gs_stepper* s, int32_t* exact, double* eps2);
 void* gs_stepper_compute_stream(gs_stepper* s);
 
 // ---------------------------------------------------------------- Hermite (libgravsim_hip)
-// 4th-order Hermite predictor-corrector (Makino & Aarseth 1992) on one GPU: hermite.hip, the
+// 4th-order Hermite predictor-corrector (Makino & Aarseth 1992): hermite.hip, the
 // acceleration+jerk kernel in nbody_hermite.hip. Uses cfg's n, dtype, device, dt (the fixed step,
 // or the ceiling of the adaptive one), G, cutoff, softening, chunk, ipl (0 auto; 1, 2, fp32: 4)
 // and split_groups (chunk groups of the evaluate grid, 0 auto); every launch shape gives the
-// same bits. Refuses nranks != 1 and cutoff == softening == 0.
+// same bits. Refuses cutoff == softening == 0.
+// nranks > 1 (shared steps only: block steps and collisions are refused there): rank r owns the
+// rows of gs_hermite_partition and predicts, evaluates and corrects those against all j; the
+// predicted rows and the per-workgroup step minima are gathered every step, so every rank holds
+// the same control block and a P-rank run equals the one-rank run bit for bit. The gathers are
+// RCCL collectives (gs_hermite_comm_init) or, for P shards in one process, device copies
+// (gs_hermite_group_*). A rank that would own no real body is refused.
 typedef struct gs_hermite gs_hermite;
 typedef struct gs_hermite_info {
   double time;      // time reached [s]
@@ -418,6 +429,29 @@ int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx
 // Virtual ranks on one device: shards[r] created with rank r of P; steps all of them in
 // lockstep with the all-gather done by device copies (the RCCL schedule without RCCL).
 int gs_group_step(gs_stepper** shards, int32_t P, int32_t nsteps);
+// The same for Hermite shards (shards[r] created with rank r of P on one device, the state set on
+// each): every shard runs the slice kernels and the control kernel of the RCCL path. nsteps 0
+// only completes what setting the states left open (the gather of the first step minima).
+// The reads return all n rows (as gs_hermite_get_state / gs_hermite_derivs on every rank of an
+// RCCL run). gs_hermite_group_time_eval: milliseconds per evaluate launch of each shard
+// (ms[P], device events around `reps` launches at the shard's current predicted rows).
+int gs_hermite_group_step(gs_hermite** shards, int32_t P, int32_t nsteps);
+int gs_hermite_group_get_state(gs_hermite** shards, int32_t P, double* pos, double* vel,
+                               double* mass, double* acc, double* jerk);
+int gs_hermite_group_derivs(gs_hermite** shards, int32_t P, double* acc4, double* jerk4);
+int gs_hermite_group_time_eval(gs_hermite** shards, int32_t P, int32_t reps, double* ms);
+
+// RCCL for a multi-rank Hermite run, one process per GPU (as gs_stepper_comm_init / _comm_info /
+// _comm_check / gs_stepper_abort): the gathers of a step are in-place ncclAllGather calls on
+// the engine's one stream (equal slices), or grouped in-place ncclBroadcast calls (uneven ones).
+// Collective; call before the state is set. gs_hermite_sync then polls the stream and the
+// communicator's async error, and aborts the communicator when nothing completes for
+// timeout_s (gs_hermite_set_step_timeout; 0: no limit).
+int gs_hermite_comm_init(gs_hermite* h, const void* id128, int32_t rank, int32_t nranks);
+int gs_hermite_comm_info(gs_hermite* h, int32_t* count, int32_t* user_rank, int32_t* cu_device);
+int gs_hermite_comm_check(gs_hermite* h);
+int32_t gs_hermite_abort(gs_hermite* h);
+int gs_hermite_set_step_timeout(gs_hermite* h, double timeout_s);
 
 // RCCL: 128-byte unique id (rank 0 creates it; the launcher broadcasts it), then init.
 int gs_rccl_unique_id(void* out128);

@@ -102,6 +102,12 @@ struct HArgs {
   double* q_out;     // HM_OUT: q and neighbour per row of a_out / j_out
   int32_t* nn_out;
   int32_t nn;
+  // A rank's slice of a multi-rank run (last, as above): the rank predicts, evaluates and
+  // corrects rows row0 + [0, n_loc) (whole units of 1024 rows) against all j; PA / PJ are then
+  // [n_chunks][n_loc], indexed by local row; every other array keeps its full length and the
+  // runtime gathers the slices. One rank: row0 = 0, n_loc = n_pad, and the kernels are the
+  // forms without the SLICE flag.
+  int64_t row0, n_loc;
 };
 
 template <typename T, typename S>

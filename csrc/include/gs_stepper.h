@@ -335,6 +335,11 @@ int wait_until(gs_stepper* s, int64_t target, double timeout_s);
 int note_progress(gs_stepper* s);
 
 // stepper_comm.hip: the collectives (RCCL, the per-rank emulation's modeled ones).
+// What RCCL formed (ncclCommCount / UserRank / CuDevice) into info[3]; -1 with the error set
+// (prefixed `who`) when it is not `nranks` ranks, this one `rank` on `device`. The caller aborts.
+int comm_verify(ncclComm_t c, int nranks, int rank, int device, int32_t info[3], const char* who);
+// The communicator's async error: 0 healthy (or still in progress), -1 with the error set.
+int comm_async_check(ncclComm_t c);
 int comm_model(gs_stepper* s, const void* src, size_t bytes, size_t src_cap,
                size_t time_bytes = SIZE_MAX);
 void rank_slice(const gs_stepper* s, int q, int64_t* b0, int64_t* cnt);

@@ -39,7 +39,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--integrator", choices=["kd", "leapfrog", "hermite"], default=d.integrator,
                    help="kd: the reference's kick-drift update; leapfrog: the same kernel on "
                         "half-step-staggered velocities (second order); hermite: 4th-order "
-                        "predictor-corrector with its own acceleration+jerk kernel (one rank)")
+                        "predictor-corrector with its own acceleration+jerk kernel (its shared "
+                        "step also runs on --gpus P)")
     p.add_argument("--eta", type=float, default=d.eta,
                    help="hermite: accuracy parameter of the shared adaptive step (Aarseth's "
                         "criterion; --dt is then the largest step); 0 = fixed step")
@@ -112,7 +113,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="comma-separated N values: run each config in turn (pyspark.py sweep)")
     p.add_argument("--nproc", "--gpus", dest="nproc", type=int, default=0,
                    help="launch this many ranks (one per GPU) on this node through "
-                        "torch.distributed.run, like `mpirun -np N` (mpi.c); 0 = as launched")
+                        "torch.distributed.run, like `mpirun -np N` (mpi.c); 0 = as launched. "
+                        "hermite: shared steps on the GPU (not with --block-steps, --collisions "
+                        "or --device cpu)")
     p.add_argument("--diagnostics", action="store_true",
                    help="conserved quantities (total energy with the exact-cutoff potential, "
                         "linear and angular momentum) at the start and end of the run, and "
@@ -150,7 +153,7 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
                      nan_check_every=a.nan_check_every, metrics_json=a.metrics_json,
                      phase_timing=a.phase_timing,
                      diagnostics=a.diagnostics or a.diag_every > 0,
-                     diag_every=a.diag_every).validate()
+                     diag_every=a.diag_every, gpus=a.nproc).validate()
 
 
 def run_one(cfg: SimConfig, dist, log, quiet: bool = False, final: bool = True,
@@ -209,6 +212,10 @@ def main(argv: Optional[list[str]] = None) -> int:
     raw = list(sys.argv[1:] if argv is None else argv)
     a = build_parser().parse_args(raw)
     if a.nproc > 1 and "WORLD_SIZE" not in os.environ:
+        try:  # (what the configuration refuses, before any rank is launched)
+            config_from_args(a)
+        except ValueError as e:
+            raise SystemExit(f"gravsim: error: {e}")
         if a.device != "cpu":
             import torch  # device_count() does not initialise the GPU on this image
 

@@ -37,7 +37,7 @@ class SimConfig:
     softening: float = 0.0        # Plummer softening length (0 = reference semantics)
     cutoff_mode: str = "auto"     # GPU: exact (select) | fast (overflow-safe core) | auto
     integrator: str = "kd"        # kd (reference kick-drift) | leapfrog (staggered KDK) |
-                                  # hermite (4th-order predictor-corrector, one rank)
+                                  # hermite (4th-order predictor-corrector)
     eta: float = 0.0              # hermite: Aarseth accuracy parameter of the shared adaptive
                                   # step (0 = fixed step dt; then dt is the step's ceiling)
     t_end: Optional[float] = None  # hermite: stop at this time [s] (steps caps the step count)
@@ -88,6 +88,8 @@ class SimConfig:
     metrics_json: Optional[str] = None
     phase_timing: bool = False        # GPU: per-step phase events (comm/compute split in the
                                       # metrics; eager steps, no graph replay)
+    gpus: int = 0                     # ranks the run is launched with, one per GPU (0: as
+                                      # launched); hermite: shared steps on the GPU only
 
     def validate(self) -> "SimConfig":
         if self.n < 1:
@@ -150,6 +152,18 @@ class SimConfig:
                 raise ValueError("hermite needs cutoff > 0 or softening > 0 (the self term)")
             if self.ipl == 8 or (self.ipl == 4 and self.dtype == "fp64"):
                 raise ValueError("hermite: ipl must be 0, 1, 2 (or 4 for fp32 and mixed)")
+            if self.gpus > 1:  # (shared steps across ranks; the rest stays on one rank)
+                if self.block_steps:
+                    raise ValueError("hermite runs on one rank with block steps (--block-steps): "
+                                     "not with --gpus > 1")
+                if self.collisions != "off":
+                    raise ValueError("hermite runs on one rank with collisions (--collisions): "
+                                     "not with --gpus > 1")
+                if self.device == "cpu":
+                    raise ValueError("hermite runs on one rank on the CPU (--device cpu): "
+                                     "not with --gpus > 1")
+        if self.gpus < 0:
+            raise ValueError("gpus must be >= 0")
         if self.cutoff_mode not in ("auto", "exact", "fast"):
             raise ValueError("cutoff_mode must be auto, exact or fast")
         if self.strategy not in ("allgather", "ring"):

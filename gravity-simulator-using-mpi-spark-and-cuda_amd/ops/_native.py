@@ -118,6 +118,8 @@ def _declare_common(lib) -> None:
                                                  c_int32, POINTER(c_int32), c_int64], optional=True)
     _sig(lib, "gs_sym_split_parts", c_int32, [c_int64], optional=True)
     _sig(lib, "gs_auto_chunk", c_int32, [c_int64])
+    _sig(lib, "gs_hermite_partition", c_int32, [c_int64, c_int32, c_int32, c_int32,
+                                                POINTER(c_int64), POINTER(c_int64)])
     _sig(lib, "gs_ic_fill_host", None, [c_int32, c_uint64, c_int64, c_int64, c_int64, _PD, _PD,
                                         _PD])
 
@@ -253,6 +255,16 @@ def hip_lib():
         _sig(lib, "gs_hermite_closest", c_int32, [S, _PD, PI, c_int32])
         _sig(lib, "gs_hermite_clear_overlap", c_int32, [S])
         _sig(lib, "gs_hermite_derivs_nn", c_int32, [S, _PD, _PD, _PD, PI])
+        PS = POINTER(S)  # the shards of a virtual group
+        _sig(lib, "gs_hermite_group_step", c_int32, [PS, c_int32, c_int32])
+        _sig(lib, "gs_hermite_group_get_state", c_int32, [PS, c_int32, _PD, _PD, _PD, _PD, _PD])
+        _sig(lib, "gs_hermite_group_derivs", c_int32, [PS, c_int32, _PD, _PD])
+        _sig(lib, "gs_hermite_group_time_eval", c_int32, [PS, c_int32, c_int32, _PD])
+        _sig(lib, "gs_hermite_comm_init", c_int32, [S, c_void_p, c_int32, c_int32])
+        _sig(lib, "gs_hermite_comm_info", c_int32, [S, PI, PI, PI])
+        _sig(lib, "gs_hermite_comm_check", c_int32, [S])
+        _sig(lib, "gs_hermite_abort", c_int32, [S])
+        _sig(lib, "gs_hermite_set_step_timeout", c_int32, [S, c_double])
         _sig(lib, "gs_hermite_derivs_active_nn", c_int32, [S, PI, c_int32, c_int32, _PD, _PD,
                                                            _PD, PI])
         _sig(lib, "gs_group_step", c_int32, [POINTER(S), c_int32, c_int32])

@@ -200,6 +200,40 @@ def layout(n: int, rank: int = 0, nranks: int = 1, chunk: int = 0, sym: bool = F
                   n_chunks=(n + c - 1) // c, rank=rank, nranks=nranks)
 
 
+HERMITE_UNIT = 1024  # rows per ownership unit of a multi-rank Hermite run (256 x the widest
+                     # lane tile: a slice is whole i-blocks for every ipl)
+
+
+def hermite_partition(n: int, chunk: int, nranks: int, rank: int) -> tuple[int, int]:
+    """(first row, rows) of one rank of a Hermite run (layout.cpp gs_hermite_partition):
+    n_pad = n rounded up to the chunk, in units of 1024 rows dealt out contiguously by mpi.c's
+    remainder rule (the first `units mod nranks` ranks hold one more)."""
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    c = chunk or auto_chunk(n)
+    if c % 1024:
+        raise ValueError("chunk must be a multiple of 1024")
+    if nranks < 1 or not 0 <= rank < nranks:
+        raise ValueError("bad rank/nranks")
+    units = round_up(n, c) // HERMITE_UNIT
+    if nranks > units:
+        raise ValueError(f"hermite: {nranks} ranks but only {units} unit(s) of 1024 rows")
+    start, count = mpi_block(units, rank, nranks)
+    return start * HERMITE_UNIT, count * HERMITE_UNIT
+
+
+def hermite_layout(n: int, rank: int = 0, nranks: int = 1, chunk: int = 0) -> Layout:
+    """The layout of one rank of a Hermite run: n_pad does not depend on the rank count, and
+    every rank must own at least one body."""
+    begin, rows = hermite_partition(n, chunk, nranks, rank)
+    if hermite_partition(n, chunk, nranks, nranks - 1)[0] >= n:
+        raise ValueError(f"hermite runs on one rank at n={n} with {nranks} ranks asked for: "
+                         "every rank needs a unit of 1024 rows that holds a body")
+    c = chunk or auto_chunk(n)
+    return Layout(n=n, n_pad=round_up(n, c), n_local=rows, local_begin=begin, chunk=c,
+                  n_chunks=(n + c - 1) // c, rank=rank, nranks=nranks)
+
+
 def mpi_block(n: int, rank: int, nranks: int) -> tuple[int, int]:
     """The reference's remainder-spread block (start, count) of mpi.c:184-187 (for parity docs)."""
     base, rem = divmod(n, nranks)

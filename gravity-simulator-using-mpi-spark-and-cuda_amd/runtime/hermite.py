@@ -1,4 +1,4 @@
-"""Engines of the 4th-order Hermite integrator (Makino & Aarseth 1992), one rank.
+"""Engines of the 4th-order Hermite integrator (Makino & Aarseth 1992).
 
 The same interface as the engines of runtime/engines.py (load / init_ics / step / sync / state /
 accel / nonfinite / steps_done / close) plus status(): the integrator carries x, v, a, j, t and
@@ -6,6 +6,13 @@ the next step size, so the time reached is the engine's, not step * dt.
 
 * HermiteHipEngine: the native gs_hermite object (csrc/hip/hermite.hip): device-resident state,
   the acceleration+jerk kernel of csrc/hip/nbody_hermite.hip, the step size chosen on the device.
+  With nranks > 1 (shared steps only) a rank owns whole units of 1024 rows
+  (parallel/partition.py hermite_partition), predicts, evaluates and corrects them against all j
+  and gathers the predicted rows and the step minima over RCCL every step (comm_init); every
+  rank then holds the same time and step size, state() / carried() / derivs() return all n rows
+  on every rank (collectives), and the run equals the one-rank run bit for bit.
+* HermiteVirtualGroup: the P shards of such a run in one process on one device, the gathers done
+  by device copies (gs_hermite_group_*): the same kernels and schedule without RCCL.
 * HermiteCpuEngine: the native C++/OpenMP step (csrc/cpu/cpu_engine.cpp gs_cpu_hermite_step_*).
 
 dtype "mixed": both engines hold x, v, a, j in fp64 and predict, correct and choose steps in fp64;
@@ -36,7 +43,7 @@ import numpy as np
 from ..config import SimConfig
 from ..models.initial_conditions import DEVICE_IC_IDS, BodySet, make
 from ..ops import _native
-from ..parallel.partition import Layout, layout as make_layout
+from ..parallel.partition import Layout, hermite_layout, layout as make_layout
 
 
 @dataclass
@@ -69,30 +76,35 @@ def _i32ptr(a):
 
 def _require_one_rank(nranks: int) -> None:
     if nranks != 1:
-        raise ValueError("hermite runs on one rank")
+        raise ValueError("hermite runs on one rank on the CPU (--device cpu)")
 
 
 class HermiteHipEngine:
-    """GPU engine: one native gs_hermite per process."""
+    """GPU engine: one native gs_hermite per process (rank `rank` of `nranks`)."""
 
     kind = "gpu"
+    gathers_all = True  # state(), carried() and derivs() return every rank's rows
 
-    def __init__(self, cfg: SimConfig, rank: int = 0, nranks: int = 1, device: int = 0):
-        _require_one_rank(nranks)
+    def __init__(self, cfg: SimConfig, rank: int = 0, nranks: int = 1, device: int = 0,
+                 dist=None):
         from .engines import _gs_config
 
+        if nranks > 1:  # (the refusals of SimConfig.validate for a run launched with P ranks)
+            cfg.replace(gpus=nranks, device="gpu").validate()
         self.cfg = cfg
-        self.rank, self.nranks, self.device = 0, 1, device
+        self.rank, self.nranks, self.device, self.dist = rank, nranks, device, dist
+        self.layout: Layout = hermite_layout(cfg.n, rank, nranks, cfg.chunk)
+        self.step_timeout_s = 0.0
         self.lib = _native.hip_lib()
-        c = _gs_config(cfg.replace(kernel="auto", mode="auto"), 0, 1, device)
+        c = _gs_config(cfg.replace(kernel="auto", mode="auto"), rank, nranks, device)
         self._h = ctypes.c_void_p()
         _native.check(self.lib, self.lib.gs_hermite_create(ctypes.byref(c), ctypes.byref(self._h)),
                       "gs_hermite_create")
         L = _native.GsLayout()
         _native.check(self.lib, self.lib.gs_hermite_layout(self._h, ctypes.byref(L)), "layout")
         self.native_layout = L.as_dict()
-        self.layout: Layout = make_layout(cfg.n, 0, 1, L.chunk)
-        assert self.layout.n_pad == L.n_pad, "Python layout mirror disagrees with native"
+        assert (self.layout.n_pad, self.layout.local_begin, self.layout.n_local) == \
+            (L.n_pad, L.local_begin, L.n_local), "Python layout mirror disagrees with native"
         _native.check(self.lib, self.lib.gs_hermite_set_adaptive(
             self._h, float(cfg.eta), float(cfg.dt),
             -1.0 if cfg.t_end is None else float(cfg.t_end)), "set_adaptive")
@@ -215,14 +227,42 @@ class HermiteHipEngine:
                 None if lev is None else lev.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
                 "set_block_state")
 
+    def comm_init(self, uid: bytes) -> None:
+        """Form the RCCL communicator of a multi-rank run (collective; before the state)."""
+        buf = ctypes.create_string_buffer(uid, 128)
+        self._comm = "in comm_init"
+        _native.check(self.lib, self.lib.gs_hermite_comm_init(self._h, buf, self.rank,
+                                                              self.nranks), "comm_init")
+        self._comm = "done"
+
+    def comm_info(self) -> dict:
+        """What RCCL formed for this rank (as HipEngine.comm_info): rccl_nranks 0 when no
+        communicator is held."""
+        c, r, d = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _native.check(self.lib, self.lib.gs_hermite_comm_info(
+            self._h, ctypes.byref(c), ctypes.byref(r), ctypes.byref(d)), "comm info")
+        return {"rccl_nranks": c.value, "rccl_rank": r.value, "rccl_device": d.value}
+
+    def comm_check(self) -> None:
+        _native.check(self.lib, self.lib.gs_hermite_comm_check(self._h), "rccl health")
+
+    def set_step_timeout(self, seconds: float) -> None:
+        """sync() aborts the communicator when no step completes for this long (0: unbounded)."""
+        self.step_timeout_s = float(seconds)
+        _native.check(self.lib, self.lib.gs_hermite_set_step_timeout(self._h, float(seconds)),
+                      "set_step_timeout")
+
+    _comm = "not started"
+
     def abort(self) -> bool:
-        """The run guard's abort hook: one rank holds no communicator whose collectives could
-        hang, so there is nothing to abort (the guard's stage deadline still ends the job)."""
-        return False
+        """The run guard's abort hook: ncclCommAbort the live communicator once (True if one was
+        aborted). One rank holds none, so there is nothing to abort (the guard's stage deadline
+        still ends the job)."""
+        return self.nranks > 1 and bool(self._h) and bool(self.lib.gs_hermite_abort(self._h))
 
     def comm_stage(self) -> str:
-        """The run guard's probe (HipEngine.comm_stage): no communicator is ever formed."""
-        return "no communicator (one rank)"
+        """The run guard's probe (HipEngine.comm_stage)."""
+        return self._comm if self.nranks > 1 else "no communicator (one rank)"
 
     def step(self, n: int) -> None:
         if n > 0:
@@ -287,9 +327,11 @@ class HermiteHipEngine:
         return ms.value
 
     def accel(self, step_path: bool = False) -> np.ndarray:
-        """(n_local, 4) = (ax, ay, az, phi), ghost rows zero."""
+        """(n_local, 4) = (ax, ay, az, phi) of the rows this rank owns, ghost rows zero
+        (collective when nranks > 1)."""
         out = np.zeros((self.layout.n_local, 4))
-        out[: self.cfg.n] = self.derivs()[0]
+        rows = self.layout.real_local
+        out[: len(rows)] = self.derivs()[0][rows.start:rows.stop]
         return out
 
     def nonfinite(self) -> int:
@@ -312,6 +354,105 @@ class HermiteHipEngine:
             self.close()
         except Exception:
             pass
+
+
+class HermiteVirtualGroup:
+    """The P ranks of a shared-step run as shards of one process on one device: every shard is
+    a HermiteHipEngine of rank r of P and runs the slice kernels and the control kernel of the
+    RCCL path; the gathers are device copies between the shards' arrays. The reads return all n
+    rows. For tests and for bench/hermite_rate.py --ranks."""
+
+    kind = "gpu"
+
+    def __init__(self, cfg: SimConfig, nranks: int, device: int = 0, order=None):
+        self.cfg, self.nranks = cfg, int(nranks)
+        self.shards: list[HermiteHipEngine] = []
+        try:
+            for r in range(self.nranks):
+                self.shards.append(HermiteHipEngine(cfg, r, self.nranks, device))
+        except Exception:
+            self.close()
+            raise
+        self.lib = self.shards[0].lib
+        # (order: a test passes the shards to the native group in another order)
+        idx = list(range(self.nranks)) if order is None else list(order)
+        self._arr = (ctypes.c_void_p * self.nranks)(*[self.shards[i]._h for i in idx])
+
+    @property
+    def layouts(self) -> list[Layout]:
+        return [e.layout for e in self.shards]
+
+    def _finish_start(self) -> None:
+        _native.check(self.lib, self.lib.gs_hermite_group_step(self._arr, self.nranks, 0),
+                      "group start")
+
+    def init_ics(self, family: str, seed: int) -> None:
+        for e in self.shards:
+            e.init_ics(family, seed)
+        self._finish_start()
+
+    def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
+             dt_next: Optional[float] = None, dt_min: Optional[float] = None) -> None:
+        for e in self.shards:
+            e.load(b, acc, jerk, t=t, dt_next=dt_next, dt_min=dt_min)
+        self._finish_start()
+
+    def step(self, n: int) -> None:
+        if n > 0:
+            _native.check(self.lib, self.lib.gs_hermite_group_step(self._arr, self.nranks, int(n)),
+                          "group step")
+
+    def sync(self, timeout_s: float = 0.0) -> None:
+        for e in self.shards:
+            e.sync()
+
+    def statuses(self) -> list[HermiteStatus]:
+        """Every shard's own control block (they are equal); waits for the enqueued steps."""
+        return [e.status() for e in self.shards]
+
+    def status(self) -> HermiteStatus:
+        return self.shards[0].status()
+
+    def _get(self, want_deriv: bool):
+        n = self.cfg.n
+        pos, vel, mass = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+        acc = np.zeros((n, 3)) if want_deriv else None
+        jerk = np.zeros((n, 3)) if want_deriv else None
+        _native.check(self.lib, self.lib.gs_hermite_group_get_state(
+            self._arr, self.nranks, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
+            _native.dptr(acc) if want_deriv else None, _native.dptr(jerk) if want_deriv else None),
+            "group get_state")
+        return BodySet(pos, vel, mass), acc, jerk
+
+    def state(self) -> BodySet:
+        return self._get(False)[0]
+
+    def carried(self) -> tuple[np.ndarray, np.ndarray]:
+        _, a, j = self._get(True)
+        return a, j
+
+    def derivs(self) -> tuple[np.ndarray, np.ndarray]:
+        n = self.cfg.n
+        a4, j4 = np.zeros((n, 4)), np.zeros((n, 4))
+        _native.check(self.lib, self.lib.gs_hermite_group_derivs(
+            self._arr, self.nranks, _native.dptr(a4), _native.dptr(j4)), "group derivs")
+        return a4, j4
+
+    def time_eval(self, reps: int = 10) -> list[float]:
+        """Milliseconds per evaluate launch of each shard, one shard at a time."""
+        ms = np.zeros(self.nranks)
+        _native.check(self.lib, self.lib.gs_hermite_group_time_eval(
+            self._arr, self.nranks, int(reps), _native.dptr(ms)), "group time_eval")
+        return [float(x) for x in ms]
+
+    @property
+    def steps_done(self) -> int:
+        return self.status().steps
+
+    def close(self) -> None:
+        for e in self.shards:
+            e.close()
+        self.shards = []
 
 
 class HermiteCpuEngine:

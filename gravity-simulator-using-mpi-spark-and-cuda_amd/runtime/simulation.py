@@ -18,10 +18,15 @@ design:
   v_k = v_{k-1/2} + a(x_k) dt/2 on output — second-order (KDK) accuracy at no extra cost per
   step. Checkpoints keep the staggered velocities (meta "velocity": "half-step") so resume
   stays bit-exact;
-* integrator "hermite" (one rank) is the 4th-order predictor-corrector of runtime/hermite.py with
+* integrator "hermite" is the 4th-order predictor-corrector of runtime/hermite.py with
   its own acceleration+jerk kernel, a fixed step or a shared adaptive one (eta) and an optional
   end time (t_end); the engine carries the time, so metrics and checkpoints report its t, and a
   checkpoint keeps the carried a, j and the next step size so that resume stays bit-exact.
+  Shared steps run on P GPU ranks (runtime/hermite.py): every rank holds the same time and step
+  size and returns all rows from state() / carried() / derivs(), so checkpoints, dumps and the
+  conserved quantities are formed from the gathered rows in the one-rank order and are the
+  one-rank values bit for bit; a checkpoint resumes at any P. Block steps, collisions and the
+  CPU engine stay on one rank.
   With block_steps every body has its own step dt 2^-k and `steps` counts macro steps of dt, at
   which all bodies stand at the same time: all periodic work lands on synchronised states, and a
   checkpoint also keeps the levels.
@@ -64,15 +69,21 @@ def engine_conserved(engine, dist, step: int = 0, staggered: bool = False,
     p = sum m v and L = sum m x cross v; the sums are all-reduced. The reference has no such
     check (it only prints positions); it is the standard correctness gauge of an N-body
     integrator (bench.py reports the drift over its timed steps)."""
-    rows = engine.layout.real_local
+    # An engine whose reads return every rank's rows (multi-rank hermite): each rank forms the
+    # sums over all bodies in the one-rank order, and nothing is reduced.
+    whole = dist.world > 1 and getattr(engine, "gathers_all", False)
+    rows = range(engine.cfg.n) if whole else engine.layout.real_local
     b = engine.state()
     sl = slice(rows.start, rows.stop)
     m, x, v = b.mass[sl], b.pos[sl], b.vel[sl]
-    a4 = engine.accel()[: len(rows)] if len(rows) else np.zeros((0, 4))
+    if whole:
+        a4 = engine.derivs()[0]
+    else:
+        a4 = engine.accel()[: len(rows)] if len(rows) else np.zeros((0, 4))
     if staggered:
         v = v + 0.5 * dt * a4[:, :3]
     xv = np.cross(x, v) if len(rows) else np.zeros((0, 3))
-    red = lambda y: comm.allreduce_sum(dist, float(y))  # noqa: E731
+    red = float if whole else lambda y: comm.allreduce_sum(dist, float(y))  # noqa: E731
     ke = red(0.5 * (m * (v * v).sum(1)).sum())
     pe = red(0.5 * (m * a4[:, 3]).sum())
     return {"step": int(step), "kinetic": ke, "potential": pe, "energy": ke + pe,
@@ -101,10 +112,14 @@ class Simulation:
         self.cfg = cfg.validate()
         self.dist = dist or comm.env_info()
         self.hermite = cfg.integrator == "hermite"
-        if self.hermite and self.dist.world > 1:
-            raise ValueError("hermite runs on one rank")
         self.overlap_check: Optional[str] = None
         use_gpu = cfg.device == "gpu" or (cfg.device == "auto" and gpu_available())
+        if self.hermite and self.dist.world > 1:
+            # shared steps on GPU ranks; the refusals before any engine or collective
+            from ..parallel.partition import hermite_layout
+
+            cfg.replace(gpus=self.dist.world, device="gpu" if use_gpu else "cpu").validate()
+            hermite_layout(cfg.n, self.dist.rank, self.dist.world, cfg.chunk)
         if cfg.device == "gpu" and not gpu_available():
             raise RuntimeError("device=gpu requested but no HIP device / native library")
         d = self.dist
@@ -118,7 +133,8 @@ class Simulation:
             dev = d.local_rank % max(1, torch.cuda.device_count())
             stage("engine", INIT_TIMEOUT_S)
             self._hermite_engine = lambda c: HermiteHipEngine(c, device=dev)
-            self.engine = (HermiteHipEngine(ecfg, device=dev) if self.hermite else
+            self.engine = (HermiteHipEngine(ecfg, d.rank, d.world, device=dev, dist=d)
+                           if self.hermite else
                            HipEngine(cfg, d.rank, d.world, device=dev, dist=d))
             if guard:
                 guard.on_abort(self.engine.abort)
@@ -128,12 +144,20 @@ class Simulation:
                 uid = HipEngine.unique_id() if d.is_root else None
                 uid = comm.broadcast_bytes(d, uid)
                 self.engine.comm_init(uid)
-                stage("self_check", INIT_TIMEOUT_S)
-                per_step = self._self_check()
-                if cfg.step_timeout_s is None:
+                if self.hermite:
+                    # (no start-up probe: a shared adaptive step has no fixed cost; the bound is
+                    # the configured one, or the floor of the derived one)
                     from ..parallel.guard import step_timeout
 
-                    self.engine.set_step_timeout(step_timeout(per_step))
+                    self.engine.set_step_timeout(step_timeout(0.0) if cfg.step_timeout_s is None
+                                                 else cfg.step_timeout_s)
+                else:
+                    stage("self_check", INIT_TIMEOUT_S)
+                    per_step = self._self_check()
+                    if cfg.step_timeout_s is None:
+                        from ..parallel.guard import step_timeout
+
+                        self.engine.set_step_timeout(step_timeout(per_step))
             stage("ics", INIT_TIMEOUT_S)
         else:
             # CPU engine (gloo for P > 1): no RCCL to hang on, and set-up includes O(N^2) work
@@ -286,6 +310,8 @@ class Simulation:
 
     def _own_accel(self) -> np.ndarray:
         """(n, 3) accelerations with this rank's rows filled (others zero)."""
+        if self.hermite and self.dist.world > 1:  # (its reads return every rank's rows)
+            return self.engine.derivs()[0][:, :3].copy()
         L = self.engine.layout
         acc = np.zeros((self.cfg.n, 3))
         rows = L.real_local
@@ -306,7 +332,7 @@ class Simulation:
     def raw_state(self) -> BodySet:
         """Full (pos, vel as stored, mass) on every rank (collective when P > 1)."""
         b = self.engine.state()
-        if self.dist.world > 1:
+        if self.dist.world > 1 and not self.hermite:  # (hermite: state() gathered all rows)
             rows = self.engine.layout.real_local
             comm.gather_rows_to_root(self.dist, b.vel, slice(rows.start, rows.stop))
         return b
@@ -316,7 +342,7 @@ class Simulation:
         b = self.raw_state()
         if self.staggered:
             acc = self._own_accel()
-            if self.dist.world > 1:
+            if self.dist.world > 1 and not self.hermite:
                 comm.gather_rows_to_root(self.dist, acc, slice(self.engine.layout.real_local.start,
                                                                self.engine.layout.real_local.stop))
             b.vel = b.vel + 0.5 * self.cfg.dt * acc
@@ -332,11 +358,13 @@ class Simulation:
         if bad:
             raise NonFiniteError(f"{int(bad)} non-finite position/velocity components at step "
                                  f"{self.step}")
-        if isinstance(self.engine, HipEngine) and self.dist.world > 1:
+        if isinstance(self.engine, (HipEngine, HermiteHipEngine)) and self.dist.world > 1:
             self.engine.comm_check()
 
     def save_checkpoint(self, path: Optional[str] = None) -> Optional[str]:
         b = self.raw_state()
+        # (hermite on P ranks: the carried a, j are gathered by every rank, the root writes)
+        carried = self.engine.carried() if self.hermite else None
         if not self.dist.is_root:
             return None
         cfg = self.cfg
@@ -348,7 +376,7 @@ class Simulation:
         extra = None
         if self.hermite:
             st = self.engine.status()
-            acc, jerk = self.engine.carried()
+            acc, jerk = carried
             extra = {"acc": acc, "jerk": jerk}
             fin = lambda y: y if np.isfinite(y) else None  # noqa: E731
             meta.update(time=st.time, dt_next=fin(st.dt_next), dt_min=fin(st.dt_min),
