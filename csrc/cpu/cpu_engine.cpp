@@ -498,6 +498,76 @@ int nn_rows_mixed(const double* X4, const double* R, int64_t n_real, const int32
   return 0;
 }
 
+// ---- k nearest neighbours (nbody_knn.hip) -----------------------------------------------------
+// The first k of the ascending order on (r^2, j) over the real j != i: r^2 = fma(dz, dz,
+// fma(dy, dy, dx dx)) of d = x_j - x_i (MIXED: (h_j - h_i) + (l_j - l_i)), no softening, no
+// cutoff. A sweep in ascending j with a strict less keeps the lower j on a tie, which is the
+// lexicographic order. (+inf, -1) past the neighbours there are.
+constexpr int kKnnMax = 8;
+
+template <typename T, bool MIXED, typename O>
+inline void knn_one(const T* X4, const T* L4, int64_t n_real, int64_t i, int32_t k, O* r2,
+                    int32_t* idx) {
+  const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
+  T r[kKnnMax];
+  int32_t n[kKnnMax];
+  for (int s = 0; s < kKnnMax; ++s) {
+    r[s] = std::numeric_limits<T>::infinity();
+    n[s] = -1;
+  }
+  for (int64_t j = 0; j < n_real; ++j) {
+    T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+    if (MIXED) {
+      dx = dx + (L4[4 * j] - L4[4 * i]);
+      dy = dy + (L4[4 * j + 1] - L4[4 * i + 1]);
+      dz = dz + (L4[4 * j + 2] - L4[4 * i + 2]);
+    }
+    const T c = std::fma(dz, dz, std::fma(dy, dy, dx * dx));
+    if (j == i || !(c < r[k - 1])) continue;  // (slots from k on never reach the output)
+    int s = k - 1;
+    for (; s > 0 && c < r[s - 1]; --s) {
+      r[s] = r[s - 1];
+      n[s] = n[s - 1];
+    }
+    r[s] = c;
+    n[s] = (int32_t)j;
+  }
+  for (int s = 0; s < k; ++s) {
+    r2[s] = (O)r[s];
+    idx[s] = n[s];
+  }
+}
+
+inline bool knn_args_ok(const void* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                        const void* r2, const void* idx) {
+  if (X4 && r2 && idx && n_real >= 1 && n_real <= INT32_MAX && i0 >= 0 && i1 >= i0 &&
+      i1 <= n_real && k >= 1 && k <= kKnnMax)
+    return true;
+  gs_set_error("cpu_knn: bad arguments (n >= 1, rows within [0, n], k in 1..8)");
+  return false;
+}
+
+template <typename T>
+int knn_rows(const T* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, T* r2,
+             int32_t* idx) {
+  if (!knn_args_ok(X4, n_real, i0, i1, k, r2, idx)) return -1;
+#pragma omp parallel for schedule(static)
+  for (int64_t i = i0; i < i1; ++i)
+    knn_one<T, false, T>(X4, nullptr, n_real, i, k, r2 + (i - i0) * k, idx + (i - i0) * k);
+  return 0;
+}
+
+int knn_rows_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                   double* r2, int32_t* idx) {
+  if (!knn_args_ok(X4, n_real, i0, i1, k, r2, idx)) return -1;
+  const MixedRows r(X4, X4, n_real);  // (the velocity rows are not used)
+#pragma omp parallel for schedule(static)
+  for (int64_t i = i0; i < i1; ++i)
+    knn_one<float, true, double>(r.H.data(), r.L.data(), n_real, i, k, r2 + (i - i0) * k,
+                                 idx + (i - i0) * k);
+  return 0;
+}
+
 inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
 
 template <typename T>
@@ -647,6 +717,18 @@ int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const
                         int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
   if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
   return nn_rows_mixed(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_knn_f64(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                   double* r2, int32_t* idx) {
+  return knn_rows<double>(X4, n_real, i0, i1, k, r2, idx);
+}
+int gs_cpu_knn_f32(const float* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, float* r2,
+                   int32_t* idx) {
+  return knn_rows<float>(X4, n_real, i0, i1, k, r2, idx);
+}
+int gs_cpu_knn_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                     double* r2, int32_t* idx) {
+  return knn_rows_mixed(X4, n_real, i0, i1, k, r2, idx);
 }
 int gs_cpu_accjerk_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0,
                          int64_t i1, int32_t chunk, double cut2, double eps2, double* acc4,

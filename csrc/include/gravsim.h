@@ -219,6 +219,17 @@ int gs_cpu_nn_idx_f32(const float* X4, const float* R, int64_t n_real, const int
                       int64_t n_idx, float cut2, float eps2, float* q, int32_t* nn);
 int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
                         int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn);
+// k nearest neighbours of bodies [i0, i1) by distance (the definition of the k-nearest section
+// below), with the arithmetic of the GPU kernel (explicit fma), so that the lists are bit-equal
+// to gs_hip_knn's. X4: n_real rows of 4 (the fourth component is not read); k in 1..8; row r of
+// r2 / idx (k entries each, ascending) belongs to body i0 + r. mixed: X4 fp64, the separation
+// from the double-single rows of gs_cpu_accjerk_mixed, r2 widened to fp64.
+int gs_cpu_knn_f64(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                   double* r2, int32_t* idx);
+int gs_cpu_knn_f32(const float* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, float* r2,
+                   int32_t* idx);
+int gs_cpu_knn_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                     double* r2, int32_t* idx);
 int gs_cpu_num_threads(void);
 int gs_cpu_set_threads(int32_t n);  // OpenMP threads for the CPU engine (returns the new max)
 
@@ -425,6 +436,28 @@ int gs_hermite_clear_overlap(gs_hermite* h);  // overlaps <- 0: a stopped run st
 int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn);
 int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                                 double* acc4, double* jerk4, double* q, int32_t* nn);
+
+// ---------------------------------------------------------------- k nearest neighbours
+// (nbody_knn.hip; the Casertano & Hut local density and the cluster read-outs rest on it.)
+// The k nearest neighbours of body i are the first k entries of the ascending lexicographic
+// order on (r^2_ij, j) over the real bodies j != i: the body itself is left out by index, not by
+// distance (another body at the same position is a neighbour at r^2 = 0). r^2 is formed in the
+// pair type, d = x_j - x_i per component (GS_MIXED: (hi_j - hi_i) + (lo_j - lo_i) on the
+// double-single rows), r^2 = fma(dz, dz, fma(dy, dy, dx dx)); no softening, no cutoff. Entries
+// past the n - 1 neighbours there are read (+inf, -1). The order is total: every launch shape
+// (ipl, groups) gives the same bits, and they are the bits of gs_cpu_knn_*.
+// gs_hip_knn is stateless: pos n*3 fp64 (rounded to the pair type as the engines do), k in 1..8,
+// ipl 0 auto / 1 / 2, groups (chunk groups of the grid) 0 auto; r2 n*k doubles ascending, idx n*k.
+// It pads, uploads, launches, merges, downloads and frees on a stream of its own, restores the
+// caller's device and leaves no device state behind, so it may run beside a live engine.
+int gs_hip_knn(const double* pos, int64_t n, int32_t dtype, int32_t k, int32_t ipl,
+               int32_t groups, int32_t device, double* r2, int32_t* idx);
+// The same pass `reps` times, nothing downloaded: ms[r] gets the milliseconds of launch + merge
+// r between two events (bench/knn_rate.py); info4 (may be NULL): n_pad, ipl, groups, chunk.
+int gs_hip_knn_time(const double* pos, int64_t n, int32_t dtype, int32_t k, int32_t ipl,
+                    int32_t groups, int32_t device, int32_t reps, double* ms, int64_t* info4);
+int32_t gs_knn_ipl_ok(int32_t dtype, int32_t ipl);  // 1 if that form is compiled (0: auto)
+int32_t gs_knn_early_out(void);  // 1 if the insertion chain sits behind the wave-uniform test
 
 // Virtual ranks on one device: shards[r] created with rank r of P; steps all of them in
 // lockstep with the all-gather done by device copies (the RCCL schedule without RCCL).

@@ -26,6 +26,10 @@ def __getattr__(name):  # lazy: keep `import gravsim` light (no torch / native l
         from . import api
 
         return getattr(api, name)
+    if name in ("k_nearest", "cluster_structure"):
+        from .ops import neighbours
+
+        return getattr(neighbours, name)
     if name == "Simulation":
         from .runtime.simulation import Simulation
 
@@ -34,4 +38,5 @@ def __getattr__(name):  # lazy: keep `import gravsim` light (no torch / native l
 
 
 __all__ = ["SimConfig", "G_SI", "Simulation", "GravitySimulator", "SparkGravitySimulator",
-           "Particle", "create_solar_system", "generate_random_particles", "__version__"]
+           "Particle", "create_solar_system", "generate_random_particles", "k_nearest",
+           "cluster_structure", "__version__"]

@@ -123,6 +123,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--diag-every", type=int, default=0,
                    help="also sample them every k steps (implies --diagnostics; each sample is "
                         "an O(N^2) pass, excluded from the timed wall)")
+    p.add_argument("--structure", action="store_true",
+                   help="cluster structure by Casertano & Hut (1985) from every body's k nearest "
+                        "neighbours: density centre, core radius, central density and the 10 / 50 "
+                        "/ 90 %% Lagrangian radii at the start and end of the run, in the metrics "
+                        "JSON (`structure`)")
+    p.add_argument("--structure-every", dest="structure_every", type=int, default=0,
+                   help="also sample them every k steps (implies --structure; macro steps of a "
+                        "block-step run; each sample is an O(N^2) pass on the engine's device, "
+                        "excluded from the timed wall)")
+    p.add_argument("--structure-k", dest="structure_k", type=int, default=d.structure_k,
+                   help="neighbours of the local density (2..8)")
     p.add_argument("--quiet", action="store_true")
     return p
 
@@ -153,7 +164,10 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
                      nan_check_every=a.nan_check_every, metrics_json=a.metrics_json,
                      phase_timing=a.phase_timing,
                      diagnostics=a.diagnostics or a.diag_every > 0,
-                     diag_every=a.diag_every, gpus=a.nproc).validate()
+                     diag_every=a.diag_every,
+                     structure=a.structure or a.structure_every > 0,
+                     structure_every=a.structure_every, structure_k=a.structure_k,
+                     gpus=a.nproc).validate()
 
 
 def run_one(cfg: SimConfig, dist, log, quiet: bool = False, final: bool = True,

@@ -85,6 +85,11 @@ class SimConfig:
     diagnostics: bool = False         # total energy, momentum, angular momentum at the start and
                                       # the end of the run (exact-cutoff potential, O(N^2) pass)
     diag_every: int = 0               # ... and every k steps (the passes are excluded from wall)
+    structure: bool = False           # cluster structure (density centre, core radius, central
+                                      # density, Lagrangian radii; Casertano & Hut 1985) at the
+                                      # start and the end of the run, in the metrics JSON
+    structure_every: int = 0          # ... and every k steps (0 = start and end only)
+    structure_k: int = 6              # neighbours of the local density (2..8)
     metrics_json: Optional[str] = None
     phase_timing: bool = False        # GPU: per-step phase events (comm/compute split in the
                                       # metrics; eager steps, no graph replay)
@@ -172,6 +177,10 @@ class SimConfig:
             raise ValueError("overlap must be -1 (default), 0 or 3")
         if self.diag_every < 0:
             raise ValueError("diag_every must be >= 0")
+        if self.structure_every < 0:
+            raise ValueError("structure_every must be >= 0")
+        if not 2 <= self.structure_k <= 8:
+            raise ValueError("structure_k must be in 2..8")
         if self.step_timeout_s is not None and self.step_timeout_s < 0:
             raise ValueError("step_timeout_s must be None (derived), or >= 0 (0 = unbounded)")
         if self.cutoff < 0 or self.softening < 0:

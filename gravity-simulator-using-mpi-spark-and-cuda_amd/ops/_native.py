@@ -69,6 +69,7 @@ MODE_NAMES = {v: k for k, v in MODE_IDS.items()}
 _P = c_void_p
 _PD = POINTER(c_double)
 _PF = POINTER(c_float)
+PI32 = POINTER(c_int32)
 
 
 def _build(which: str) -> None:
@@ -160,6 +161,10 @@ def cpu_lib():
              [_PD, _PD, c_int64, c_int64, c_int64, D, D, _PD, POINTER(c_int32)])
         _sig(lib, "gs_cpu_nn_idx_mixed", c_int32,
              [_PD, _PD, c_int64, POINTER(c_int32), c_int64, D, D, _PD, POINTER(c_int32)])
+        _sig(lib, "gs_cpu_knn_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_int32, _PD, PI32])
+        _sig(lib, "gs_cpu_knn_f32", c_int32, [_PF, c_int64, c_int64, c_int64, c_int32, _PF, PI32])
+        _sig(lib, "gs_cpu_knn_mixed", c_int32, [_PD, c_int64, c_int64, c_int64, c_int32, _PD,
+                                                PI32])
         _sig(lib, "gs_cpu_hermite_step_mixed", c_int32,
              [_PD, _PD, _PD, _PD, _PD, c_int64, c_int32, D, D, D, D, _PD])
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -267,6 +272,12 @@ def hip_lib():
         _sig(lib, "gs_hermite_set_step_timeout", c_int32, [S, c_double])
         _sig(lib, "gs_hermite_derivs_active_nn", c_int32, [S, PI, c_int32, c_int32, _PD, _PD,
                                                            _PD, PI])
+        _sig(lib, "gs_hip_knn", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, _PD, PI32])
+        _sig(lib, "gs_hip_knn_time", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                               c_int32, c_int32, _PD, POINTER(c_int64)])
+        _sig(lib, "gs_knn_ipl_ok", c_int32, [c_int32, c_int32])
+        _sig(lib, "gs_knn_early_out", c_int32, [])
         _sig(lib, "gs_group_step", c_int32, [POINTER(S), c_int32, c_int32])
         _sig(lib, "gs_rccl_unique_id", c_int32, [c_void_p])
         _sig(lib, "gs_stepper_comm_init", c_int32, [S, c_void_p, c_int32, c_int32])

@@ -148,6 +148,88 @@ def acc_jerk(pos, vel, mass, G: float = G_SI, cutoff: float = 1e-10, softening: 
     return out
 
 
+# ---- k nearest neighbours, local density and cluster structure -------------------------------
+def k_nearest(pos, k: int = 6, block: int = 256):
+    """The k nearest neighbours of every body in fp64: (r2 (n, k), idx (n, k) int32), the first k
+    entries of the ascending lexicographic order on (r^2_ij, j) over j != i. The body itself is
+    left out by index, not by distance: another body at the same position is a neighbour at
+    r^2 = 0. No softening, no cutoff. Entries past the n - 1 neighbours there are: (+inf, -1)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    n, k = pos.shape[0], int(k)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    r2 = np.full((n, k), np.inf)
+    idx = np.full((n, k), -1, dtype=np.int32)
+    m = min(k, n - 1)
+    jj = np.arange(n)
+    for b0 in range(0, n if m > 0 else 0, block):
+        rows = np.arange(b0, min(b0 + block, n))
+        d = pos[None, :, :] - pos[rows, None, :]
+        rr = (d * d).sum(-1)
+        rr[np.arange(len(rows)), rows] = np.inf  # (after every real pair, whatever its j)
+        order = np.lexsort((np.broadcast_to(jj, rr.shape), rr), axis=1)[:, :m]
+        r2[rows, :m] = np.take_along_axis(rr, order, 1)
+        idx[rows, :m] = order
+    return r2, idx
+
+
+def density_from_lists(r2, idx, mass, k: int = 6):
+    """Casertano & Hut (1985) local density from k-nearest lists (at least k columns):
+    rho_i = (sum of the masses of the k - 1 nearest) / (4/3 pi r_k^3), r_k the k-th distance.
+    Returns (rho (n,), degenerate (n,) bool): a body with r_k = 0 or fewer than k neighbours has
+    no density (rho 0, flagged)."""
+    r2, idx = np.asarray(r2, dtype=np.float64), np.asarray(idx)
+    mass, k = np.asarray(mass, dtype=np.float64), int(k)
+    if k < 2 or r2.shape[1] < k:
+        raise ValueError("the local density needs k >= 2 and lists of at least k columns")
+    rk2 = r2[:, k - 1]
+    bad = (idx[:, k - 1] < 0) | ~np.isfinite(rk2) | (rk2 <= 0)
+    inner = np.where(idx[:, :k - 1] >= 0, mass[np.clip(idx[:, :k - 1], 0, None)], 0.0).sum(1)
+    rk = np.sqrt(np.where(bad, 1.0, rk2))
+    rho = np.where(bad, 0.0, inner / (4.0 / 3.0 * np.pi * rk ** 3))
+    return rho, bad
+
+
+def local_density(pos, mass, k: int = 6):
+    """rho_i of density_from_lists on the fp64 lists of k_nearest (nan where undefined)."""
+    rho, bad = density_from_lists(*k_nearest(pos, k), mass, k)
+    return np.where(bad, np.nan, rho)
+
+
+def cluster_structure(pos, mass, k: int = 6, fractions=(0.1, 0.5, 0.9), lists=None):
+    """Structure read-outs of a cluster (Casertano & Hut 1985), all fp64:
+      density_centre    x_d = sum rho_i x_i / sum rho_i
+      core_radius       sqrt(sum rho_i^2 |x_i - x_d|^2 / sum rho_i^2)
+      density_max       max rho_i
+      lagrangian_radii  per fraction f, the radius about x_d of the first body (by radius) at
+                        which the cumulative mass fraction reaches f
+      degenerate        bodies without a density (r_k = 0, or fewer than k neighbours): left
+                        out of the weighted sums (not of the cumulative mass)
+    lists: (r2, idx) of k_nearest from another device (default: the oracle's own). When no body
+    has a density the centre is the centre of mass and core_radius, density_max are 0."""
+    pos = np.asarray(pos, dtype=np.float64)
+    mass = np.asarray(mass, dtype=np.float64)
+    r2, idx = k_nearest(pos, k) if lists is None else lists
+    rho, bad = density_from_lists(r2, idx, mass, k)
+    w = rho.sum()
+    if w > 0:
+        xd = (rho[:, None] * pos).sum(0) / w
+    else:
+        xd = (mass[:, None] * pos).sum(0) / mass.sum() if mass.sum() > 0 else pos.mean(0)
+    rad2 = ((pos - xd) ** 2).sum(1)
+    w2 = (rho * rho).sum()
+    order = np.argsort(rad2, kind="stable")
+    cum = np.cumsum(mass[order])
+    lag = []
+    for f in fractions:
+        at = int(np.searchsorted(cum, f * cum[-1], side="left")) if cum[-1] > 0 else 0
+        lag.append(float(np.sqrt(rad2[order[min(at, len(order) - 1)]])))
+    return {"density_centre": [float(c) for c in xd],
+            "core_radius": float(np.sqrt((rho * rho * rad2).sum() / w2)) if w2 > 0 else 0.0,
+            "density_max": float(rho.max()) if len(rho) else 0.0,
+            "lagrangian_radii": lag, "degenerate": int(bad.sum())}
+
+
 # ---- nearest neighbours, overlaps and mergers ------------------------------------------------
 def nearest_neighbours(pos, radius, cutoff: float = 1e-10, softening: float = 0.0, rows=None,
                        block: int = 256, second: bool = False):

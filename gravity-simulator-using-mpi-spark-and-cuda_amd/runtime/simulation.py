@@ -11,6 +11,9 @@ design:
   checks run at a configurable period;
 * optional conserved-quantity diagnostics (--diagnostics / --diag-every): total energy with
   the exact-cutoff potential, linear and angular momentum, and their relative drift;
+* optional cluster-structure read-outs (--structure / --structure-every): density centre, core
+  radius, central density and Lagrangian radii from the k-nearest-neighbour lists of the state
+  (ops/neighbours.py), on the engine's device in the run's dtype, outside the timed wall;
 * checkpoints are rank-agnostic and a resumed run continues bit-exactly;
 * integrator "kd" is the reference's kick-drift update (cuda.cu:73-76, mpi.c:207-215);
   "leapfrog" runs the very same per-step kernel on velocities staggered by half a step
@@ -353,6 +356,22 @@ class Simulation:
         see engine_conserved."""
         return engine_conserved(self.engine, self.dist, self.step, self.staggered, self.cfg.dt)
 
+    def structure(self, step: Optional[int] = None) -> Optional[dict]:
+        """One cluster-structure sample of the current state (the bodies left after mergers):
+        the k-nearest lists from the engine's device in the run's dtype, the rest on the host
+        (ops/neighbours.py). Every rank reads the state as it does for a dump; rank 0 alone
+        computes and returns the sample (the others None)."""
+        from ..ops import neighbours
+
+        b = self.engine.state()
+        if not self.dist.is_root:
+            return None
+        t = self.engine.status().time if self.hermite else self.step * self.cfg.dt
+        kw = {"gpu": self.engine.device} if self.engine.kind == "gpu" else {}
+        out = neighbours.cluster_structure(b.pos, b.mass, self.cfg.structure_k,
+                                           device=self.engine.kind, dtype=self.cfg.dtype, **kw)
+        return {"step": int(self.step if step is None else step), "time": float(t), **out}
+
     def check_finite(self) -> None:
         bad = comm.allreduce_sum(self.dist, self.engine.nonfinite())
         if bad:
@@ -398,11 +417,14 @@ class Simulation:
         steps = cfg.steps if steps is None else int(steps)
         periods = [p for p in (cfg.progress_every if log else 0, cfg.checkpoint_every,
                                cfg.record_every, cfg.nan_check_every, cfg.dump_every,
-                               cfg.diag_every)
+                               cfg.diag_every, cfg.structure_every if cfg.structure else 0)
                    if p and p > 0]
         gpu = isinstance(self.engine, HipEngine)
         c0 = self.conserved() if cfg.diagnostics else None
         samples, diag_s = [], 0.0
+        # structure samples: the start, every structure_every steps (macro steps of a block-step
+        # run) short of the last, and the end; none inside the timed wall
+        struct = [self.structure()] if cfg.structure else []
         timing = cfg.phase_timing and gpu
         if timing:
             self.engine.set_timing(True)
@@ -460,6 +482,12 @@ class Simulation:
                 td = time.perf_counter()
                 samples.append(self.conserved())
                 diag_s += time.perf_counter() - td  # ... the O(N^2) sample does not
+            if cfg.structure and cfg.structure_every and s % cfg.structure_every == 0 and \
+                    s < steps and not finished:
+                self.engine.sync()
+                td = time.perf_counter()
+                struct.append(self.structure())
+                diag_s += time.perf_counter() - td
         self.engine.sync()
         wall = time.perf_counter() - t0 - diag_s
         wall = comm.allreduce_max(self.dist, wall)
@@ -491,6 +519,8 @@ class Simulation:
                          step_timeout_s=self.engine.step_timeout_s or None)
         if c0 is not None:
             extra["conservation"] = conservation_summary(c0, self.conserved(), samples)
+        if cfg.structure:
+            struct.append(self.structure())
         lay = getattr(self.engine, "native_layout", {})
         from ..ops._native import KERNEL_NAMES, MODE_NAMES
 
@@ -520,7 +550,9 @@ class Simulation:
         return RunMetrics(n=cfg.n, steps=steps, dt=cfg.dt, dtype=cfg.dtype, device=self.device,
                           nranks=self.dist.world, wall_s=wall,
                           kernel=KERNEL_NAMES.get(lay.get("kernel", 0), "cpu"),
-                          mode=MODE_NAMES.get(lay.get("mode", 0), "cpu"), extra=extra, **herm)
+                          mode=MODE_NAMES.get(lay.get("mode", 0), "cpu"), extra=extra,
+                          structure={"k": cfg.structure_k, "samples": struct}
+                          if cfg.structure and self.dist.is_root else None, **herm)
 
     def dump_path_for(self, step: int) -> str:
         cfg = self.cfg

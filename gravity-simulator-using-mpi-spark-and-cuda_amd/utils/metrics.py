@@ -47,6 +47,9 @@ class RunMetrics:
     bodies_left: int | None = None
     closest_q_min: float | None = None
     overlaps_seen: int | None = None
+    # --structure: {"k", "samples": [{"step", "time", "density_centre", "core_radius",
+    # "density_max", "lagrangian_radii", "degenerate"}]} (None, and left out, otherwise)
+    structure: dict | None = None
 
     @property
     def ms_per_step(self) -> float:
@@ -71,7 +74,7 @@ class RunMetrics:
         d = asdict(self)
         for k in ("time_reached", "steps_taken", "dt_min", "block_steps", "body_steps",
                   "pair_evals", "level_max", "level_clamped", "mergers", "bodies_left",
-                  "closest_q_min", "overlaps_seen"):
+                  "closest_q_min", "overlaps_seen", "structure"):
             if d[k] is None:
                 del d[k]
         d.update(ms_per_step=self.ms_per_step, body_updates_per_s=self.body_updates_per_s,
