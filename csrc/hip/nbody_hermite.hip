@@ -7,7 +7,7 @@
 // with the project's pair law (a pair contributes exactly zero to all three when
 // r^2 < cutoff^2: the self term, coincident bodies, a ghost row on a body at the origin).
 //   * One-sided and i-owned like force_split_kernel: a lane owns IPL i-bodies and keeps a, j
-//     (and phi behind a template flag) in registers; no atomics.
+//     (and phi where the variant has it) in registers; no atomics.
 //   * A j-body is two rows, (x, y, z, mu) and (vx, vy, vz, 0); both are staged into
 //     double-buffered LDS tiles by LDS-DMA (tile_fill) and read back as broadcast ds_read_b128.
 //   * fp32 runs over pairs of i as 2-vectors: everything but the v_rsq_f32 and the cutoff
@@ -19,8 +19,8 @@
 //   * Mixed precision (HArgs<float, double>): the state, the predictor, the reduce and the
 //     corrector are fp64; the predictor hands the pair kernels the position as a double-single
 //     pair of fp32 rows, hi = float(xp) and lo = float(xp - hi), a third LDS tile, and the pair
-//     term starts from d = (hi_j - hi_i) + (lo_j - lo_i); all else is the fp32 kernel (hsep).
-//   * Collisions (template flag NN, off by default and then compiled out): every body has a
+//     term starts from d = (hi_j - hi_i) + (lo_j - lo_i); all else is the fp32 kernel.
+//   * Collisions (NN, off by default and then compiled out): every body has a
 //     radius, carried in the spare component of the VP row, and the evaluate kernels also keep,
 //     per i-body, the j of the smallest q = r^2 - (R_i + R_j)^2 (the lowest j on an exact tie),
 //     stored per chunk or slice beside the partial sums; the reduce kernels fold them, keep
@@ -29,16 +29,37 @@
 // per-workgroup dt minima; advances t, steps) -> predict -> evaluate -> reduce + correct.
 // Block time steps (each body on its own step dt 2^-k; second half of this file): next-time
 // minima + control -> predict-all + mark -> compact (scan) -> evaluate of the active bodies,
-// narrow (hermite_narrow_kernel, parallel over j) or wide (the GATHER form of
+// narrow (hermite_narrow_kernel, parallel over j) or wide (the Rows::List form of
 // hermite_eval_kernel) by n_act -> reduce + correct + new level of the active bodies.
+// Every kernel that comes in forms takes one HVariant (pair type, state type, PHI, NN, row
+// mode); the host maps the run's settings to it in one place (with_variant, with_ipl), where the
+// rule for which forms are built is written down.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gs_common.h"
 #include "gs_hermite.h"
 #include "gs_tile.h"
 
 namespace gs {
+
+// The i-rows a kernel works on: all n_pad rows, the rows of a block step's active list
+// (a.blk.list), or a rank's slice a.row0 + [0, a.n_loc) of a multi-rank run.
+enum class Rows { All, List, Slice };
+
+// One form of a kernel: T the type of the pair arithmetic, S of the state (mixed precision: S is
+// not T, and the pair term works on double-single positions, DS); PHI: the potential sum too;
+// NN: collisions on. Kernels that do not sum pairs have the one form, PHI off, for both.
+template <typename T_, typename S_, bool PHI_, bool NN_, Rows ROWS_>
+struct HVariant {
+  using T = T_;
+  using S = S_;
+  using Args = HArgs<T_, S_>;
+  static constexpr bool PHI = PHI_, NN = NN_, DS = sizeof(S_) != sizeof(T_);
+  static constexpr Rows ROWS = ROWS_;
+};
 
 // Separation of a pair: plain, or (DS, mixed precision) from double-single positions hi + lo,
 // where the difference of the hi parts is exact whenever the bodies are close and the lo parts
@@ -49,25 +70,20 @@ __device__ __forceinline__ V hsep(V qh, V xh, V ql, V xl) {
   return qh - xh;
 }
 
-// The lo rows of a lane's i-bodies (DS only).
-template <typename T, int IPL>
-struct HLo {
-  T x[IPL], y[IPL], z[IPL];
-};
-
 // One i-j interaction: 6 sub, 3 fma (r^2), rsq + select, 3 mul (r^-2, mu r^-1, s), mul + 2 fma
 // (d.w), 2 mul (alpha), 3 fma (a), 3 fma (w - alpha d), 3 fma (j); DS: 3 sub and 3 add more.
 // NN (collisions on): also the pair measure q = r^2 - (R_i + R_j)^2 (one add, one fma on the
 // kernel's own r^2; R_j rides in p.w) and a strict-less compare-and-select against the best so
 // far, so that the lowest j keeps an exact tie. A pair the law zeroes, a ghost row j (jreal
 // false) or the body itself (with softening the law does not zero the self pair) takes no part.
-template <typename T, bool PHI, bool DS = false, bool NN = false>
+// The operands of a flag that is off (DS: l, lxi, lyi, lzi; NN: ri, jreal, jg, self, bq, bn) are
+// never read: every caller passes what it has, and the compiler drops them.
+template <bool PHI, bool DS, bool NN, typename T>
 __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, const V4<T>& q,
                                           const V4<T>& p, T cut2, T eps2, T& ax, T& ay, T& az,
-                                          T& ph, T& jx, T& jy, T& jz, const V4<T>& l = V4<T>(),
-                                          T lxi = T(0), T lyi = T(0), T lzi = T(0), T ri = T(0),
-                                          bool jreal = false, int32_t jg = 0, int32_t self = 0,
-                                          T* bq = nullptr, int32_t* bn = nullptr) {
+                                          T& ph, T& jx, T& jy, T& jz, const V4<T>& l, T lxi,
+                                          T lyi, T lzi, T ri, bool jreal, int32_t jg,
+                                          int32_t self, T* bq, int32_t* bn) {
   const T dx = hsep<DS>(q.x, xi, l.x, lxi), dy = hsep<DS>(q.y, yi, l.y, lyi),
           dz = hsep<DS>(q.z, zi, l.z, lzi);
   const T wx = p.x - ui, wy = p.y - vi, wz = p.z - wi;
@@ -106,16 +122,13 @@ __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, co
 // fp32, two i per lane as 2-vectors: each element sees exactly hinteract()'s arithmetic.
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-template <bool PHI, bool DS = false, bool NN = false>
+template <bool PHI, bool DS, bool NN>
 __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, f2 wi,
                                              const V4<float>& q, const V4<float>& p, float cut2,
                                              float eps2, f2& ax, f2& ay, f2& az, f2& ph, f2& jx,
-                                             f2& jy, f2& jz, const V4<float>& l = V4<float>(),
-                                             f2 lxi = f2(0.0f), f2 lyi = f2(0.0f),
-                                             f2 lzi = f2(0.0f), f2 ri = f2(0.0f),
-                                             bool jreal = false, int32_t jg = 0,
-                                             const int32_t* self = nullptr, float* bq = nullptr,
-                                             int32_t* bn = nullptr) {
+                                             f2& jy, f2& jz, const V4<float>& l, f2 lxi, f2 lyi,
+                                             f2 lzi, f2 ri, bool jreal, int32_t jg,
+                                             const int32_t* self, float* bq, int32_t* bn) {
   const f2 dx = hsep<DS>(f2(q.x), xi, f2(l.x), lxi), dy = hsep<DS>(f2(q.y), yi, f2(l.y), lyi),
            dz = hsep<DS>(f2(q.z), zi, f2(l.z), lzi);
   const f2 wx = f2(p.x) - ui, wy = f2(p.y) - vi, wz = f2(p.z) - wi;
@@ -148,61 +161,76 @@ __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, 
   }
 }
 
+// A lane's i-bodies: the predicted rows and the sums of the current chunk; the lo rows (read by
+// DS kernels only); the nearest neighbours (NN kernels only): own radius and row, the best q of
+// the current chunk or slice and its j.
 template <typename T, int IPL>
 struct HState {
   T x[IPL], y[IPL], z[IPL], u[IPL], v[IPL], w[IPL];  // predicted position and velocity
   T ax[IPL], ay[IPL], az[IPL], ph[IPL], jx[IPL], jy[IPL], jz[IPL];  // current chunk
 };
-
-// Nearest neighbour of a lane's i-bodies (NN kernels): own radius and row, the best q of the
-// current chunk or slice and its j.
+template <typename T, int IPL>
+struct HLo {
+  T x[IPL], y[IPL], z[IPL];
+};
 template <typename T, int IPL>
 struct HNear {
   T r[IPL], q[IPL];
   int32_t n[IPL], self[IPL];
 };
 
-template <typename T, int IPL>
-__device__ __forceinline__ void hnear_reset(HNear<T, IPL>& s) {
-#pragma unroll
-  for (int k = 0; k < IPL; ++k) {
-    s.q[k] = T(INFINITY);
-    s.n[k] = -1;
+// Body k of the lane <- row `row` of the predicted state.
+template <bool DS, bool NN, typename T, int IPL>
+__device__ __forceinline__ void hload_row(HState<T, IPL>& st, HLo<T, IPL>& lo, HNear<T, IPL>& nr,
+                                          int k, const V4<T>* XP, const V4<T>* VP,
+                                          const V4<T>* XL, int64_t row) {
+  const V4<T> x = XP[row];
+  const V4<T> v = VP[row];
+  st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
+  st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
+  if constexpr (NN) {
+    nr.r[k] = v.w;
+    nr.self[k] = (int32_t)row;
+  }
+  if constexpr (DS) {
+    const V4<T> l = XL[row];
+    lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
   }
 }
 
-template <typename T, int IPL>
-__device__ __forceinline__ void hzero(HState<T, IPL>& s) {
+// The sums of the lane start from zero, and (NN) its nearest neighbours from (+inf, none).
+template <bool NN, typename T, int IPL>
+__device__ __forceinline__ void hreset(HState<T, IPL>& s, HNear<T, IPL>& nr) {
 #pragma unroll
   for (int k = 0; k < IPL; ++k)
     s.ax[k] = s.ay[k] = s.az[k] = s.ph[k] = s.jx[k] = s.jy[k] = s.jz[k] = T(0);
+  if constexpr (NN) {
+#pragma unroll
+    for (int k = 0; k < IPL; ++k) {
+      nr.q[k] = T(INFINITY);
+      nr.n[k] = -1;
+    }
+  }
 }
 
-template <typename T, int IPL, bool PHI, bool DS = false, bool NN = false>
-__device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q, const V4<T>& p,
-                                              T cut2, T eps2, const V4<T>& l = V4<T>(),
-                                              const HLo<T, IPL>& lo = HLo<T, IPL>(),
-                                              HNear<T, IPL>* nr = nullptr, bool jreal = false,
-                                              int32_t jg = 0) {
+// Row j = (q, p, lo row l, row number jg, real or ghost) against every i-body of the lane.
+template <bool PHI, bool DS, bool NN, typename T, int IPL>
+__device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const HLo<T, IPL>& lo,
+                                              HNear<T, IPL>& nr, const V4<T>& q, const V4<T>& p,
+                                              const V4<T>& l, bool jreal, int32_t jg, T cut2,
+                                              T eps2) {
   if constexpr (sizeof(T) == 4 && IPL % 2 == 0) {
 #pragma unroll
     for (int k = 0; k < IPL; k += 2) {
       f2 ax = {s.ax[k], s.ax[k + 1]}, ay = {s.ay[k], s.ay[k + 1]}, az = {s.az[k], s.az[k + 1]};
       f2 jx = {s.jx[k], s.jx[k + 1]}, jy = {s.jy[k], s.jy[k + 1]}, jz = {s.jz[k], s.jz[k + 1]};
       f2 ph = {s.ph[k], s.ph[k + 1]};
-      if constexpr (NN)
-        hinteract_pk<PHI, DS, true>(
-            f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
-            f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
-            eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
-            f2{lo.y[k], lo.y[k + 1]}, f2{lo.z[k], lo.z[k + 1]}, f2{nr->r[k], nr->r[k + 1]}, jreal,
-            jg, &nr->self[k], &nr->q[k], &nr->n[k]);
-      else
-        hinteract_pk<PHI, DS>(
-            f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
-            f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
-            eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
-            f2{lo.y[k], lo.y[k + 1]}, f2{lo.z[k], lo.z[k + 1]});
+      hinteract_pk<PHI, DS, NN>(
+          f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
+          f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
+          eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
+          f2{lo.y[k], lo.y[k + 1]}, f2{lo.z[k], lo.z[k + 1]}, f2{nr.r[k], nr.r[k + 1]}, jreal,
+          jg, &nr.self[k], &nr.q[k], &nr.n[k]);
       s.ax[k] = ax.x; s.ax[k + 1] = ax.y;
       s.ay[k] = ay.x; s.ay[k + 1] = ay.y;
       s.az[k] = az.x; s.az[k + 1] = az.y;
@@ -211,46 +239,40 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const V4<T>& q,
       s.jz[k] = jz.x; s.jz[k + 1] = jz.y;
       s.ph[k] = ph.x; s.ph[k + 1] = ph.y;
     }
-    return;
-  }
+  } else {
 #pragma unroll
-  for (int k = 0; k < IPL; ++k) {
-    if constexpr (NN)
-      hinteract<T, PHI, DS, true>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
-                                  s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k],
-                                  l, lo.x[k], lo.y[k], lo.z[k], nr->r[k], jreal, jg, nr->self[k],
-                                  &nr->q[k], &nr->n[k]);
-    else
-      hinteract<T, PHI, DS>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
-                            s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
-                            lo.x[k], lo.y[k], lo.z[k]);
+    for (int k = 0; k < IPL; ++k)
+      hinteract<PHI, DS, NN>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
+                             s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
+                             lo.x[k], lo.y[k], lo.z[k], nr.r[k], jreal, jg, nr.self[k], &nr.q[k],
+                             &nr.n[k]);
   }
 }
 
-// EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
+// EVALUATE: grid (rows / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
 // stores one partial per chunk: PA[c][i] = (ax, ay, az, sum mu/r), PJ[c][i] = (jx, jy, jz, 0).
-// GATHER (a block step's wide path): lane slot s owns body list[s], the partials are stored per
-// slot and i-blocks beyond n_act exit; the j loop, hence a body's bits, is the same.
-// Mixed precision (S is not T): a third tile carries the lo rows XL, the lane keeps the lo rows
-// of its i-bodies, and only the separation differs (hsep).
+// Rows::List (a block step's wide path): lane slot s owns body list[s], the partials are stored
+// per slot and i-blocks beyond n_act exit; the j loop, hence a body's bits, is the same.
+// Mixed precision (DS): a third tile carries the lo rows XL, the lane keeps the lo rows of its
+// i-bodies, and only the separation differs.
 // NN: the lane also keeps the nearest neighbour (smallest q, lowest j on a tie) of each of its
 // i-bodies over the chunk; the partial is (PJ[c][i].w, PN[c][i]). j is uniform over the wave, so
 // the ghost-row test is a scalar compare.
-// SLICE (a rank of a multi-rank run): the i-rows are the rank's own, a.row0 + [0, a.n_loc), which
-// the grid's x extent covers; the partials are indexed by local row with stride a.n_loc. The j
-// sweep is the same, so a body's bits are those of the one-rank run.
-template <typename T, int IPL, bool PHI, bool GATHER = false, typename S = T, bool NN = false,
-          bool SLICE = false>
-__global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int gated) {
-  constexpr bool DS = sizeof(S) != sizeof(T);
+// Rows::Slice (a rank of a multi-rank run): the i-rows are the rank's own, a.row0 + [0, a.n_loc),
+// which the grid's x extent covers; the partials are indexed by local row with stride a.n_loc.
+// The j sweep is the same, so a body's bits are those of the one-rank run.
+template <typename K, int IPL>
+__global__ __launch_bounds__(kBlock) void hermite_eval_kernel(typename K::Args a, int gated) {
+  using T = typename K::T;
+  constexpr bool DS = K::DS, NN = K::NN;
   constexpr int TB = Tile<T>::kBodies;
   __shared__ __attribute__((aligned(16))) V4<T> tx[2][TB];
   __shared__ __attribute__((aligned(16))) V4<T> tv[2][TB];
   __shared__ __attribute__((aligned(16))) V4<T> tl[2][DS ? TB : 1];
   if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
-  const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);  // (SLICE: counted from a.row0)
+  const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);  // (Slice: counted from a.row0)
   int64_t n_act = 0;
-  if constexpr (GATHER) {
+  if constexpr (K::ROWS == Rows::List) {
     const HermiteBlockCtrl* bc = a.blk.bc;
     if (!bc->active || bc->path != HP_WIDE) return;
     n_act = bc->n_act;
@@ -268,25 +290,15 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
   V4<T>* PJ = reinterpret_cast<V4<T>*>(a.PJ);
   const V4<T>* XL = reinterpret_cast<const V4<T>*>(a.XL);
   HState<T, IPL> st;
-  HLo<T, IPL> lo;
-  HNear<T, IPL> nr;
+  HLo<T, IPL> lo = {};
+  HNear<T, IPL> nr = {};
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
     int64_t row = ib + threadIdx.x + k * kBlock;
-    if constexpr (SLICE) row += a.row0;
-    if constexpr (GATHER) row = a.blk.list[row < n_act ? row : n_act - 1];  // (spare slots: a copy)
-    const V4<T> x = XP[row];
-    const V4<T> v = VP[row];
-    st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
-    st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
-    if constexpr (NN) {
-      nr.r[k] = v.w;
-      nr.self[k] = (int32_t)row;
-    }
-    if constexpr (DS) {
-      const V4<T> l = XL[row];
-      lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
-    }
+    if constexpr (K::ROWS == Rows::Slice) row += a.row0;
+    if constexpr (K::ROWS == Rows::List)
+      row = a.blk.list[row < n_act ? row : n_act - 1];  // (spare slots: a copy)
+    hload_row<DS, NN>(st, lo, nr, k, XP, VP, XL, row);
   }
   auto fill = [&](int t) {
     const int64_t j0 = (int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB;
@@ -295,8 +307,8 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
     if constexpr (DS) tile_fill<T>(XL + j0, tl[t & 1]);
   };
   fill(0);
-  hzero<T, IPL>(st);
-  if constexpr (NN) hnear_reset<T, IPL>(nr);
+  hreset<NN>(st, nr);
+  const int64_t pstride = K::ROWS == Rows::Slice ? a.n_loc : a.n_pad;  // of the partials
   for (int t = 0; t < ntiles; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile t is in LDS for every wave; buffer (t+1)&1 is free
@@ -304,29 +316,14 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
     const V4<T>* cx = tx[t & 1];
     const V4<T>* cv = tv[t & 1];
     const V4<T>* cl = tl[t & 1];
-    if constexpr (NN) {
-      const int32_t jb = (int32_t)((int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB);
-      const int32_t nreal = (int32_t)a.n_real;
+    // (NN only) the tile's first row and the count of real rows
+    const int32_t jb = (int32_t)((int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB);
+    const int32_t nreal = (int32_t)a.n_real;
 #pragma unroll 4
-      for (int j = 0; j < TB; ++j) {
-        const V4<T> q = cx[j], p = cv[j];
-        const int32_t jg = jb + j;
-        if constexpr (DS)
-          hinteract_all<T, IPL, PHI, true, true>(st, q, p, a.cut2, a.eps2, cl[j], lo, &nr,
-                                                 jg < nreal, jg);
-        else
-          hinteract_all<T, IPL, PHI, false, true>(st, q, p, a.cut2, a.eps2, V4<T>(),
-                                                  HLo<T, IPL>(), &nr, jg < nreal, jg);
-      }
-    } else {
-#pragma unroll 4
-      for (int j = 0; j < TB; ++j) {
-        const V4<T> q = cx[j], p = cv[j];  // uniform addresses: broadcast ds_reads
-        if constexpr (DS)
-          hinteract_all<T, IPL, PHI, true>(st, q, p, a.cut2, a.eps2, cl[j], lo);
-        else
-          hinteract_all<T, IPL, PHI>(st, q, p, a.cut2, a.eps2);
-      }
+    for (int j = 0; j < TB; ++j) {
+      const V4<T> q = cx[j], p = cv[j];  // uniform addresses: broadcast ds_reads
+      hinteract_all<K::PHI, DS, NN>(st, lo, nr, q, p, DS ? cl[j] : V4<T>(), jb + j < nreal,
+                                    jb + j, a.cut2, a.eps2);
     }
     if ((t + 1) % tpc == 0) {
       const int c = c0 + t / tpc;
@@ -337,18 +334,12 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(HArgs<T, S> a, int
         oj.x = st.jx[k]; oj.y = st.jy[k]; oj.z = st.jz[k]; oj.w = T(0);
         if constexpr (NN) {
           oj.w = nr.q[k];
-          a.PN[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = nr.n[k];
+          a.PN[(int64_t)c * pstride + ib + threadIdx.x + k * kBlock] = nr.n[k];
         }
-        if constexpr (SLICE) {
-          PA[(int64_t)c * a.n_loc + ib + threadIdx.x + k * kBlock] = oa;
-          PJ[(int64_t)c * a.n_loc + ib + threadIdx.x + k * kBlock] = oj;
-        } else {
-          PA[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oa;
-          PJ[(int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock] = oj;
-        }
+        PA[(int64_t)c * pstride + ib + threadIdx.x + k * kBlock] = oa;
+        PJ[(int64_t)c * pstride + ib + threadIdx.x + k * kBlock] = oj;
       }
-      hzero<T, IPL>(st);
-      if constexpr (NN) hnear_reset<T, IPL>(nr);
+      hreset<NN>(st, nr);
     }
   }
 }
@@ -400,17 +391,36 @@ __global__ __launch_bounds__(kBlock) void hermite_ctrl_kernel(HermiteCtrl* ctrl,
   *ctrl = c;
 }
 
-// PREDICT: xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2 (ghost rows stay zero).
+// The predictor of real body i over h: xp = x + v h + a h^2/2 + j h^3/6, vp = v + a h + j h^2/2.
+template <typename T, typename S>
+__device__ __forceinline__ void hpredict(const HArgs<T, S>& a, int64_t i, S h, V4<S>& xp,
+                                         V4<S>& vp) {
+  const S h2 = (h * h) / S(2), h3 = (h * h * h) / S(6);
+  const V4<S> x = reinterpret_cast<const V4<S>*>(a.X)[i];
+  const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
+  const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
+  const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
+  xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
+  xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
+  xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
+  xp.w = x.w;
+  vp.x = v.x + (ac.x * h + jk.x * h2);
+  vp.y = v.y + (ac.y * h + jk.y * h2);
+  vp.z = v.z + (ac.z * h + jk.z * h2);
+}
+
 // Store row i of the predicted state for the evaluate kernels: as it is, or (mixed precision,
 // S is not T) the position split into XP = (float(xp), mu), XL = (float(xp - double(hi)), 0).
-// NN: the spare component of the VP row carries the body's radius (R, state precision).
-template <typename T, typename S, bool NN = false>
+// Spare::Radius (collisions on): the spare component of the VP row carries the body's radius (R,
+// state precision).
+enum class Spare { Zero, Radius };
+template <Spare SPARE, typename T, typename S>
 __device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i, const V4<S>& xp,
                                                 const V4<S>& vp) {
   V4<T> h, v;
   h.x = (T)xp.x; h.y = (T)xp.y; h.z = (T)xp.z; h.w = (T)xp.w;
   v.x = (T)vp.x; v.y = (T)vp.y; v.z = (T)vp.z; v.w = T(0);
-  if constexpr (NN) v.w = (T)a.R[i];
+  if constexpr (SPARE == Spare::Radius) v.w = (T)a.R[i];
   reinterpret_cast<V4<T>*>(a.XP)[i] = h;
   reinterpret_cast<V4<T>*>(a.VP)[i] = v;
   if constexpr (sizeof(S) != sizeof(T)) {
@@ -420,29 +430,19 @@ __device__ __forceinline__ void store_predicted(const HArgs<T, S>& a, int64_t i,
   }
 }
 
-// SLICE: the grid covers the rank's rows a.row0 + [0, a.n_loc) of the full-length XP, VP (XL).
-template <typename T, typename S, bool NN = false, bool SLICE = false>
-__global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) {
+// PREDICT over the step's h (ghost rows stay zero).
+// Rows::Slice: the grid covers the rank's rows a.row0 + [0, a.n_loc) of the full-length XP, VP
+// (XL).
+template <typename K>
+__global__ __launch_bounds__(kBlock) void hermite_predict_kernel(typename K::Args a) {
+  using S = typename K::S;
   if (!a.ctrl->active) return;
-  const int64_t i = (SLICE ? a.row0 : 0) + (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i =
+      (K::ROWS == Rows::Slice ? a.row0 : 0) + (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
   V4<S> xp = {S(0), S(0), S(0), S(0)}, vp = xp;
-  if (i < a.n_real) {
-    const S h = (S)a.ctrl->h;
-    const S h2 = (h * h) / S(2), h3 = (h * h * h) / S(6);
-    const V4<S> x = reinterpret_cast<const V4<S>*>(a.X)[i];
-    const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
-    const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
-    const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
-    xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
-    xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
-    xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
-    xp.w = x.w;
-    vp.x = v.x + (ac.x * h + jk.x * h2);
-    vp.y = v.y + (ac.y * h + jk.y * h2);
-    vp.z = v.z + (ac.z * h + jk.z * h2);
-  }
-  store_predicted<T, S, NN>(a, i, xp, vp);
+  if (i < a.n_real) hpredict(a, i, (S)a.ctrl->h, xp, vp);
+  store_predicted<K::NN ? Spare::Radius : Spare::Zero>(a, i, xp, vp);
 }
 
 // SPLIT (mixed precision): the predictor's output at h = 0, for the derivatives of the current
@@ -450,8 +450,8 @@ __global__ __launch_bounds__(kBlock) void hermite_predict_kernel(HArgs<T, S> a) 
 __global__ __launch_bounds__(kBlock) void hermite_split_kernel(HArgs<float, double> a) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
-  store_predicted<float, double>(a, i, reinterpret_cast<const V4<double>*>(a.X)[i],
-                                 reinterpret_cast<const V4<double>*>(a.V)[i]);
+  store_predicted<Spare::Zero>(a, i, reinterpret_cast<const V4<double>*>(a.X)[i],
+                               reinterpret_cast<const V4<double>*>(a.V)[i]);
 }
 
 // STAGE (collisions on): XP, VP (and XL) <- the current X, V with the radius in VP's spare
@@ -460,8 +460,8 @@ template <typename T, typename S>
 __global__ __launch_bounds__(kBlock) void hermite_stage_kernel(HArgs<T, S> a) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
-  store_predicted<T, S, true>(a, i, reinterpret_cast<const V4<S>*>(a.X)[i],
-                              reinterpret_cast<const V4<S>*>(a.V)[i]);
+  store_predicted<Spare::Radius>(a, i, reinterpret_cast<const V4<S>*>(a.X)[i],
+                                 reinterpret_cast<const V4<S>*>(a.V)[i]);
 }
 
 // The latest (q, nn) of body i, its closest-approach record since the last clear, and the
@@ -482,16 +482,101 @@ __device__ __forceinline__ double norm3(double x, double y, double z) {
   return sqrt(x * x + y * y + z * z);
 }
 
+// The derivatives of one body, summed from its partials (state precision), and (NN) the
+// nearest neighbour folded from them.
+template <typename T, typename S>
+struct HSum {
+  S ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
+  T q = T(INFINITY);
+  int32_t n = -1;
+};
+
+// One step of the in-order fold of a body's partials: m += the partial at index o; NN: its (q, j)
+// with a strict less, so that on a tie the earlier partial (the lower j) stays.
+template <bool NN, typename T, typename S>
+__device__ __forceinline__ void hfold(HSum<T, S>& m, const V4<T>* PA, const V4<T>* PJ,
+                                      const int32_t* PN, int64_t o) {
+  const V4<T> pa = PA[o];
+  const V4<T> pj = PJ[o];
+  m.ax += pa.x; m.ay += pa.y; m.az += pa.z; m.ph += pa.w;
+  m.jx += pj.x; m.jy += pj.y; m.jz += pj.z;
+  if constexpr (NN) {
+    if (pj.w < m.q) {
+      m.q = pj.w;
+      m.n = PN[o];
+    }
+  }
+}
+
+// (The helpers below take the arrays, not the HArgs: a reference to the kernel's argument block
+// costs a kernel that does not otherwise take one a private copy of it, and registers.)
+
+// The carried a, j of body i <- the sums.
+template <typename T, typename S>
+__device__ __forceinline__ void hcarry(V4<S>* A, V4<S>* J, int64_t i, const HSum<T, S>& m) {
+  V4<S> oa, oj;
+  oa.x = m.ax; oa.y = m.ay; oa.z = m.az; oa.w = S(0);
+  oj.x = m.jx; oj.y = m.jy; oj.z = m.jz; oj.w = S(0);
+  A[i] = oa;
+  J[i] = oj;
+}
+
+// The corrector of body i over h: x, v <- corrected from the carried (a0, j0), which are handed
+// back for the criterion, and the new sums.
+template <typename T, typename S>
+__device__ __forceinline__ void hcorrect(V4<S>* X, V4<S>* V, const V4<S>* A, const V4<S>* J,
+                                         int64_t i, S h, const HSum<T, S>& m, V4<S>& a0,
+                                         V4<S>& j0) {
+  const S hh = h / S(2), h12 = (h * h) / S(12);
+  const V4<S> x = X[i], v = V[i];
+  a0 = A[i];
+  j0 = J[i];
+  V4<S> v1, x1;
+  v1.x = v.x + ((a0.x + m.ax) * hh + (j0.x - m.jx) * h12);
+  v1.y = v.y + ((a0.y + m.ay) * hh + (j0.y - m.jy) * h12);
+  v1.z = v.z + ((a0.z + m.az) * hh + (j0.z - m.jz) * h12);
+  v1.w = S(0);
+  x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - m.ax) * h12);
+  x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - m.ay) * h12);
+  x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - m.az) * h12);
+  x1.w = x.w;
+  X[i] = x1;
+  V[i] = v1;
+}
+
+// Aarseth's criterion from the 2nd and 3rd derivatives that the two evaluations (a0, j0 before
+// the step hd, the sums after it) imply. False where |j| = 0 or the ratio is not finite.
+template <typename T, typename S>
+__device__ __forceinline__ bool aarseth_dt(double hd, double eta, const V4<S>& a0,
+                                           const V4<S>& j0, const HSum<T, S>& m, double& dt) {
+  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
+  const double da[3] = {(double)a0.x - (double)m.ax, (double)a0.y - (double)m.ay,
+                        (double)a0.z - (double)m.az};
+  const double jo[3] = {j0.x, j0.y, j0.z}, jn[3] = {m.jx, m.jy, m.jz};
+  double s2[3], s3[3];
+  for (int d = 0; d < 3; ++d) {
+    const double a2 = (-6.0 * da[d] - hd * (4.0 * jo[d] + 2.0 * jn[d])) * ih2;
+    s3[d] = (12.0 * da[d] + 6.0 * hd * (jo[d] + jn[d])) * ih3;
+    s2[d] = a2 + hd * s3[d];
+  }
+  const double an = norm3(m.ax, m.ay, m.az), jnn = norm3(m.jx, m.jy, m.jz);
+  const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
+  dt = sqrt(eta * (an * n2 + jnn * jnn) / (jnn * n3 + n2 * n2));
+  return jnn > 0.0 && isfinite(dt);
+}
+
 // REDUCE (+ CORRECT): one thread per body adds its chunk partials in chunk order, then
 // HM_STEP applies the corrector and Aarseth's criterion, HM_INIT starts a run from (x, v),
 // HM_OUT returns the derivatives. Per-workgroup dt minima go to wgmin (+inf when no body of the
 // workgroup takes part: ghost rows, |j| = 0, a non-finite ratio, or a fixed-step run).
-// NN: the chunks' (q, j) partials fold with a strict less in chunk order (the lowest j keeps a
-// tie); HM_OUT writes them to q_out / nn_out, the other modes record them (nn_record).
-// SLICE: the grid covers the rank's rows; it reads the rank's partials [n_chunks][n_loc] and
-// writes the rows' entries of the full-length X, V, A, J, outputs and wgmin.
-template <typename T, typename S, bool NN = false, bool SLICE = false>
-__global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
+// NN: HM_OUT writes the folded (q, j) to q_out / nn_out, the other modes record them (nn_record).
+// Rows::Slice: the grid covers the rank's rows; it reads the rank's partials [n_chunks][n_loc]
+// and writes the rows' entries of the full-length X, V, A, J, outputs and wgmin.
+template <typename K>
+__global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(typename K::Args a) {
+  using T = typename K::T;
+  using S = typename K::S;
+  constexpr bool SLICE = K::ROWS == Rows::Slice, NN = K::NN;
   __shared__ double red[kBlock / 64];
   if (a.mode == HM_STEP && !a.ctrl->active) return;
   int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad is a multiple of 256)
@@ -503,35 +588,22 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
   }
   const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
   const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
-  S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
-  T bq = T(INFINITY);
-  int32_t bn = -1;
-  for (int c = 0; c < a.n_chunks; ++c) {
-    const V4<T> pa = PA[(int64_t)c * pstride + li];
-    const V4<T> pj = PJ[(int64_t)c * pstride + li];
-    a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
-    j1x += pj.x; j1y += pj.y; j1z += pj.z;
-    if constexpr (NN) {
-      if (pj.w < bq) {
-        bq = pj.w;
-        bn = a.PN[(int64_t)c * pstride + li];
-      }
-    }
-  }
+  HSum<T, S> m;
+  for (int c = 0; c < a.n_chunks; ++c) hfold<NN>(m, PA, PJ, a.PN, (int64_t)c * pstride + li);
   if (a.mode == HM_OUT) {
     V4<S> oa, oj;
-    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = -sp;
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
+    oa.x = m.ax; oa.y = m.ay; oa.z = m.az; oa.w = -m.ph;
+    oj.x = m.jx; oj.y = m.jy; oj.z = m.jz; oj.w = S(0);
     reinterpret_cast<V4<S>*>(a.a_out)[i] = oa;
     reinterpret_cast<V4<S>*>(a.j_out)[i] = oj;
     if constexpr (NN) {
-      a.q_out[i] = (double)bq;
-      a.nn_out[i] = bn;
+      a.q_out[i] = (double)m.q;
+      a.nn_out[i] = m.n;
     }
     return;
   }
   if constexpr (NN) {
-    if (i < a.n_real) nn_record<T, S>(a, i, bq, bn, &a.ctrl->overlaps);
+    if (i < a.n_real) nn_record<T, S>(a, i, m.q, m.n, &a.ctrl->overlaps);
   }
   V4<S>* A = reinterpret_cast<V4<S>*>(a.A);
   V4<S>* J = reinterpret_cast<V4<S>*>(a.J);
@@ -547,53 +619,21 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(HArgs<T, S> a) {
     }
   } else if (a.mode == HM_INIT) {
     if (eta > 0.0) {
-      const double an = norm3(a1x, a1y, a1z), jn = norm3(j1x, j1y, j1z);
+      const double an = norm3(m.ax, m.ay, m.az), jn = norm3(m.jx, m.jy, m.jz);
       const double d = 0.5 * eta * an / jn;
       if (jn > 0.0 && isfinite(d)) dti = d;
     }
   } else {
     const double hd = a.ctrl->h;
-    const S h = (S)hd;
-    const S hh = h / S(2), h12 = (h * h) / S(12);
-    V4<S>* X = reinterpret_cast<V4<S>*>(a.X);
-    V4<S>* V = reinterpret_cast<V4<S>*>(a.V);
-    const V4<S> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
-    V4<S> v1, x1;
-    v1.x = v.x + ((a0.x + a1x) * hh + (j0.x - j1x) * h12);
-    v1.y = v.y + ((a0.y + a1y) * hh + (j0.y - j1y) * h12);
-    v1.z = v.z + ((a0.z + a1z) * hh + (j0.z - j1z) * h12);
-    v1.w = S(0);
-    x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - a1x) * h12);
-    x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - a1y) * h12);
-    x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - a1z) * h12);
-    x1.w = x.w;
-    X[i] = x1;
-    V[i] = v1;
+    V4<S> a0, j0;
+    hcorrect(reinterpret_cast<V4<S>*>(a.X), reinterpret_cast<V4<S>*>(a.V), A, J, i, (S)hd, m, a0,
+             j0);
     if (eta > 0.0) {
-      // Aarseth's criterion from the 2nd and 3rd derivatives the two evaluations imply
-      const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
-      const double da[3] = {(double)a0.x - (double)a1x, (double)a0.y - (double)a1y,
-                            (double)a0.z - (double)a1z};
-      const double jo[3] = {j0.x, j0.y, j0.z}, jn[3] = {j1x, j1y, j1z};
-      double s2[3], s3[3];
-      for (int d = 0; d < 3; ++d) {
-        const double a2 = (-6.0 * da[d] - hd * (4.0 * jo[d] + 2.0 * jn[d])) * ih2;
-        s3[d] = (12.0 * da[d] + 6.0 * hd * (jo[d] + jn[d])) * ih3;
-        s2[d] = a2 + hd * s3[d];
-      }
-      const double an = norm3(a1x, a1y, a1z), jnn = norm3(j1x, j1y, j1z);
-      const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
-      const double d = sqrt(eta * (an * n2 + jnn * jnn) / (jnn * n3 + n2 * n2));
-      if (jnn > 0.0 && isfinite(d)) dti = d;
+      double d;
+      if (aarseth_dt(hd, eta, a0, j0, m, d)) dti = d;
     }
   }
-  if (i < a.n_real) {
-    V4<S> oa, oj;
-    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = S(0);
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
-    A[i] = oa;
-    J[i] = oj;
-  }
+  if (i < a.n_real) hcarry(A, J, i, m);
   dti = block_min(dti, red);
   if (threadIdx.x == 0) a.wgmin[(SLICE ? a.row0 / kBlock : 0) + blockIdx.x] = dti;
 }
@@ -607,6 +647,16 @@ __device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
     const long long o = __shfl_down((long long)v, off, 64);
     v = o < v ? (int64_t)o : v;
   }
+  return v;
+}
+
+// Minimum over the workgroup's threads (valid in thread 0).
+__device__ __forceinline__ int64_t block_min_i64(int64_t v, int64_t* red) {
+  v = wave_min_i64(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kBlock / 64; ++w) v = red[w] < v ? red[w] : v;
   return v;
 }
 
@@ -633,13 +683,8 @@ __global__ __launch_bounds__(kBlock) void block_next_kernel(HArgs<T, S> a) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   int64_t v = INT64_MAX;
   if (i < a.n_real) v = b.tb[i] + ((int64_t)1 << (L - b.level[i]));
-  v = wave_min_i64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) v = red[w] < v ? red[w] : v;
-    b.wgnext[blockIdx.x] = v;
-  }
+  v = block_min_i64(v, red);
+  if (threadIdx.x == 0) b.wgnext[blockIdx.x] = v;
 }
 
 // NEXT, stage 2 and CONTROL (one workgroup): t_next = the earliest due time; past the target the
@@ -649,11 +694,8 @@ __global__ __launch_bounds__(kBlock) void block_ctrl_kernel(HermiteBlockCtrl* bc
   __shared__ int64_t red[kBlock / 64];
   int64_t m = INT64_MAX;
   for (int k = threadIdx.x; k < nwg; k += kBlock) m = wgnext[k] < m ? wgnext[k] : m;
-  m = wave_min_i64(m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
+  m = block_min_i64(m, red);
   if (threadIdx.x != 0) return;
-  for (int w = 1; w < kBlock / 64; ++w) m = red[w] < m ? red[w] : m;
   if (bc->t_ticks >= bc->target || m > bc->target) {
     bc->active = 0;
     return;
@@ -666,8 +708,9 @@ __global__ __launch_bounds__(kBlock) void block_ctrl_kernel(HermiteBlockCtrl* bc
 
 // PREDICT-ALL + MARK: every real body from its own tb to t_next; counts the due bodies of the
 // workgroup for the compaction.
-template <typename T, typename S, bool NN = false>
-__global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T, S> a) {
+template <typename K>
+__global__ __launch_bounds__(kBlock) void block_predict_kernel(typename K::Args a) {
+  using S = typename K::S;
   __shared__ int cnt[kBlock / 64];
   const HBlock& b = a.blk;
   if (!b.bc->active) return;
@@ -678,21 +721,9 @@ __global__ __launch_bounds__(kBlock) void block_predict_kernel(HArgs<T, S> a) {
   bool due = false;
   if (i < a.n_real) {
     due = body_due(b, i, L, t_next);
-    const S h = (S)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L);
-    const S h2 = (h * h) / S(2), h3 = (h * h * h) / S(6);
-    const V4<S> x = reinterpret_cast<const V4<S>*>(a.X)[i];
-    const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
-    const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
-    const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
-    xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
-    xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
-    xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
-    xp.w = x.w;
-    vp.x = v.x + (ac.x * h + jk.x * h2);
-    vp.y = v.y + (ac.y * h + jk.y * h2);
-    vp.z = v.z + (ac.z * h + jk.z * h2);
+    hpredict(a, i, (S)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L), xp, vp);
   }
-  store_predicted<T, S, NN>(a, i, xp, vp);
+  store_predicted<K::NN ? Spare::Radius : Spare::Zero>(a, i, xp, vp);
   const int c = __popcll(__ballot(due));
   if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -745,9 +776,10 @@ __global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T, S> a) {
 // NN: a lane folds its rows with a strict less in j order; the lanes' and the waves' (q, j) fold
 // lexicographically (the smaller q, on a tie the lower j); the partial is (NJ[s][slot].w,
 // NNI[s][slot]).
-template <typename T, bool PHI, typename S = T, bool NN = false>
-__global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
-  constexpr bool DS = sizeof(S) != sizeof(T);
+template <typename K>
+__global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(typename K::Args a) {
+  using T = typename K::T;
+  constexpr bool DS = K::DS, NN = K::NN;
   constexpr int G = kNarrowGroup;
   __shared__ T red[kBlock / 64][G][8];
   __shared__ int32_t redn[kBlock / 64][NN ? G : 1];
@@ -765,41 +797,20 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int g = blockIdx.y; g < ngroups; g += (int)gridDim.y) {
     HState<T, G> st;
-    HLo<T, G> lo;
-    HNear<T, G> nr;
+    HLo<T, G> lo = {};
+    HNear<T, G> nr = {};
 #pragma unroll
-    for (int k = 0; k < G; ++k) {
-      const int slot = min(g * G + k, n_act - 1);  // (spare slots of the last group: a copy)
-      const int64_t row = b.list[slot];
-      const V4<T> x = XP[row];
-      const V4<T> v = VP[row];
-      st.x[k] = x.x; st.y[k] = x.y; st.z[k] = x.z;
-      st.u[k] = v.x; st.v[k] = v.y; st.w[k] = v.z;
-      if constexpr (NN) {
-      nr.r[k] = v.w;
-      nr.self[k] = (int32_t)row;
-    }
-      if constexpr (DS) {
-        const V4<T> l = XL[row];
-        lo.x[k] = l.x; lo.y[k] = l.y; lo.z[k] = l.z;
-      }
-    }
-    hzero<T, G>(st);
-    if constexpr (NN) hnear_reset<T, G>(nr);
+    for (int k = 0; k < G; ++k)  // (spare slots of the last group: a copy)
+      hload_row<DS, NN>(st, lo, nr, k, XP, VP, XL, (int64_t)b.list[min(g * G + k, n_act - 1)]);
+    hreset<NN>(st, nr);
     for (int64_t j = j0 + threadIdx.x; j < j1; j += kBlock) {
       const V4<T> q = XP[j], p = VP[j];
-      if constexpr (NN) {
-        if constexpr (DS)
-          hinteract_all<T, G, PHI, true, true>(st, q, p, a.cut2, a.eps2, XL[j], lo, &nr,
-                                               j < a.n_real, (int32_t)j);
-        else
-          hinteract_all<T, G, PHI, false, true>(st, q, p, a.cut2, a.eps2, V4<T>(), HLo<T, G>(),
-                                                &nr, j < a.n_real, (int32_t)j);
-      } else if constexpr (DS) {
-        hinteract_all<T, G, PHI, true>(st, q, p, a.cut2, a.eps2, XL[j], lo);
-      } else {
-        hinteract_all<T, G, PHI>(st, q, p, a.cut2, a.eps2);
-      }
+      if constexpr (DS)  // (the lo row straight from memory: a copy of it costs a move per row)
+        hinteract_all<K::PHI, DS, NN>(st, lo, nr, q, p, XL[j], j < a.n_real, (int32_t)j, a.cut2,
+                                      a.eps2);
+      else
+        hinteract_all<K::PHI, DS, NN>(st, lo, nr, q, p, V4<T>(), j < a.n_real, (int32_t)j, a.cut2,
+                                      a.eps2);
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -861,106 +872,57 @@ __global__ __launch_bounds__(kBlock) void hermite_narrow_kernel(HArgs<T, S> a) {
 // body's own h, Aarseth's dt_want and the level rule: any number of halvings (capped at L), at
 // most one doubling and only where t_next allows the doubled step. HM_OUT: the sums go to
 // a_out / j_out [slot] and nothing else is touched.
-template <typename T, typename S, bool NN = false>
-__global__ __launch_bounds__(kBlock) void block_correct_kernel(HArgs<T, S> a) {
+template <typename K>
+__global__ __launch_bounds__(kBlock) void block_correct_kernel(typename K::Args a) {
+  using T = typename K::T;
+  using S = typename K::S;
+  constexpr bool NN = K::NN;
   const HBlock& b = a.blk;
   HermiteBlockCtrl* bc = b.bc;
   if (!bc->active) return;
   const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= bc->n_act) return;
-  S a1x = 0, a1y = 0, a1z = 0, sp = 0, j1x = 0, j1y = 0, j1z = 0;
-  T bq = T(INFINITY);
-  int32_t bn = -1;
+  HSum<T, S> m;
   if (bc->path == HP_NARROW) {
     const V4<T>* NA = reinterpret_cast<const V4<T>*>(b.NA);
     const V4<T>* NJ = reinterpret_cast<const V4<T>*>(b.NJ);
 #pragma unroll 8
-    for (int c = 0; c < b.n_slices; ++c) {  // (unrolled: the loads of 8 slices are in flight)
-      const V4<T> pa = NA[(int64_t)c * b.cap + s];
-      const V4<T> pj = NJ[(int64_t)c * b.cap + s];
-      a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
-      j1x += pj.x; j1y += pj.y; j1z += pj.z;
-      if constexpr (NN) {
-        if (pj.w < bq) {
-          bq = pj.w;
-          bn = a.NNI[(int64_t)c * b.cap + s];
-        }
-      }
-    }
+    for (int c = 0; c < b.n_slices; ++c)  // (unrolled: the loads of 8 slices are in flight)
+      hfold<NN>(m, NA, NJ, a.NNI, (int64_t)c * b.cap + s);
   } else {
     const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
     const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
-    for (int c = 0; c < a.n_chunks; ++c) {
-      const V4<T> pa = PA[(int64_t)c * a.n_pad + s];
-      const V4<T> pj = PJ[(int64_t)c * a.n_pad + s];
-      a1x += pa.x; a1y += pa.y; a1z += pa.z; sp += pa.w;
-      j1x += pj.x; j1y += pj.y; j1z += pj.z;
-      if constexpr (NN) {
-        if (pj.w < bq) {
-          bq = pj.w;
-          bn = a.PN[(int64_t)c * a.n_pad + s];
-        }
-      }
-    }
+    for (int c = 0; c < a.n_chunks; ++c) hfold<NN>(m, PA, PJ, a.PN, (int64_t)c * a.n_pad + s);
   }
   if (a.mode == HM_OUT) {
     V4<S> oa, oj;
-    oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = -sp;
-    oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
+    oa.x = m.ax; oa.y = m.ay; oa.z = m.az; oa.w = -m.ph;
+    oj.x = m.jx; oj.y = m.jy; oj.z = m.jz; oj.w = S(0);
     reinterpret_cast<V4<S>*>(a.a_out)[s] = oa;
     reinterpret_cast<V4<S>*>(a.j_out)[s] = oj;
     if constexpr (NN) {
-      a.q_out[s] = (double)bq;
-      a.nn_out[s] = bn;
+      a.q_out[s] = (double)m.q;
+      a.nn_out[s] = m.n;
     }
     return;
   }
   const int64_t i = b.list[s];
-  if constexpr (NN) nn_record<T, S>(a, i, bq, bn, &bc->overlaps);
+  if constexpr (NN) nn_record<T, S>(a, i, m.q, m.n, &bc->overlaps);
   const int L = bc->L;
   const int64_t t_next = bc->t_ticks;
   const double dt_max = bc->dt_max, eta = bc->eta;
   const double hd = ticks_seconds(dt_max, t_next - b.tb[i], L);
-  const S h = (S)hd;
-  const S hh = h / S(2), h12 = (h * h) / S(12);
-  V4<S>* X = reinterpret_cast<V4<S>*>(a.X);
-  V4<S>* V = reinterpret_cast<V4<S>*>(a.V);
   V4<S>* A = reinterpret_cast<V4<S>*>(a.A);
   V4<S>* J = reinterpret_cast<V4<S>*>(a.J);
-  const V4<S> x = X[i], v = V[i], a0 = A[i], j0 = J[i];
-  V4<S> v1, x1;
-  v1.x = v.x + ((a0.x + a1x) * hh + (j0.x - j1x) * h12);
-  v1.y = v.y + ((a0.y + a1y) * hh + (j0.y - j1y) * h12);
-  v1.z = v.z + ((a0.z + a1z) * hh + (j0.z - j1z) * h12);
-  v1.w = S(0);
-  x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - a1x) * h12);
-  x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - a1y) * h12);
-  x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - a1z) * h12);
-  x1.w = x.w;
-  X[i] = x1;
-  V[i] = v1;
-  V4<S> oa, oj;
-  oa.x = a1x; oa.y = a1y; oa.z = a1z; oa.w = S(0);
-  oj.x = j1x; oj.y = j1y; oj.z = j1z; oj.w = S(0);
-  A[i] = oa;
-  J[i] = oj;
+  V4<S> a0, j0;
+  hcorrect(reinterpret_cast<V4<S>*>(a.X), reinterpret_cast<V4<S>*>(a.V), A, J, i, (S)hd, m, a0,
+           j0);
+  hcarry(A, J, i, m);
   b.tb[i] = t_next;
-  // Aarseth's criterion (as hermite_reduce_kernel), per body
-  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
-  const double da[3] = {(double)a0.x - (double)a1x, (double)a0.y - (double)a1y,
-                        (double)a0.z - (double)a1z};
-  const double jo[3] = {j0.x, j0.y, j0.z}, jn[3] = {j1x, j1y, j1z};
-  double s2[3], s3[3];
-  for (int d = 0; d < 3; ++d) {
-    const double a2 = (-6.0 * da[d] - hd * (4.0 * jo[d] + 2.0 * jn[d])) * ih2;
-    s3[d] = (12.0 * da[d] + 6.0 * hd * (jo[d] + jn[d])) * ih3;
-    s2[d] = a2 + hd * s3[d];
-  }
-  const double an = norm3(a1x, a1y, a1z), jnn = norm3(j1x, j1y, j1z);
-  const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
-  const double want = sqrt(eta * (an * n2 + jnn * jnn) / (jnn * n3 + n2 * n2));
+  double want;
+  const bool rated = aarseth_dt(hd, eta, a0, j0, m, want);
   int k = b.level[i];
-  if (jnn > 0.0 && isfinite(want)) {
+  if (rated) {
     const double dtk = ldexp(dt_max, -k);
     if (want < dtk) {
       while (k < L && ldexp(dt_max, -k) > want) ++k;
@@ -997,49 +959,72 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64
 }
 
 // ---------------------------------------------------------------------------------------
-// Host launchers.
+// Host launchers: validate, compute the grid, dispatch.
 
-// A rank's slice of a multi-rank run (never with collisions or block steps).
+template <typename... P, typename... A>
+static hipError_t hlaunch(void (*kernel)(P...), dim3 grid, hipStream_t s, const A&... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, args...);
+  return hipGetLastError();
+}
+
+// Workgroups of one thread per row.
+static dim3 row_grid(int64_t rows) { return dim3((unsigned)(rows / kBlock)); }
+
+// A rank's slice of a multi-rank run.
 template <typename T, typename S>
 static bool is_slice(const HArgs<T, S>& a) { return a.n_loc != a.n_pad; }
 
-template <typename T, typename S, int IPL>
-static hipError_t launch_eval_t(const HArgs<T, S>& a, int groups, bool gated, hipStream_t s) {
-  if (is_slice(a)) {
-    const dim3 grid((unsigned)(a.n_loc / (kBlock * IPL)), (unsigned)groups);
-    if (a.phi)
-      hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S, false, true>), grid,
-                         dim3(kBlock), 0, s, a, (int)gated);
-    else
-      hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S, false, true>), grid,
-                         dim3(kBlock), 0, s, a, (int)gated);
-    return hipGetLastError();
+// The forms that are built (the one place that says so).
+// Rows::All and Rows::List have PHI x NN; a slice never carries
+// collisions (nor block state: slice_ok), so Rows::Slice has PHI alone. The evaluate kernels
+// come with 1 or 2 i-bodies per lane, and with 4 where the pair type is fp32, except mixed
+// precision with collisions on: that kernel would need all 256 VGPRs, and the runtime's launch
+// shape (hermite.hip) never asks for it.
+template <typename K>
+constexpr bool eval_built(int ipl) {
+  return ipl == 1 || ipl == 2 || (ipl == 4 && sizeof(typename K::T) == 4 && !(K::DS && K::NN));
+}
+
+bool hermite_ipl_ok(int fp64, int ipl) { return ipl == 1 || ipl == 2 || (ipl == 4 && !fp64); }
+
+// f(HVariant) for the run's settings. Over::List: the block step's kernels, which work on the
+// active list; Over::Run: all rows, or the rank's slice. Sums::Pairs: the kernels that sum pairs
+// come with and without the potential (a.phi); the others have the one form, PHI off.
+enum class Over { Run, List };
+enum class Sums { None, Pairs };
+
+template <Rows R, Sums P, typename T, typename S, typename F>
+static hipError_t with_flags(const HArgs<T, S>& a, F&& f) {
+  constexpr bool kPhi = P == Sums::Pairs, kNN = R != Rows::Slice;
+  if (a.nn && !kNN) return hipErrorInvalidValue;
+  const bool phi = kPhi && a.phi;
+  if constexpr (kPhi && kNN)
+    if (phi && a.nn) return f(HVariant<T, S, true, true, R>());
+  if constexpr (kPhi)
+    if (phi) return f(HVariant<T, S, true, false, R>());
+  if constexpr (kNN)
+    if (a.nn) return f(HVariant<T, S, false, true, R>());
+  return f(HVariant<T, S, false, false, R>());
+}
+
+template <Over O, Sums P, typename T, typename S, typename F>
+static hipError_t with_variant(const HArgs<T, S>& a, F&& f) {
+  if constexpr (O == Over::List) {
+    return with_flags<Rows::List, P>(a, f);
+  } else {
+    if (is_slice(a)) return with_flags<Rows::Slice, P>(a, f);
+    return with_flags<Rows::All, P>(a, f);
   }
-  const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
-  // Mixed precision with collisions on would need all 256 VGPRs at 4 i-bodies per lane: that
-  // kernel is not built, and the runtime's launch shape never asks for it (hermite.hip).
-  constexpr bool kNoNN = IPL == 4 && sizeof(S) != sizeof(T);
-  if constexpr (kNoNN) {
-    if (a.nn) return hipErrorInvalidValue;
-  }
-  if constexpr (!kNoNN) {
-    if (a.nn) {
-      if (a.phi)
-        hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S, true>), grid,
-                           dim3(kBlock), 0, s, a, (int)gated);
-      else
-        hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S, true>), grid,
-                           dim3(kBlock), 0, s, a, (int)gated);
-      return hipGetLastError();
-    }
-  }
-  if (a.phi)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, false, S>), grid, dim3(kBlock), 0, s, a,
-                       (int)gated);
-  else
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, false, S>), grid, dim3(kBlock), 0, s, a,
-                       (int)gated);
-  return hipGetLastError();
+}
+
+// f(IPL) for the i-bodies per lane of an evaluate kernel of variant K.
+template <typename K, typename F>
+static hipError_t with_ipl(int ipl, F&& f) {
+  if (!eval_built<K>(ipl)) return hipErrorInvalidValue;
+  if (ipl == 1) return f(std::integral_constant<int, 1>());
+  if (ipl == 2) return f(std::integral_constant<int, 2>());
+  if constexpr (eval_built<K>(4)) return f(std::integral_constant<int, 4>());
+  return hipErrorInvalidValue;
 }
 
 // The arrays a collisions-on launch writes.
@@ -1049,85 +1034,69 @@ static bool nn_args_ok(const HArgs<T, S>& a) {
          a.n_pad <= INT32_MAX;
 }
 
-bool hermite_ipl_ok(int fp64, int ipl) { return ipl == 1 || ipl == 2 || (ipl == 4 && !fp64); }
+// The geometry of an evaluate launch: whole chunks of whole tiles, whole workgroups of ipl rows.
+template <typename T, typename S>
+static bool eval_geometry_ok(const HArgs<T, S>& a, int ipl) {
+  return hermite_ipl_ok(sizeof(T) == 8, ipl) && a.n_chunks >= 1 && a.n_pad % (kBlock * ipl) == 0 &&
+         a.chunk % Tile<T>::kBodies == 0 && (int64_t)a.n_chunks * a.chunk == a.n_pad &&
+         (sizeof(S) == sizeof(T) || a.XL) && (!a.nn || nn_args_ok(a));
+}
+
+// The rows row0 + [0, n_loc) of a launch: whole units of `unit` rows inside n_pad (one rank: all
+// of them); a slice carries no block state.
+template <typename T, typename S>
+static bool slice_ok(const HArgs<T, S>& a, int64_t unit) {
+  return a.row0 >= 0 && a.n_loc >= 1 && a.row0 + a.n_loc <= a.n_pad && a.n_loc % unit == 0 &&
+         a.row0 % kBlock == 0 && !(is_slice(a) && a.blk.bc);
+}
+
+static int clamp_groups(int groups, int n_chunks) {
+  return groups < 1 ? 1 : groups > n_chunks ? n_chunks : groups;
+}
 
 template <typename T, typename S>
 hipError_t launch_hermite_eval(const HArgs<T, S>& a, int ipl, int groups, bool gated,
                                hipStream_t s) {
-  if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
-      (int64_t)a.n_chunks * a.chunk != a.n_pad || (gated && !a.ctrl) ||
-      (sizeof(S) != sizeof(T) && !a.XL) || (a.nn && !nn_args_ok(a)))
+  if (!eval_geometry_ok(a, ipl) || (gated && !a.ctrl) || !slice_ok(a, (int64_t)kBlock * ipl))
     return hipErrorInvalidValue;
-  if (a.row0 < 0 || a.n_loc < 1 || a.row0 + a.n_loc > a.n_pad || a.n_loc % (kBlock * ipl) ||
-      a.row0 % kBlock || (is_slice(a) && (a.nn || a.blk.bc)))
-    return hipErrorInvalidValue;
-  if (groups < 1) groups = 1;
-  if (groups > a.n_chunks) groups = a.n_chunks;
-  switch (ipl) {
-    case 1: return launch_eval_t<T, S, 1>(a, groups, gated, s);
-    case 2: return launch_eval_t<T, S, 2>(a, groups, gated, s);
-    case 4:
-      if constexpr (sizeof(T) == 4) return launch_eval_t<T, S, 4>(a, groups, gated, s);
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
+  const dim3 grid((unsigned)(a.n_loc / (kBlock * ipl)), (unsigned)clamp_groups(groups, a.n_chunks));
+  return with_variant<Over::Run, Sums::Pairs>(a, [&](auto k) {
+    using K = decltype(k);
+    return with_ipl<K>(ipl, [&](auto n) {
+      return hlaunch(hermite_eval_kernel<K, decltype(n)::value>, grid, s, a, (int)gated);
+    });
+  });
 }
 
 template <typename T, typename S>
 hipError_t launch_hermite_ctrl(const HArgs<T, S>& a, hipStream_t s) {
-  hipLaunchKernelGGL(hermite_ctrl_kernel, dim3(1), dim3(kBlock), 0, s, a.ctrl, a.wgmin,
-                     (int)(a.n_pad / kBlock));
-  return hipGetLastError();
+  return hlaunch(hermite_ctrl_kernel, dim3(1), s, a.ctrl, a.wgmin, (int)(a.n_pad / kBlock));
 }
 
 template <typename T, typename S>
 hipError_t launch_hermite_predict(const HArgs<T, S>& a, hipStream_t s) {
-  if (is_slice(a)) {
-    if (a.nn || a.row0 < 0 || a.row0 % kBlock || a.n_loc % kBlock || a.row0 + a.n_loc > a.n_pad)
-      return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hermite_predict_kernel<T, S, false, true>),
-                       dim3((unsigned)(a.n_loc / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-  }
-  if (a.nn)
-    hipLaunchKernelGGL((hermite_predict_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((hermite_predict_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  if (is_slice(a) && !slice_ok(a, kBlock)) return hipErrorInvalidValue;
+  return with_variant<Over::Run, Sums::None>(a, [&](auto k) {
+    return hlaunch(hermite_predict_kernel<decltype(k)>, row_grid(a.n_loc), s, a);
+  });
 }
 
 hipError_t launch_hermite_split(const HArgs<float, double>& a, hipStream_t s) {
-  hipLaunchKernelGGL(hermite_split_kernel, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0, s,
-                     a);
-  return hipGetLastError();
+  return hlaunch(hermite_split_kernel, row_grid(a.n_pad), s, a);
 }
 
 template <typename T, typename S>
 hipError_t launch_hermite_stage(const HArgs<T, S>& a, hipStream_t s) {
   if (!a.R) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((hermite_stage_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
-                     dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  return hlaunch(hermite_stage_kernel<T, S>, row_grid(a.n_pad), s, a);
 }
 
 template <typename T, typename S>
 hipError_t launch_hermite_reduce(const HArgs<T, S>& a, hipStream_t s) {
-  if (is_slice(a)) {
-    if (a.nn || a.row0 < 0 || a.row0 % kBlock || a.n_loc % kBlock || a.row0 + a.n_loc > a.n_pad)
-      return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hermite_reduce_kernel<T, S, false, true>),
-                       dim3((unsigned)(a.n_loc / kBlock)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-  }
-  if (a.nn)
-    hipLaunchKernelGGL((hermite_reduce_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((hermite_reduce_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  if (is_slice(a) && !slice_ok(a, kBlock)) return hipErrorInvalidValue;
+  return with_variant<Over::Run, Sums::None>(a, [&](auto k) {
+    return hlaunch(hermite_reduce_kernel<decltype(k)>, row_grid(a.n_loc), s, a);
+  });
 }
 
 int32_t hermite_narrow_slice(int64_t n_pad) {
@@ -1139,22 +1108,18 @@ int32_t hermite_narrow_slice(int64_t n_pad) {
 
 template <typename T, typename S>
 hipError_t launch_block_next(const HArgs<T, S>& a, hipStream_t s) {
-  const unsigned nwg = (unsigned)(a.n_pad / kBlock);
-  hipLaunchKernelGGL((block_next_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
-  hipLaunchKernelGGL(block_ctrl_kernel, dim3(1), dim3(kBlock), 0, s, a.blk.bc, a.blk.wgnext,
-                     (int)nwg);
-  return hipGetLastError();
+  const hipError_t e = hlaunch(block_next_kernel<T, S>, row_grid(a.n_pad), s, a);
+  if (e != hipSuccess) return e;
+  return hlaunch(block_ctrl_kernel, dim3(1), s, a.blk.bc, a.blk.wgnext, (int)(a.n_pad / kBlock));
 }
 
 template <typename T, typename S>
 hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s) {
-  const unsigned nwg = (unsigned)(a.n_pad / kBlock);
-  if (a.nn)
-    hipLaunchKernelGGL((block_predict_kernel<T, S, true>), dim3(nwg), dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((block_predict_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
-  hipLaunchKernelGGL((block_compact_kernel<T, S>), dim3(nwg), dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  const hipError_t e = with_variant<Over::List, Sums::None>(a, [&](auto k) {
+    return hlaunch(block_predict_kernel<decltype(k)>, row_grid(a.n_pad), s, a);
+  });
+  if (e != hipSuccess) return e;
+  return hlaunch(block_compact_kernel<T, S>, row_grid(a.n_pad), s, a);
 }
 
 template <typename T, typename S>
@@ -1167,69 +1132,33 @@ hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s) {
     return hipErrorInvalidValue;
   const int groups = (b.cap + kNarrowGroup - 1) / kNarrowGroup;
   const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
-  if (a.nn && a.phi)
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, true, S, true>), grid, dim3(kBlock), 0, s, a);
-  else if (a.nn)
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, false, S, true>), grid, dim3(kBlock), 0, s, a);
-  else if (a.phi)
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, true, S>), grid, dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((hermite_narrow_kernel<T, false, S>), grid, dim3(kBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-template <typename T, typename S, int IPL>
-static hipError_t launch_wide_t(const HArgs<T, S>& a, int groups, hipStream_t s) {
-  const dim3 grid((unsigned)(a.n_pad / (kBlock * IPL)), (unsigned)groups);
-  if (a.nn && a.phi)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true, S, true>), grid, dim3(kBlock), 0,
-                       s, a, 0);
-  else if (a.nn)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true, S, true>), grid, dim3(kBlock), 0,
-                       s, a, 0);
-  else if (a.phi)
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, true, true, S>), grid, dim3(kBlock), 0, s, a,
-                       0);
-  else
-    hipLaunchKernelGGL((hermite_eval_kernel<T, IPL, false, true, S>), grid, dim3(kBlock), 0, s, a,
-                       0);
-  return hipGetLastError();
+  return with_variant<Over::List, Sums::Pairs>(a, [&](auto k) {
+    return hlaunch(hermite_narrow_kernel<decltype(k)>, grid, s, a);
+  });
 }
 
 template <typename T, typename S>
 hipError_t launch_block_wide(const HArgs<T, S>& a, int ipl, int groups, hipStream_t s) {
-  if (a.n_chunks < 1 || a.n_pad % (kBlock * ipl) || a.chunk % Tile<T>::kBodies ||
-      (int64_t)a.n_chunks * a.chunk != a.n_pad || !a.blk.bc || !a.blk.list ||
-      (sizeof(S) != sizeof(T) && !a.XL) || (a.nn && !nn_args_ok(a)))
-    return hipErrorInvalidValue;
-  if (groups < 1) groups = 1;
-  if (groups > a.n_chunks) groups = a.n_chunks;
-  switch (ipl) {
-    case 1: return launch_wide_t<T, S, 1>(a, groups, s);
-    case 2: return launch_wide_t<T, S, 2>(a, groups, s);
-    case 4:
-      if constexpr (sizeof(T) == 4) return launch_wide_t<T, S, 4>(a, groups, s);
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
+  if (!eval_geometry_ok(a, ipl) || !a.blk.bc || !a.blk.list) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)clamp_groups(groups, a.n_chunks));
+  return with_variant<Over::List, Sums::Pairs>(a, [&](auto k) {
+    using K = decltype(k);
+    return with_ipl<K>(ipl, [&](auto n) {
+      return hlaunch(hermite_eval_kernel<K, decltype(n)::value>, grid, s, a, 0);
+    });
+  });
 }
 
 template <typename T, typename S>
 hipError_t launch_block_correct(const HArgs<T, S>& a, hipStream_t s) {
-  if (a.nn)
-    hipLaunchKernelGGL((block_correct_kernel<T, S, true>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((block_correct_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)),
-                       dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  return with_variant<Over::List, Sums::None>(a, [&](auto k) {
+    return hlaunch(block_correct_kernel<decltype(k)>, row_grid(a.n_pad), s, a);
+  });
 }
 
 template <typename T, typename S>
 hipError_t launch_block_init(const HArgs<T, S>& a, int64_t t0, hipStream_t s) {
-  hipLaunchKernelGGL((block_init_kernel<T, S>), dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock), 0,
-                     s, a, t0);
-  return hipGetLastError();
+  return hlaunch(block_init_kernel<T, S>, row_grid(a.n_pad), s, a, t0);
 }
 
 #define GS_HERMITE_INSTANTIATE(T, S)                                                          \

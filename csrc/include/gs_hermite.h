@@ -106,7 +106,7 @@ struct HArgs {
   // corrects rows row0 + [0, n_loc) (whole units of 1024 rows) against all j; PA / PJ are then
   // [n_chunks][n_loc], indexed by local row; every other array keeps its full length and the
   // runtime gathers the slices. One rank: row0 = 0, n_loc = n_pad, and the kernels are the
-  // forms without the SLICE flag.
+  // Rows::All forms.
   int64_t row0, n_loc;
 };
 

@@ -285,6 +285,28 @@ def test_collisions_off_refuses_the_queries(hip):
         eng.close()
 
 
+def test_mixed_collisions_asked_for_four_per_lane_runs_two(hip):
+    """Mixed precision with collisions on has no 4-bodies-per-lane evaluate kernel: the launch
+    shape caps ipl at 2, and the gathered (wide) evaluate of a block step runs with it, to the
+    bits of an engine that was asked for 2."""
+    n = 2049
+    b = _bodies("solar", n)
+    idx = np.arange(0, n, 3, dtype=np.int32)
+    got = {}
+    for ipl in (4, 2):
+        eng = _block_engine(n, "mixed", ipl=ipl)
+        try:
+            assert eng.native_layout["ipl"] == 2
+            eng.load(b)
+            got[ipl] = eng.derivs(active=idx, path="wide")
+        finally:
+            eng.close()
+    a4, j4 = got[4]
+    assert a4.shape == (len(idx), 4) and np.isfinite(a4).all() and np.isfinite(j4).all()
+    assert np.any(a4[:, :3] != 0.0)
+    assert np.array_equal(a4, got[2][0]) and np.array_equal(j4, got[2][1])
+
+
 # ---- 5. closest-approach record and overlap stop -------------------------------------------------
 @pytest.mark.parametrize("dtype,centre", [("fp64", (1.5e11, 0.7e11, -0.3e11)),
                                           ("mixed", (1.5e11, 0.7e11, -0.3e11)),
