@@ -9,6 +9,7 @@
 
 #include <cmath>
 #include <limits>
+#include <string>
 #include <type_traits>
 #include <vector>
 #include <stdint.h>
@@ -259,21 +260,85 @@ int accel_abs_range(const double* X4, int64_t n_real, int64_t i0, int64_t i1, do
   return 0;
 }
 
-// ---- 4th-order Hermite (Makino & Aarseth 1992) --------------------------------------------
-// Acceleration, jerk and potential of body i at (X4, V4): the arithmetic of the GPU kernel
-// (nbody_hermite.hip hinteract), chunk sums from zero in j order, added in chunk order.
+// ---- the rows of a pair loop ------------------------------------------------------------------
+// Position rows X (x, y, z, mu) and, where the operation needs them, lo rows L and velocity rows
+// V, all of the pair type T. fp32 and fp64 point at the caller's arrays. Mixed precision (fp64
+// state, fp32 pair arithmetic on double-single positions) fills the rows the GPU predictor hands
+// its pair kernels: X = (float(x), mu), L = (float(x - double(hi)), 0), V = (float(v), 0).
 template <typename T>
-inline void accjerk_one(const T* X4, const T* V4, int64_t n_real, int64_t i, int32_t chunk,
-                        T cut2, T eps2, T a4[4], T j4[4]) {
+struct Rows {
+  const T *X = nullptr, *L = nullptr, *V = nullptr;
+  std::vector<T> own;  // mixed: the storage of X, L (and V)
+};
+
+// S: the type of the caller's arrays; the pair type is float for MIXED and S otherwise.
+template <typename S, bool MIXED>
+using pair_t = std::conditional_t<MIXED, float, S>;
+
+// V4 null: no velocity rows (nn, knn).
+template <typename S, bool MIXED>
+Rows<pair_t<S, MIXED>> make_rows(const S* X4, const S* V4, int64_t n) {
+  Rows<pair_t<S, MIXED>> r;
+  if constexpr (!MIXED) {
+    r.X = X4;
+    r.V = V4;
+  } else {
+    r.own.resize((size_t)(V4 ? 12 : 8) * n);
+    float *H = r.own.data(), *L = H + 4 * n, *W = V4 ? L + 4 * n : nullptr;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+      for (int d = 0; d < 3; ++d) {
+        const float hi = (float)X4[4 * i + d];
+        H[4 * i + d] = hi;
+        L[4 * i + d] = (float)(X4[4 * i + d] - (double)hi);
+        if (W) W[4 * i + d] = (float)V4[4 * i + d];
+      }
+      H[4 * i + 3] = (float)X4[4 * i + 3];
+      L[4 * i + 3] = 0.0f;
+      if (W) W[4 * i + 3] = 0.0f;
+    }
+    r.X = H;
+    r.L = L;
+    r.V = W;
+  }
+  return r;
+}
+
+// The rows a driver serves: idx[0..n_idx), or (idx null) i0 + k. False, with the error set, for
+// a range or an index outside [0, n_real), or when the driver's own checks (args_ok) failed.
+bool rows_ok(const char* what, bool args_ok, const int32_t* idx, int64_t i0, int64_t n_idx,
+             int64_t n_real) {
+  const char* why = nullptr;
+  if (!args_ok || n_idx < 0 || (!idx && (i0 < 0 || i0 + n_idx > n_real))) why = "bad arguments";
+  for (int64_t k = 0; !why && idx && k < n_idx; ++k)
+    if (idx[k] < 0 || idx[k] >= n_real) why = "index out of range";
+  if (why) gs_set_error((std::string(what) + ": " + why).c_str());
+  return !why;
+}
+
+// ---- 4th-order Hermite (Makino & Aarseth 1992) --------------------------------------------
+// Acceleration, jerk and potential of body i at the rows r: the arithmetic of the GPU kernel
+// (nbody_hermite.hip hinteract), chunk sums in T from zero in j order, added in chunk order into
+// totals of type O (T, or double for mixed: the GPU's reduce). MIXED: the separation is
+// (h_j - h_i) + (l_j - l_i).
+template <typename T, bool MIXED, typename O>
+inline void accjerk_one(const Rows<T>& r, int64_t n_real, int64_t i, int32_t chunk, T cut2, T eps2,
+                        O a4[4], O j4[4]) {
+  const T *X4 = r.X, *L4 = r.L, *V4 = r.V;
   const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
   const T ui = V4[4 * i], vi = V4[4 * i + 1], wi = V4[4 * i + 2];
   const int64_t n_chunks = (n_real + chunk - 1) / chunk;
-  T tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
+  O tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
   for (int64_t c = 0; c < n_chunks; ++c) {
     T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
     const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
     for (int64_t j = j0; j < j1; ++j) {
-      const T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+      T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+      if (MIXED) {
+        dx = dx + (L4[4 * j] - L4[4 * i]);
+        dy = dy + (L4[4 * j + 1] - L4[4 * i + 1]);
+        dz = dz + (L4[4 * j + 2] - L4[4 * i + 2]);
+      }
       const T wx = V4[4 * j] - ui, wy = V4[4 * j + 1] - vi, wz = V4[4 * j + 2] - wi;
       const T r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
       const T inv = (r2 >= cut2) ? rsqrt_ref(r2) : T(0);
@@ -297,141 +362,35 @@ inline void accjerk_one(const T* X4, const T* V4, int64_t n_real, int64_t i, int
   j4[0] = sx; j4[1] = sy; j4[2] = sz; j4[3] = 0;
 }
 
-template <typename T>
-int accjerk_range(const T* X4, const T* V4, int64_t n_real, int64_t i0, int64_t i1,
-                  int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4) {
-  if (chunk <= 0 || i1 < i0 || i1 > n_real) {
-    gs_set_error("cpu_accjerk: bad arguments");
-    return -1;
-  }
+// Row k of the output is body idx[k] (a block step's active set), or (idx null) body i0 + k.
+template <typename S, bool MIXED>
+int accjerk_rows(const S* X4, const S* V4, int64_t n_real, const int32_t* idx, int64_t i0,
+                 int64_t n_idx, int32_t chunk, S cut2, S eps2, S* acc4, S* jerk4) {
+  using T = pair_t<S, MIXED>;
+  if (!rows_ok("cpu_accjerk", chunk > 0, idx, i0, n_idx, n_real)) return -1;
+  const Rows<T> r = make_rows<S, MIXED>(X4, V4, n_real);
 #pragma omp parallel for schedule(static)
-  for (int64_t i = i0; i < i1; ++i)
-    accjerk_one<T>(X4, V4, n_real, i, chunk, cut2, eps2, acc4 + 4 * (i - i0),
-                   jerk4 + 4 * (i - i0));
+  for (int64_t k = 0; k < n_idx; ++k)
+    accjerk_one<T, MIXED, S>(r, n_real, idx ? idx[k] : i0 + k, chunk, (T)cut2, (T)eps2,
+                             acc4 + 4 * k, jerk4 + 4 * k);
   return 0;
 }
 
-// The same sums for a list of bodies (a block step's active set): row k of the output is body
-// idx[k].
-template <typename T>
-int accjerk_idx(const T* X4, const T* V4, int64_t n_real, const int32_t* idx, int64_t n_idx,
-                int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4) {
-  if (chunk <= 0 || n_idx < 0 || (n_idx > 0 && !idx)) {
-    gs_set_error("cpu_accjerk_idx: bad arguments");
-    return -1;
-  }
-  for (int64_t k = 0; k < n_idx; ++k)
-    if (idx[k] < 0 || idx[k] >= n_real) {
-      gs_set_error("cpu_accjerk_idx: index out of range");
-      return -1;
-    }
-#pragma omp parallel for schedule(static)
-  for (int64_t k = 0; k < n_idx; ++k)
-    accjerk_one<T>(X4, V4, n_real, idx[k], chunk, cut2, eps2, acc4 + 4 * k, jerk4 + 4 * k);
-  return 0;
-}
-
-// ---- mixed precision: fp64 state, fp32 pair arithmetic on double-single positions ----------
-// The rows the GPU predictor hands its pair kernels: H = (float(x), mu), L = (float(x -
-// double(hi)), 0), W = (float(v), 0).
-struct MixedRows {
-  std::vector<float> H, L, W;
-  MixedRows(const double* X4, const double* V4, int64_t n) : H(4 * n), L(4 * n), W(4 * n) {
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < n; ++i) {
-      for (int d = 0; d < 3; ++d) {
-        const float hi = (float)X4[4 * i + d];
-        H[4 * i + d] = hi;
-        L[4 * i + d] = (float)(X4[4 * i + d] - (double)hi);
-        W[4 * i + d] = (float)V4[4 * i + d];
-      }
-      H[4 * i + 3] = (float)X4[4 * i + 3];
-      L[4 * i + 3] = W[4 * i + 3] = 0.0f;
-    }
-  }
-};
-
-// accjerk_one<float> with d = (h_j - h_i) + (l_j - l_i); the chunk sums are fp32 and are added
-// in fp64 in chunk order (the GPU's reduce).
-inline void accjerk_one_mixed(const MixedRows& r, int64_t n_real, int64_t i, int32_t chunk,
-                              float cut2, float eps2, double a4[4], double j4[4]) {
-  const float *H = r.H.data(), *L = r.L.data(), *W = r.W.data();
-  const float xi = H[4 * i], yi = H[4 * i + 1], zi = H[4 * i + 2];
-  const float lx = L[4 * i], ly = L[4 * i + 1], lz = L[4 * i + 2];
-  const float ui = W[4 * i], vi = W[4 * i + 1], wi = W[4 * i + 2];
-  const int64_t n_chunks = (n_real + chunk - 1) / chunk;
-  double tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    float ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
-    const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
-    for (int64_t j = j0; j < j1; ++j) {
-      const float dx = (H[4 * j] - xi) + (L[4 * j] - lx);
-      const float dy = (H[4 * j + 1] - yi) + (L[4 * j + 1] - ly);
-      const float dz = (H[4 * j + 2] - zi) + (L[4 * j + 2] - lz);
-      const float wx = W[4 * j] - ui, wy = W[4 * j + 1] - vi, wz = W[4 * j + 2] - wi;
-      const float r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
-      const float inv = (r2 >= cut2) ? rsqrt_ref(r2) : 0.0f;
-      const float inv2 = inv * inv;
-      const float mi = H[4 * j + 3] * inv;
-      const float s = mi * inv2;
-      const float dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
-      const float al = dw * (3.0f * inv2);
-      ax = std::fma(s, dx, ax);
-      ay = std::fma(s, dy, ay);
-      az = std::fma(s, dz, az);
-      jx = std::fma(s, std::fma(-al, dx, wx), jx);
-      jy = std::fma(s, std::fma(-al, dy, wy), jy);
-      jz = std::fma(s, std::fma(-al, dz, wz), jz);
-      ph += mi;
-    }
-    tx += ax; ty += ay; tz += az; tp += ph;
-    sx += jx; sy += jy; sz += jz;
-  }
-  a4[0] = tx; a4[1] = ty; a4[2] = tz; a4[3] = -tp;
-  j4[0] = sx; j4[1] = sy; j4[2] = sz; j4[3] = 0;
-}
-
-int accjerk_range_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0, int64_t i1,
-                        int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4) {
-  if (chunk <= 0 || i0 < 0 || i1 < i0 || i1 > n_real) {
-    gs_set_error("cpu_accjerk_mixed: bad arguments");
-    return -1;
-  }
-  const MixedRows r(X4, V4, n_real);
-#pragma omp parallel for schedule(static)
-  for (int64_t i = i0; i < i1; ++i)
-    accjerk_one_mixed(r, n_real, i, chunk, (float)cut2, (float)eps2, acc4 + 4 * (i - i0),
-                      jerk4 + 4 * (i - i0));
-  return 0;
-}
-
-int accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
-                      int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
-                      double* jerk4) {
-  if (chunk <= 0 || n_idx < 0 || (n_idx > 0 && !idx)) {
-    gs_set_error("cpu_accjerk_idx_mixed: bad arguments");
-    return -1;
-  }
-  for (int64_t k = 0; k < n_idx; ++k)
-    if (idx[k] < 0 || idx[k] >= n_real) {
-      gs_set_error("cpu_accjerk_idx_mixed: index out of range");
-      return -1;
-    }
-  const MixedRows r(X4, V4, n_real);
-#pragma omp parallel for schedule(static)
-  for (int64_t k = 0; k < n_idx; ++k)
-    accjerk_one_mixed(r, n_real, idx[k], chunk, (float)cut2, (float)eps2, acc4 + 4 * k,
-                      jerk4 + 4 * k);
-  return 0;
+// A list entry's idx may be null only for an empty list (a null idx means a range to the drivers).
+inline bool list_ok(const char* what, const int32_t* idx, int64_t n_idx) {
+  if (idx || n_idx == 0) return true;
+  gs_set_error((std::string(what) + ": bad arguments").c_str());
+  return false;
 }
 
 // ---- nearest neighbours (the NN flag of the GPU kernels) ------------------------------------
 // q_ij = r^2 - (R_i + R_j)^2 with the pair's own r^2 (one add, one fma), the smallest over the
 // real j != i whose pair the law does not zero, the lowest j on a tie (a strict less in j order);
-// (+inf, -1) when there is none. MIXED: the separation from double-single rows (H, L).
+// (+inf, -1) when there is none. MIXED: the separation from double-single rows (X, L).
 template <typename T, bool MIXED>
-inline void nn_one(const T* X4, const T* L4, const T* R, int64_t n_real, int64_t i, T cut2, T eps2,
+inline void nn_one(const Rows<T>& r, const T* R, int64_t n_real, int64_t i, T cut2, T eps2,
                    T* q_out, int32_t* nn_out) {
+  const T *X4 = r.X, *L4 = r.L;
   const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2], ri = R[i];
   T bq = std::numeric_limits<T>::infinity();
   int32_t bn = -1;
@@ -454,46 +413,22 @@ inline void nn_one(const T* X4, const T* L4, const T* R, int64_t n_real, int64_t
   *nn_out = bn;
 }
 
-// Bodies idx[0..n_idx) (idx null: i0 + k). X4 rows of 4, R n_real radii, all of type T.
-template <typename T>
-int nn_rows(const T* X4, const T* R, int64_t n_real, const int32_t* idx, int64_t i0, int64_t n_idx,
-            T cut2, T eps2, T* q, int32_t* nn) {
-  if (!X4 || !R || !q || !nn || n_idx < 0 || n_real > INT32_MAX ||
-      (!idx && (i0 < 0 || i0 + n_idx > n_real))) {
-    gs_set_error("cpu_nn: bad arguments");
+// Bodies idx[0..n_idx) (idx null: i0 + k). X4 rows of 4, R n_real radii, q: all of type S.
+template <typename S, bool MIXED>
+int nn_rows(const S* X4, const S* R, int64_t n_real, const int32_t* idx, int64_t i0, int64_t n_idx,
+            S cut2, S eps2, S* q, int32_t* nn) {
+  using T = pair_t<S, MIXED>;
+  if (!rows_ok("cpu_nn", X4 && R && q && nn && n_real <= INT32_MAX, idx, i0, n_idx, n_real))
     return -1;
-  }
-  for (int64_t k = 0; idx && k < n_idx; ++k)
-    if (idx[k] < 0 || idx[k] >= n_real) {
-      gs_set_error("cpu_nn: index out of range");
-      return -1;
-    }
-#pragma omp parallel for schedule(static)
-  for (int64_t k = 0; k < n_idx; ++k)
-    nn_one<T, false>(X4, nullptr, R, n_real, idx ? idx[k] : i0 + k, cut2, eps2, q + k, nn + k);
-  return 0;
-}
-
-int nn_rows_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx, int64_t i0,
-                  int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
-  if (!X4 || !R || !q || !nn || n_idx < 0 || n_real > INT32_MAX ||
-      (!idx && (i0 < 0 || i0 + n_idx > n_real))) {
-    gs_set_error("cpu_nn_mixed: bad arguments");
-    return -1;
-  }
-  for (int64_t k = 0; idx && k < n_idx; ++k)
-    if (idx[k] < 0 || idx[k] >= n_real) {
-      gs_set_error("cpu_nn_mixed: index out of range");
-      return -1;
-    }
-  const MixedRows r(X4, X4, n_real);  // (the velocity rows are not used)
-  std::vector<float> Rf(R, R + n_real);
+  const Rows<T> r = make_rows<S, MIXED>(X4, nullptr, n_real);
+  const std::vector<T> Rt(R, R + (MIXED ? n_real : 0));  // (mixed: the radii in fp32, once)
+  const T* Rp;
+  if constexpr (MIXED) Rp = Rt.data(); else Rp = R;
 #pragma omp parallel for schedule(static)
   for (int64_t k = 0; k < n_idx; ++k) {
-    float qf;
-    nn_one<float, true>(r.H.data(), r.L.data(), Rf.data(), n_real, idx ? idx[k] : i0 + k,
-                        (float)cut2, (float)eps2, &qf, nn + k);
-    q[k] = (double)qf;
+    T qt;
+    nn_one<T, MIXED>(r, Rp, n_real, idx ? idx[k] : i0 + k, (T)cut2, (T)eps2, &qt, nn + k);
+    q[k] = (S)qt;
   }
   return 0;
 }
@@ -506,8 +441,9 @@ int nn_rows_mixed(const double* X4, const double* R, int64_t n_real, const int32
 constexpr int kKnnMax = 8;
 
 template <typename T, bool MIXED, typename O>
-inline void knn_one(const T* X4, const T* L4, int64_t n_real, int64_t i, int32_t k, O* r2,
+inline void knn_one(const Rows<T>& rows, int64_t n_real, int64_t i, int32_t k, O* r2,
                     int32_t* idx) {
+  const T *X4 = rows.X, *L4 = rows.L;
   const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
   T r[kKnnMax];
   int32_t n[kKnnMax];
@@ -538,33 +474,19 @@ inline void knn_one(const T* X4, const T* L4, int64_t n_real, int64_t i, int32_t
   }
 }
 
-inline bool knn_args_ok(const void* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
-                        const void* r2, const void* idx) {
-  if (X4 && r2 && idx && n_real >= 1 && n_real <= INT32_MAX && i0 >= 0 && i1 >= i0 &&
-      i1 <= n_real && k >= 1 && k <= kKnnMax)
-    return true;
-  gs_set_error("cpu_knn: bad arguments (n >= 1, rows within [0, n], k in 1..8)");
-  return false;
-}
-
-template <typename T>
-int knn_rows(const T* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, T* r2,
+template <typename S, bool MIXED>
+int knn_rows(const S* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, S* r2,
              int32_t* idx) {
-  if (!knn_args_ok(X4, n_real, i0, i1, k, r2, idx)) return -1;
+  using T = pair_t<S, MIXED>;
+  if (!(X4 && r2 && idx && n_real >= 1 && n_real <= INT32_MAX && i0 >= 0 && i1 >= i0 &&
+        i1 <= n_real && k >= 1 && k <= kKnnMax)) {
+    gs_set_error("cpu_knn: bad arguments (n >= 1, rows within [0, n], k in 1..8)");
+    return -1;
+  }
+  const Rows<T> r = make_rows<S, MIXED>(X4, nullptr, n_real);
 #pragma omp parallel for schedule(static)
   for (int64_t i = i0; i < i1; ++i)
-    knn_one<T, false, T>(X4, nullptr, n_real, i, k, r2 + (i - i0) * k, idx + (i - i0) * k);
-  return 0;
-}
-
-int knn_rows_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
-                   double* r2, int32_t* idx) {
-  if (!knn_args_ok(X4, n_real, i0, i1, k, r2, idx)) return -1;
-  const MixedRows r(X4, X4, n_real);  // (the velocity rows are not used)
-#pragma omp parallel for schedule(static)
-  for (int64_t i = i0; i < i1; ++i)
-    knn_one<float, true, double>(r.H.data(), r.L.data(), n_real, i, k, r2 + (i - i0) * k,
-                                 idx + (i - i0) * k);
+    knn_one<T, MIXED, S>(r, n_real, i, k, r2 + (i - i0) * k, idx + (i - i0) * k);
   return 0;
 }
 
@@ -606,11 +528,7 @@ int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chun
     XP[4 * i + 3] = X4[4 * i + 3];
     VP[4 * i + 3] = 0;
   }
-  if constexpr (MIXED) {
-    if (accjerk_range_mixed(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
-  } else {
-    if (accjerk_range<T>(XP, VP, n, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
-  }
+  if (accjerk_rows<T, MIXED>(XP, VP, n, nullptr, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
   const T hh = h / T(2), h12 = (h * h) / T(12);
   const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
   double dtm = INFINITY;
@@ -675,70 +593,79 @@ int gs_cpu_step_f32(const float* X4, float* Xn4, float* vel4, int64_t n_real, in
 }
 int gs_cpu_accjerk_f64(const double* X4, const double* V4, int64_t n_real, int64_t i0, int64_t i1,
                        int32_t chunk, double cut2, double eps2, double* acc4, double* jerk4) {
-  return accjerk_range<double>(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+  return accjerk_rows<double, false>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2, acc4,
+                                     jerk4);
 }
 int gs_cpu_accjerk_f32(const float* X4, const float* V4, int64_t n_real, int64_t i0, int64_t i1,
                        int32_t chunk, float cut2, float eps2, float* acc4, float* jerk4) {
-  return accjerk_range<float>(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
-}
-int gs_cpu_accjerk_idx_f64(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
-                           int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
-                           double* jerk4) {
-  return accjerk_idx<double>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
-}
-int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, const int32_t* idx,
-                           int64_t n_idx, int32_t chunk, float cut2, float eps2, float* acc4,
-                           float* jerk4) {
-  return accjerk_idx<float>(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
-}
-int gs_cpu_nn_f64(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
-                  double cut2, double eps2, double* q, int32_t* nn) {
-  return nn_rows<double>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
-}
-int gs_cpu_nn_f32(const float* X4, const float* R, int64_t n_real, int64_t i0, int64_t i1,
-                  float cut2, float eps2, float* q, int32_t* nn) {
-  return nn_rows<float>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
-}
-int gs_cpu_nn_mixed(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
-                    double cut2, double eps2, double* q, int32_t* nn) {
-  return nn_rows_mixed(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
-}
-int gs_cpu_nn_idx_f64(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
-                      int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
-  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
-  return nn_rows<double>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
-}
-int gs_cpu_nn_idx_f32(const float* X4, const float* R, int64_t n_real, const int32_t* idx,
-                      int64_t n_idx, float cut2, float eps2, float* q, int32_t* nn) {
-  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
-  return nn_rows<float>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
-}
-int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
-                        int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
-  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
-  return nn_rows_mixed(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
-}
-int gs_cpu_knn_f64(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
-                   double* r2, int32_t* idx) {
-  return knn_rows<double>(X4, n_real, i0, i1, k, r2, idx);
-}
-int gs_cpu_knn_f32(const float* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, float* r2,
-                   int32_t* idx) {
-  return knn_rows<float>(X4, n_real, i0, i1, k, r2, idx);
-}
-int gs_cpu_knn_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
-                     double* r2, int32_t* idx) {
-  return knn_rows_mixed(X4, n_real, i0, i1, k, r2, idx);
+  return accjerk_rows<float, false>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2, acc4,
+                                    jerk4);
 }
 int gs_cpu_accjerk_mixed(const double* X4, const double* V4, int64_t n_real, int64_t i0,
                          int64_t i1, int32_t chunk, double cut2, double eps2, double* acc4,
                          double* jerk4) {
-  return accjerk_range_mixed(X4, V4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4);
+  return accjerk_rows<double, true>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2, acc4,
+                                    jerk4);
+}
+int gs_cpu_accjerk_idx_f64(const double* X4, const double* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, double cut2, double eps2, double* acc4,
+                           double* jerk4) {
+  if (!list_ok("cpu_accjerk_idx", idx, n_idx)) return -1;
+  return accjerk_rows<double, false>(X4, V4, n_real, idx, 0, n_idx, chunk, cut2, eps2, acc4,
+                                     jerk4);
+}
+int gs_cpu_accjerk_idx_f32(const float* X4, const float* V4, int64_t n_real, const int32_t* idx,
+                           int64_t n_idx, int32_t chunk, float cut2, float eps2, float* acc4,
+                           float* jerk4) {
+  if (!list_ok("cpu_accjerk_idx", idx, n_idx)) return -1;
+  return accjerk_rows<float, false>(X4, V4, n_real, idx, 0, n_idx, chunk, cut2, eps2, acc4,
+                                    jerk4);
 }
 int gs_cpu_accjerk_idx_mixed(const double* X4, const double* V4, int64_t n_real,
                              const int32_t* idx, int64_t n_idx, int32_t chunk, double cut2,
                              double eps2, double* acc4, double* jerk4) {
-  return accjerk_idx_mixed(X4, V4, n_real, idx, n_idx, chunk, cut2, eps2, acc4, jerk4);
+  if (!list_ok("cpu_accjerk_idx", idx, n_idx)) return -1;
+  return accjerk_rows<double, true>(X4, V4, n_real, idx, 0, n_idx, chunk, cut2, eps2, acc4,
+                                    jerk4);
+}
+int gs_cpu_nn_f64(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                  double cut2, double eps2, double* q, int32_t* nn) {
+  return nn_rows<double, false>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_f32(const float* X4, const float* R, int64_t n_real, int64_t i0, int64_t i1,
+                  float cut2, float eps2, float* q, int32_t* nn) {
+  return nn_rows<float, false>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_mixed(const double* X4, const double* R, int64_t n_real, int64_t i0, int64_t i1,
+                    double cut2, double eps2, double* q, int32_t* nn) {
+  return nn_rows<double, true>(X4, R, n_real, nullptr, i0, i1 - i0, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_f64(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows<double, false>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_f32(const float* X4, const float* R, int64_t n_real, const int32_t* idx,
+                      int64_t n_idx, float cut2, float eps2, float* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows<float, false>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_nn_idx_mixed(const double* X4, const double* R, int64_t n_real, const int32_t* idx,
+                        int64_t n_idx, double cut2, double eps2, double* q, int32_t* nn) {
+  if (!idx) { gs_set_error("cpu_nn_idx: null argument"); return -1; }
+  return nn_rows<double, true>(X4, R, n_real, idx, 0, n_idx, cut2, eps2, q, nn);
+}
+int gs_cpu_knn_f64(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                   double* r2, int32_t* idx) {
+  return knn_rows<double, false>(X4, n_real, i0, i1, k, r2, idx);
+}
+int gs_cpu_knn_f32(const float* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, float* r2,
+                   int32_t* idx) {
+  return knn_rows<float, false>(X4, n_real, i0, i1, k, r2, idx);
+}
+int gs_cpu_knn_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
+                     double* r2, int32_t* idx) {
+  return knn_rows<double, true>(X4, n_real, i0, i1, k, r2, idx);
 }
 double gs_cpu_hermite_first_dt_f64(const double* A4, const double* J4, int64_t n_real,
                                    double eta) {

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <initializer_list>
 #include <limits>
+#include <memory>
 #include <utility>
 #include <vector>
 
@@ -80,6 +81,11 @@ template <typename F>
 int by_dtype(const gs_hermite* h, F f) {
   if (is_mixed(h)) return f(float(), double());
   return h->esz == 4 ? f(float(), float()) : f(double(), double());
+}
+// f(S state type): fp32 rows for an fp32 run, fp64 rows for fp64 and mixed.
+template <typename F>
+auto by_state(const gs_hermite* h, F f) {
+  return h->esz == 4 ? f(float()) : f(double());
 }
 int nwg(const gs_hermite* h) { return (int)(h->n_pad / gs::kForceBlock); }
 bool multi(const gs_hermite* h) { return h->cfg.nranks > 1; }
@@ -141,17 +147,11 @@ int launch_shape(gs_hermite* h) {
   return 0;
 }
 
-// Write the control block for a run that stands at time t (stream-ordered). overlaps < 0: the
-// overlap count stays as it is.
+// Write the control block for a run that stands at time t (stream-ordered).
 int write_ctrl(gs_hermite* h, double t, uint64_t steps, double dt_last, double dt_min,
-               int64_t overlaps = -1) {
+               unsigned long long overlaps) {
   gs::HermiteCtrl c{};
-  if (overlaps < 0) {
-    if (read_ctrl(h, &c)) return -1;
-    overlaps = (int64_t)c.overlaps;
-    c = gs::HermiteCtrl{};
-  }
-  c.overlaps = (unsigned long long)overlaps;
+  c.overlaps = overlaps;
   c.ov_stop = h->nn == 2 ? 1 : 0;
   c.t = t;
   c.h = 0.0;
@@ -172,6 +172,15 @@ int read_ctrl(gs_hermite* h, gs::HermiteCtrl* c) {
   GS_HIP(hipMemcpyAsync(c, h->ctrl, sizeof(*c), hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+// The engine's settings changed: rewrite the control block where the run stands. overlaps < 0:
+// the overlap count stays as it is.
+int update_ctrl(gs_hermite* h, int64_t overlaps = -1) {
+  gs::HermiteCtrl c;
+  if (read_ctrl(h, &c)) return -1;
+  return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min,
+                    overlaps < 0 ? c.overlaps : (unsigned long long)overlaps);
 }
 
 // The evaluate kernels read the current (x, v) instead of a predicted state: in place, or
@@ -351,44 +360,74 @@ int step_t(gs_hermite* const* sh, int P, int32_t nsteps) {
   return 0;
 }
 
-// Host fp64 (n x 3 [+ w]) -> device rows of 4 (ghost rows zero).
-template <typename T>
+// Host fp64 (n x 3 [+ w]) -> device state rows of 4 (ghost rows zero).
 int upload_rows(gs_hermite* h, void* dst, const double* src3, const double* w, double wscale) {
-  std::vector<T> buf((size_t)h->n_pad * 4, T(0));
-  for (int64_t i = 0; i < h->n; ++i) {
-    for (int d = 0; d < 3; ++d) buf[4 * i + d] = (T)src3[3 * i + d];
-    if (w) buf[4 * i + 3] = (T)(wscale * w[i]);
-  }
-  GS_HIP(hipMemcpyAsync(dst, buf.data(), rows_bytes(h), hipMemcpyHostToDevice, h->stream));
-  GS_HIP(hipStreamSynchronize(h->stream));
-  return 0;
+  return by_state(h, [&](auto s) {
+    using T = decltype(s);
+    std::vector<T> buf((size_t)h->n_pad * 4, T(0));
+    for (int64_t i = 0; i < h->n; ++i) {
+      for (int d = 0; d < 3; ++d) buf[4 * i + d] = (T)src3[3 * i + d];
+      if (w) buf[4 * i + 3] = (T)(wscale * w[i]);
+    }
+    GS_HIP(hipMemcpyAsync(dst, buf.data(), rows_bytes(h), hipMemcpyHostToDevice, h->stream));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
 }
 
-template <typename T>
+// The first `comps` components of `rows` device state rows -> host fp64 (out null: nothing).
 int download_rows(gs_hermite* h, const void* src, int64_t rows, double* out, int comps) {
   if (!out) return 0;
-  std::vector<T> buf((size_t)rows * 4);
-  GS_HIP(hipMemcpyAsync(buf.data(), src, (size_t)rows * 4 * sizeof(T), hipMemcpyDeviceToHost,
-                        h->stream));
+  return by_state(h, [&](auto s) {
+    using T = decltype(s);
+    std::vector<T> buf((size_t)rows * 4);
+    GS_HIP(hipMemcpyAsync(buf.data(), src, (size_t)rows * 4 * sizeof(T), hipMemcpyDeviceToHost,
+                          h->stream));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < rows; ++i)
+      for (int d = 0; d < comps; ++d) out[comps * i + d] = (double)buf[4 * i + d];
+    return 0;
+  });
+}
+
+// The first `rows` entries of a (q, neighbour) pair of device arrays (a null output: skipped).
+int download_pair(gs_hermite* h, const double* dq, const int32_t* di, int64_t rows, double* q,
+                  int32_t* nn) {
+  if (q)
+    GS_HIP(hipMemcpyAsync(q, dq, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (nn)
+    GS_HIP(hipMemcpyAsync(nn, di, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
-  for (int64_t i = 0; i < rows; ++i)
-    for (int d = 0; d < comps; ++d) out[comps * i + d] = (double)buf[4 * i + d];
   return 0;
 }
 
-// q and neighbour of the first `rows` rows of the last HM_OUT reduce.
-int download_nn(gs_hermite* h, int64_t rows, double* q, int32_t* nn) {
-  if (!q && !nn) return 0;
-  if (!h->nn) { gs_set_error("hermite: collisions are off"); return -1; }
-  if (q)
-    GS_HIP(hipMemcpyAsync(q, h->q_out, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
-  if (nn)
-    GS_HIP(hipMemcpyAsync(nn, h->nn_out, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost,
-                          h->stream));
-  GS_HIP(hipStreamSynchronize(h->stream));
-  return 0;
-}
+// Two events around a stretch of a stream's work; destroyed on every way out of the scope.
+struct EventTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EventTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  int create() {
+    GS_HIP(hipEventCreate(&e0));
+    GS_HIP(hipEventCreate(&e1));
+    return 0;
+  }
+  int start(hipStream_t s) {
+    GS_HIP(hipEventRecord(e0, s));
+    return 0;
+  }
+  // Waits for the stretch to end; *ms: its milliseconds.
+  int stop(hipStream_t s, double* ms) {
+    float t = 0.0f;
+    GS_HIP(hipEventRecord(e1, s));
+    GS_HIP(hipEventSynchronize(e1));
+    GS_HIP(hipEventElapsedTime(&t, e0, e1));
+    *ms = (double)t;
+    return 0;
+  }
+};
 
 // The per-body records of a run that starts: no neighbour yet, no approach.
 int clear_records(gs_hermite* h, bool latest) {
@@ -405,14 +444,26 @@ int clear_records(gs_hermite* h, bool latest) {
   return 0;
 }
 
+// The neighbour partials of the narrow path, the one place that frees and allocates them: they
+// exist exactly while block mode has narrow slots and collisions (`nn`) are on.
+int size_nni(gs_hermite* h, bool nn) {
+  if (h->NNI) GS_HIP(hipFree(h->NNI));
+  h->NNI = nullptr;
+  if (h->block && h->blk.cap > 0 && nn)
+    GS_HIP(hipMalloc((void**)&h->NNI,
+                     (size_t)h->blk.n_slices * (size_t)h->blk.cap * sizeof(int32_t)));
+  return 0;
+}
+
 void free_nn(gs_hermite* h) {
-  for (void* p : {h->R, (void*)h->PN, (void*)h->NNI, (void*)h->nn_i, (void*)h->ca_i,
-                  (void*)h->nn_out, (void*)h->nn_q, (void*)h->ca_q, (void*)h->q_out})
+  for (void* p : {h->R, (void*)h->PN, (void*)h->nn_i, (void*)h->ca_i, (void*)h->nn_out,
+                  (void*)h->nn_q, (void*)h->ca_q, (void*)h->q_out})
     if (p) (void)hipFree(p);
   h->R = nullptr;
-  h->PN = h->NNI = h->nn_i = h->ca_i = h->nn_out = nullptr;
+  h->PN = h->nn_i = h->ca_i = h->nn_out = nullptr;
   h->nn_q = h->ca_q = h->q_out = nullptr;
   h->nn = 0;
+  (void)size_nni(h, false);
 }
 
 int set_wgmin(gs_hermite* h, double first) {
@@ -453,11 +504,10 @@ int32_t default_narrow_max(const gs_hermite* h) {
 
 void free_block(gs_hermite* h) {
   for (void* p : {(void*)h->blk.bc, (void*)h->blk.tb, (void*)h->blk.level, (void*)h->blk.list,
-                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ,
-                  (void*)h->NNI})
+                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ})
     if (p) (void)hipFree(p);
   h->blk = gs::HBlock{};
-  h->NNI = nullptr;
+  (void)size_nni(h, h->nn != 0);  // (no slots: freed)
 }
 
 // (Re)allocate the narrow partial buffer for narrow_max slots.
@@ -467,19 +517,15 @@ int set_narrow(gs_hermite* h, int32_t narrow_max) {
   GS_HIP(hipStreamSynchronize(h->stream));
   if (h->blk.NA) GS_HIP(hipFree(h->blk.NA));
   if (h->blk.NJ) GS_HIP(hipFree(h->blk.NJ));
-  if (h->NNI) GS_HIP(hipFree(h->NNI));
   h->blk.NA = h->blk.NJ = nullptr;
-  h->NNI = nullptr;
   h->blk.cap = narrow_max;
   h->narrow_max = narrow_max;
   if (narrow_max > 0) {
     const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->psz;
     GS_HIP(hipMalloc(&h->blk.NA, bytes));
     GS_HIP(hipMalloc(&h->blk.NJ, bytes));
-    if (h->nn)
-      GS_HIP(hipMalloc((void**)&h->NNI,
-                       (size_t)h->blk.n_slices * (size_t)narrow_max * sizeof(int32_t)));
   }
+  if (size_nni(h, h->nn != 0)) return -1;
   gs::HermiteBlockCtrl c;
   if (read_bctrl(h, &c)) return -1;
   c.narrow_max = narrow_max;
@@ -567,12 +613,8 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   if (write_bctrl(h, c)) return -1;
   gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_OUT, true);
   if (point_at_current(h, a)) return -1;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ms) {
-    GS_HIP(hipEventCreate(&e0));
-    GS_HIP(hipEventCreate(&e1));
-    GS_HIP(hipEventRecord(e0, h->stream));
-  }
+  EventTimer timer;
+  if (ms && (timer.create() || timer.start(h->stream))) return -1;
   for (int32_t r = 0; r < reps; ++r) {
     if (path == gs::HP_NARROW)
       GS_HIP((gs::launch_block_narrow<T, S>(a, h->stream)));
@@ -581,16 +623,11 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
     GS_HIP((gs::launch_block_correct<T, S>(a, h->stream)));
   }
   if (ms) {
-    float t = 0.0f;
-    GS_HIP(hipEventRecord(e1, h->stream));
-    GS_HIP(hipEventSynchronize(e1));
-    GS_HIP(hipEventElapsedTime(&t, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms = (double)t / reps;
+    if (timer.stop(h->stream, ms)) return -1;
+    *ms /= reps;
   }
-  if (download_rows<S>(h, h->a_out, n_idx, acc4, 4) ||
-      download_rows<S>(h, h->j_out, n_idx, jerk4, 4) || download_nn(h, n_idx, q, nn))
+  if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
+      ((q || nn) && download_pair(h, h->q_out, h->nn_out, n_idx, q, nn)))
     return -1;
   return write_bctrl(h, keep);
 }
@@ -645,13 +682,10 @@ int get_state_group(gs_hermite* const* sh, int P, double* pos, double* vel, doub
   gs_hermite* h = sh[0];
   GS_HIP(hipSetDevice(h->cfg.device));
   if (gather(sh, P, {G_X, G_V, G_A, G_J})) return -1;
-  const bool f32 = h->esz == 4;
   const std::pair<const void*, double*> rows[4] = {{h->X, pos}, {h->V, vel}, {h->A, acc},
                                                    {h->J, jerk}};
   for (const auto& r : rows)
-    if (f32 ? download_rows<float>(h, r.first, h->n, r.second, 3)
-            : download_rows<double>(h, r.first, h->n, r.second, 3))
-      return -1;
+    if (download_rows(h, r.first, h->n, r.second, 3)) return -1;
   if (mass)
     for (int64_t i = 0; i < h->n; ++i) mass[i] = h->mass_host[(size_t)i];
   for (int r = 1; r < P; ++r) GS_HIP(hipStreamSynchronize(sh[r]->stream));
@@ -669,35 +703,24 @@ int derivs_group(gs_hermite* const* sh, int P, double* acc4, double* jerk4, doub
         }))
       return -1;
   if (gather(sh, P, {G_AOUT, G_JOUT})) return -1;
-  const bool f32 = h->esz == 4;
-  if (f32 ? download_rows<float>(h, h->a_out, h->n, acc4, 4)
-          : download_rows<double>(h, h->a_out, h->n, acc4, 4))
-    return -1;
-  if (f32 ? download_rows<float>(h, h->j_out, h->n, jerk4, 4)
-          : download_rows<double>(h, h->j_out, h->n, jerk4, 4))
+  if (download_rows(h, h->a_out, h->n, acc4, 4) || download_rows(h, h->j_out, h->n, jerk4, 4))
     return -1;
   for (int r = 1; r < P; ++r) GS_HIP(hipStreamSynchronize(sh[r]->stream));
-  return download_nn(h, h->n, q, nn);
+  return q || nn ? download_pair(h, h->q_out, h->nn_out, h->n, q, nn) : 0;
 }
 
 // Milliseconds per evaluate launch at the engine's current predicted rows.
 template <typename T, typename S>
 int time_eval_t(gs_hermite* h, int32_t reps, double* ms) {
   const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  GS_HIP(hipEventCreate(&e0));
-  GS_HIP(hipEventCreate(&e1));
+  EventTimer timer;
+  if (timer.create()) return -1;
   GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));  // warm
-  GS_HIP(hipEventRecord(e0, h->stream));
+  if (timer.start(h->stream)) return -1;
   for (int32_t k = 0; k < reps; ++k)
     GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));
-  GS_HIP(hipEventRecord(e1, h->stream));
-  GS_HIP(hipEventSynchronize(e1));
-  float t = 0.0f;
-  GS_HIP(hipEventElapsedTime(&t, e0, e1));
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  *ms = (double)t / reps;
+  if (timer.stop(h->stream, ms)) return -1;
+  *ms /= reps;
   return 0;
 }
 
@@ -728,7 +751,9 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   const int fp64 = cfg->dtype == GS_FP64;  // (the pair kernels': mixed takes fp32's launch shape)
   const int32_t chunk = cfg->chunk > 0 ? cfg->chunk : gs::auto_chunk(cfg->n);
   if (chunk % 1024) { gs_set_error("hermite: chunk must be a multiple of 1024"); return -1; }
-  gs_hermite* h = new gs_hermite();
+  // (a half-built engine is destroyed on every way out but the last)
+  std::unique_ptr<gs_hermite, int (*)(gs_hermite*)> guard(new gs_hermite(), gs_hermite_destroy);
+  gs_hermite* h = guard.get();
   h->cfg = *cfg;
   h->esz = cfg->dtype == GS_FP32 ? 4 : 8;
   h->psz = fp64 ? 8 : 4;
@@ -738,14 +763,10 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   h->n_chunks = (int32_t)(h->n_pad / chunk);
   for (int32_t q = 0; q < cfg->nranks; ++q) {
     int64_t b = 0, c = 0;
-    if (gs_hermite_partition(cfg->n, chunk, cfg->nranks, q, &b, &c)) {
-      delete h;
-      return -1;
-    }
+    if (gs_hermite_partition(cfg->n, chunk, cfg->nranks, q, &b, &c)) return -1;
     if (b >= cfg->n) {
       gs_set_error("hermite: more ranks than units of 1024 rows that hold a body (a rank would "
                    "own ghost rows only)");
-      delete h;
       return -1;
     }
     h->ubeg.push_back(b / kUnit);
@@ -754,52 +775,32 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   }
   h->row0 = h->ubeg[(size_t)cfg->rank] * kUnit;
   h->n_loc = h->ucnt[(size_t)cfg->rank] * kUnit;
-  if (launch_shape(h)) {
-    delete h;
-    return -1;
-  }
-  auto fail = [&](const char*) {
-    gs_hermite_destroy(h);
-    return -1;
-  };
-#define HM_TRY(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess) {                                                           \
-      char b_[256];                                                                   \
-      snprintf(b_, sizeof(b_), "hermite create: %s: %s", #call, hipGetErrorString(e_)); \
-      gs_set_error(b_);                                                               \
-      return fail(b_);                                                                \
-    }                                                                                 \
-  } while (0)
-  HM_TRY(hipSetDevice(cfg->device));
-  HM_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  HM_TRY(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
+  if (launch_shape(h)) return -1;
+  GS_HIP(hipSetDevice(cfg->device));
+  GS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  GS_HIP(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
   const size_t rb = rows_bytes(h), pb = (size_t)h->n_loc * 4 * h->psz;  // (partials: own rows)
   for (void** p : {&h->X, &h->V, &h->A, &h->J, &h->a_out, &h->j_out}) {
-    HM_TRY(hipMalloc(p, rb));
-    HM_TRY(hipMemsetAsync(*p, 0, rb, h->stream));
+    GS_HIP(hipMalloc(p, rb));
+    GS_HIP(hipMemsetAsync(*p, 0, rb, h->stream));
   }
   for (void** p : {&h->XP, &h->VP, &h->XL}) {
     if (p == &h->XL && !is_mixed(h)) continue;
-    HM_TRY(hipMalloc(p, pair_rows_bytes(h)));
-    HM_TRY(hipMemsetAsync(*p, 0, pair_rows_bytes(h), h->stream));
+    GS_HIP(hipMalloc(p, pair_rows_bytes(h)));
+    GS_HIP(hipMemsetAsync(*p, 0, pair_rows_bytes(h), h->stream));
   }
-  HM_TRY(hipMalloc(&h->PA, pb * (size_t)h->n_chunks));
-  HM_TRY(hipMalloc(&h->PJ, pb * (size_t)h->n_chunks));
-  HM_TRY(hipMalloc((void**)&h->ctrl, sizeof(gs::HermiteCtrl)));
-  HM_TRY(hipMalloc((void**)&h->wgmin, (size_t)nwg(h) * sizeof(double)));
-  HM_TRY(hipMalloc((void**)&h->mass_dev, (size_t)h->n_pad * sizeof(double)));
-  HM_TRY(hipMalloc((void**)&h->nonfinite, sizeof(unsigned long long)));
-  HM_TRY(hipStreamSynchronize(h->stream));
-#undef HM_TRY
+  GS_HIP(hipMalloc(&h->PA, pb * (size_t)h->n_chunks));
+  GS_HIP(hipMalloc(&h->PJ, pb * (size_t)h->n_chunks));
+  GS_HIP(hipMalloc((void**)&h->ctrl, sizeof(gs::HermiteCtrl)));
+  GS_HIP(hipMalloc((void**)&h->wgmin, (size_t)nwg(h) * sizeof(double)));
+  GS_HIP(hipMalloc((void**)&h->mass_dev, (size_t)h->n_pad * sizeof(double)));
+  GS_HIP(hipMalloc((void**)&h->nonfinite, sizeof(unsigned long long)));
+  GS_HIP(hipStreamSynchronize(h->stream));
   h->mass_host.assign((size_t)h->n, 0.0);
   if (set_wgmin(h, std::numeric_limits<double>::infinity()) ||
-      write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) {
-    gs_hermite_destroy(h);
+      write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0))
     return -1;
-  }
-  *out = h;
+  *out = guard.release();
   return 0;
 }
 
@@ -846,23 +847,18 @@ int gs_hermite_set_adaptive(gs_hermite* h, double eta, double dt_max, double t_e
   h->cfg.dt = dt_max;
   h->has_end = t_end >= 0.0;  // (a negative or NaN t_end: no end time)
   h->t_end = h->has_end ? t_end : 0.0;
-  gs::HermiteCtrl c;
-  if (read_ctrl(h, &c)) return -1;
-  return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min);
+  return update_ctrl(h);
 }
 
 int gs_hermite_init_ics(gs_hermite* h, int32_t ic, uint64_t seed) {
   GS_HIP(hipSetDevice(h->cfg.device));
-  hipError_t e;
-  if (h->esz == 4)
-    e = gs::launch_init_ics<float>(ic, seed, h->n, h->n_pad, 0, h->n_pad, h->cfg.G,
-                                   static_cast<float*>(h->X), static_cast<float*>(h->V),
-                                   h->mass_dev, h->stream);
-  else
-    e = gs::launch_init_ics<double>(ic, seed, h->n, h->n_pad, 0, h->n_pad, h->cfg.G,
-                                    static_cast<double*>(h->X), static_cast<double*>(h->V),
-                                    h->mass_dev, h->stream);
-  GS_HIP(e);
+  const hipError_t launched = by_state(h, [&](auto s) {
+    using T = decltype(s);
+    return gs::launch_init_ics<T>(ic, seed, h->n, h->n_pad, 0, h->n_pad, h->cfg.G,
+                                  static_cast<T*>(h->X), static_cast<T*>(h->V), h->mass_dev,
+                                  h->stream);
+  });
+  GS_HIP(launched);
   GS_HIP(hipMemcpyAsync(h->mass_host.data(), h->mass_dev, (size_t)h->n * sizeof(double),
                         hipMemcpyDeviceToHost, h->stream));
   GS_HIP(hipStreamSynchronize(h->stream));
@@ -874,12 +870,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
                          double dt_min) {
   if (!pos || !vel || !mass) { gs_set_error("hermite set_state: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
-  const bool f32 = h->esz == 4;
-  if (f32 ? upload_rows<float>(h, h->X, pos, mass, h->cfg.G)
-          : upload_rows<double>(h, h->X, pos, mass, h->cfg.G))
-    return -1;
-  if (f32 ? upload_rows<float>(h, h->V, vel, nullptr, 0.0)
-          : upload_rows<double>(h, h->V, vel, nullptr, 0.0))
+  if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
     return -1;
   h->mass_host.assign(mass, mass + h->n);
   // block mode: the run stands at a whole number of steps of dt (a synchronised state)
@@ -894,15 +885,11 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
     gs::HermiteCtrl c;
     if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
     return write_ctrl(h, t, 0, 0.0,
-                      dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity());
+                      dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity(), c.overlaps);
   }
   // A resumed run: a, j as the last step left them, and the step size its criterion chose.
   if (clear_records(h, true)) return -1;
-  if (f32 ? upload_rows<float>(h, h->A, acc, nullptr, 0.0)
-          : upload_rows<double>(h, h->A, acc, nullptr, 0.0))
-    return -1;
-  if (f32 ? upload_rows<float>(h, h->J, jerk, nullptr, 0.0)
-          : upload_rows<double>(h, h->J, jerk, nullptr, 0.0))
+  if (upload_rows(h, h->A, acc, nullptr, 0.0) || upload_rows(h, h->J, jerk, nullptr, 0.0))
     return -1;
   if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
   if (h->block && block_start(h, macro)) return -1;  // (levels afresh until set_block_state)
@@ -949,29 +936,27 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   if (!h || !out) { gs_set_error("hermite status: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
   if (!h->ring.empty() && wait_seen(h, h->rec)) return -1;  // (an RCCL run: a bounded wait)
+  *out = gs_hermite_info{};
+  out->ipl = h->ipl;
+  gs::HermiteBlockCtrl b;
+  if (h->block && read_bctrl(h, &b)) return -1;
+  gs::HermiteCtrl c;  // (block runs: the evaluation a run starts with counts its overlaps here)
+  if (read_ctrl(h, &c)) return -1;
   if (h->block) {
-    gs::HermiteBlockCtrl b;
-    if (read_bctrl(h, &b)) return -1;
-    *out = gs_hermite_info{};
     const int64_t macro = b.t_ticks >> b.L;
     out->time = b.dt_max * ldexp((double)b.t_ticks, -b.L);
     out->dt_last = out->dt_next = b.dt_max;
     out->dt_min = ldexp(b.dt_max, -b.level_max);
     out->steps = macro - h->macro0;
     out->finished = h->has_end && out->time >= h->t_end;
-    out->ipl = h->ipl;
     out->block_steps = (int64_t)b.block_steps;
     out->body_steps = (int64_t)b.body_steps;
     out->level_clamped = (int64_t)b.level_clamped;
     out->level_max = b.level_max;
     out->narrow_max = b.narrow_max;
-    gs::HermiteCtrl c0;  // (the evaluation a run starts with counts in the shared block)
-    if (read_ctrl(h, &c0)) return -1;
-    out->overlaps = (int64_t)(b.overlaps + c0.overlaps);
+    out->overlaps = (int64_t)(b.overlaps + c.overlaps);
     return 0;
   }
-  gs::HermiteCtrl c;
-  if (read_ctrl(h, &c)) return -1;
   double next = c.dt_max;
   if (c.eta > 0.0) {
     std::vector<double> w((size_t)nwg(h));
@@ -987,9 +972,6 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   out->dt_min = c.dt_min;
   out->steps = (int64_t)c.steps;
   out->finished = c.has_end && c.t >= c.t_end;
-  out->ipl = h->ipl;
-  out->block_steps = out->body_steps = out->level_clamped = 0;
-  out->level_max = out->narrow_max = 0;
   out->overlaps = (int64_t)c.overlaps;
   return 0;
 }
@@ -1139,9 +1121,7 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
   if (!on) {
     free_nn(h);
     if (launch_shape(h)) return -1;
-    gs::HermiteCtrl c;
-    if (read_ctrl(h, &c)) return -1;
-    return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0);
+    return update_ctrl(h, 0);
   }
   if (multi(h)) {
     gs_set_error("hermite collisions run on one rank");
@@ -1164,16 +1144,12 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
       GS_HIP(hipMalloc((void**)p, np * sizeof(double)));
       GS_HIP(hipMemsetAsync(*p, 0, np * sizeof(double), h->stream));
     }
-    if (h->block && h->blk.cap > 0)
-      GS_HIP(hipMalloc((void**)&h->NNI,
-                       (size_t)h->blk.n_slices * (size_t)h->blk.cap * sizeof(int32_t)));
+    if (size_nni(h, true)) return -1;
   }
   h->nn = on;
   if (launch_shape(h)) return -1;
   if (clear_records(h, true)) return -1;
-  gs::HermiteCtrl c;
-  if (read_ctrl(h, &c)) return -1;
-  return write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0);
+  return update_ctrl(h, 0);
 }
 
 int gs_hermite_set_radii(gs_hermite* h, const double* r) {
@@ -1185,50 +1161,33 @@ int gs_hermite_set_radii(gs_hermite* h, const double* r) {
       return -1;
     }
   GS_HIP(hipSetDevice(h->cfg.device));
-  std::vector<double> d((size_t)h->n_pad, 0.0);
-  std::vector<float> f;
-  for (int64_t i = 0; i < h->n; ++i) d[(size_t)i] = r[i];
-  const void* src = d.data();
-  if (h->esz == 4) {
-    f.assign(d.begin(), d.end());
-    src = f.data();
-  }
-  GS_HIP(hipMemcpyAsync(h->R, src, (size_t)h->n_pad * h->esz, hipMemcpyHostToDevice, h->stream));
-  GS_HIP(hipStreamSynchronize(h->stream));
-  return 0;
-}
-
-static int get_records(gs_hermite* h, const double* dq, const int32_t* di, double* q,
-                       int32_t* nn) {
-  if (q)
-    GS_HIP(hipMemcpyAsync(q, dq, (size_t)h->n * sizeof(double), hipMemcpyDeviceToHost,
-                          h->stream));
-  if (nn)
-    GS_HIP(hipMemcpyAsync(nn, di, (size_t)h->n * sizeof(int32_t), hipMemcpyDeviceToHost,
-                          h->stream));
-  GS_HIP(hipStreamSynchronize(h->stream));
-  return 0;
+  return by_state(h, [&](auto s) {
+    using T = decltype(s);
+    std::vector<T> d((size_t)h->n_pad, T(0));
+    for (int64_t i = 0; i < h->n; ++i) d[(size_t)i] = (T)r[i];
+    GS_HIP(hipMemcpyAsync(h->R, d.data(), d.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
 }
 
 int gs_hermite_neighbours(gs_hermite* h, double* q, int32_t* nn) {
   if (!h || !h->nn) { gs_set_error("hermite neighbours: collisions are off"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
-  return get_records(h, h->nn_q, h->nn_i, q, nn);
+  return download_pair(h, h->nn_q, h->nn_i, h->n, q, nn);
 }
 
 int gs_hermite_closest(gs_hermite* h, double* q, int32_t* nn, int32_t clear) {
   if (!h || !h->nn) { gs_set_error("hermite closest: collisions are off"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
-  if (get_records(h, h->ca_q, h->ca_i, q, nn)) return -1;
+  if (download_pair(h, h->ca_q, h->ca_i, h->n, q, nn)) return -1;
   return clear ? clear_records(h, false) : 0;
 }
 
 int gs_hermite_clear_overlap(gs_hermite* h) {
   if (!h) { gs_set_error("hermite clear_overlap: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
-  gs::HermiteCtrl c;
-  if (read_ctrl(h, &c)) return -1;
-  if (write_ctrl(h, c.t, c.steps, c.dt_last, c.dt_min, 0)) return -1;
+  if (update_ctrl(h, 0)) return -1;
   if (h->block) {
     gs::HermiteBlockCtrl b;
     if (read_bctrl(h, &b)) return -1;
@@ -1244,13 +1203,12 @@ int64_t gs_hermite_count_nonfinite(gs_hermite* h) {
     gs_set_error("hermite count_nonfinite: device error");
     return -1;
   }
-  hipError_t e = h->esz == 4
-      ? gs::launch_count_nonfinite<float>(static_cast<const float*>(h->X), h->row0, h->n_loc,
-                                          static_cast<const float*>(h->V) + 4 * h->row0,
-                                          h->nonfinite, h->stream)
-      : gs::launch_count_nonfinite<double>(static_cast<const double*>(h->X), h->row0, h->n_loc,
-                                           static_cast<const double*>(h->V) + 4 * h->row0,
-                                           h->nonfinite, h->stream);  // (the rows this rank owns)
+  const hipError_t e = by_state(h, [&](auto s) {  // (the rows this rank owns)
+    using T = decltype(s);
+    return gs::launch_count_nonfinite<T>(static_cast<const T*>(h->X), h->row0, h->n_loc,
+                                         static_cast<const T*>(h->V) + 4 * h->row0, h->nonfinite,
+                                         h->stream);
+  });
   unsigned long long cnt = 0;
   if (e != hipSuccess ||
       hipMemcpyAsync(&cnt, h->nonfinite, sizeof(cnt), hipMemcpyDeviceToHost, h->stream) !=

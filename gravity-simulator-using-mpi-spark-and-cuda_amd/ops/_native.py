@@ -136,37 +136,21 @@ def cpu_lib():
             _build("cpu")
         lib = ctypes.CDLL(str(path))
         _declare_common(lib)
-        for t, P in (("f64", _PD), ("f32", _PF)):
-            T = c_double if t == "f64" else c_float
-            _sig(lib, f"gs_cpu_accel_{t}", c_int32, [P, c_int64, c_int64, c_int64, c_int32, T, T, P])
-            _sig(lib, f"gs_cpu_step_{t}", c_int32,
-                 [P, P, P, c_int64, c_int64, c_int64, c_int32, T, T, T])
-            _sig(lib, f"gs_cpu_accjerk_{t}", c_int32,
-                 [P, P, c_int64, c_int64, c_int64, c_int32, T, T, P, P])
-            _sig(lib, f"gs_cpu_accjerk_idx_{t}", c_int32,
-                 [P, P, c_int64, POINTER(c_int32), c_int64, c_int32, T, T, P, P])
-            _sig(lib, f"gs_cpu_nn_{t}", c_int32,
-                 [P, P, c_int64, c_int64, c_int64, T, T, P, POINTER(c_int32)])
-            _sig(lib, f"gs_cpu_nn_idx_{t}", c_int32,
-                 [P, P, c_int64, POINTER(c_int32), c_int64, T, T, P, POINTER(c_int32)])
-            _sig(lib, f"gs_cpu_hermite_step_{t}", c_int32,
-                 [P, P, P, P, P, c_int64, c_int32, c_double, T, T, c_double, _PD])
-            _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, c_int64, c_double])
-        D = c_double  # mixed precision: the signatures of the f64 forms
-        _sig(lib, "gs_cpu_accjerk_mixed", c_int32,
-             [_PD, _PD, c_int64, c_int64, c_int64, c_int32, D, D, _PD, _PD])
-        _sig(lib, "gs_cpu_accjerk_idx_mixed", c_int32,
-             [_PD, _PD, c_int64, POINTER(c_int32), c_int64, c_int32, D, D, _PD, _PD])
-        _sig(lib, "gs_cpu_nn_mixed", c_int32,
-             [_PD, _PD, c_int64, c_int64, c_int64, D, D, _PD, POINTER(c_int32)])
-        _sig(lib, "gs_cpu_nn_idx_mixed", c_int32,
-             [_PD, _PD, c_int64, POINTER(c_int32), c_int64, D, D, _PD, POINTER(c_int32)])
-        _sig(lib, "gs_cpu_knn_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_int32, _PD, PI32])
-        _sig(lib, "gs_cpu_knn_f32", c_int32, [_PF, c_int64, c_int64, c_int64, c_int32, _PF, PI32])
-        _sig(lib, "gs_cpu_knn_mixed", c_int32, [_PD, c_int64, c_int64, c_int64, c_int32, _PD,
-                                                PI32])
-        _sig(lib, "gs_cpu_hermite_step_mixed", c_int32,
-             [_PD, _PD, _PD, _PD, _PD, c_int64, c_int32, D, D, D, D, _PD])
+        # One entry per operation and precision; mixed has the signatures of the f64 forms.
+        I, L = c_int32, c_int64
+        for t, P, T in (("f64", _PD, c_double), ("f32", _PF, c_float), ("mixed", _PD, c_double)):
+            ops = {"accjerk": [P, P, L, L, L, I, T, T, P, P],
+                   "accjerk_idx": [P, P, L, PI32, L, I, T, T, P, P],
+                   "nn": [P, P, L, L, L, T, T, P, PI32],
+                   "nn_idx": [P, P, L, PI32, L, T, T, P, PI32],
+                   "knn": [P, L, L, L, I, P, PI32],
+                   "hermite_step": [P, P, P, P, P, L, I, c_double, T, T, c_double, _PD]}
+            if t != "mixed":  # (the operations of _CPU_MIXED_FALLBACK)
+                ops["accel"] = [P, L, L, L, I, T, T, P]
+                ops["step"] = [P, P, P, L, L, L, I, T, T, T]
+                _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, L, c_double])
+            for stem, args in ops.items():
+                _sig(lib, f"gs_cpu_{stem}_{t}", c_int32, args)
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
                                                     c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_ld", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -337,6 +321,20 @@ def loaded_libraries() -> list[str]:
     if _hip is not None:
         out.append(str(NATIVE_DIR / "libgravsim_hip.so"))
     return out
+
+
+# The operations that have a mixed form, and what a mixed run calls for the others: the plain
+# stepper has no mixed precision and runs in fp32; first_dt reads a mixed run's fp64 a, j rows.
+_CPU_MIXED_OPS = ("accjerk", "accjerk_idx", "nn", "nn_idx", "knn", "hermite_step")
+_CPU_MIXED_FALLBACK = {"accel": "f32", "step": "f32", "hermite_first_dt": "f64"}
+
+
+def cpu_entry(lib, stem: str, dtype: str):
+    """(gs_cpu_<stem>_* of the precision "fp32" | "fp64" | "mixed", its row-pointer cast)."""
+    suf = {"fp32": "f32", "fp64": "f64", "mixed": "mixed"}[dtype]
+    if suf == "mixed" and stem not in _CPU_MIXED_OPS:
+        suf = _CPU_MIXED_FALLBACK[stem]
+    return getattr(lib, f"gs_cpu_{stem}_{suf}"), (fptr if suf == "f32" else dptr)
 
 
 def dptr(a):

@@ -25,8 +25,7 @@ def cpu_accelerations(pos, mass, dtype: str = "fp64", G: float = G_SI, cutoff: f
     X[:n, :3] = pos
     X[:n, 3] = G * np.asarray(mass, dtype=np.float64)
     out = np.zeros((n, 4), T)
-    fn = lib.gs_cpu_accel_f64 if dtype == "fp64" else lib.gs_cpu_accel_f32
-    ptr = _native.dptr if dtype == "fp64" else _native.fptr
+    fn, ptr = _native.cpu_entry(lib, "accel", dtype)
     _native.check(lib, fn(ptr(X), n, 0, n, L.chunk, T(cutoff * cutoff), T(softening ** 2),
                           ptr(out)), "cpu accel")
     out = out.astype(np.float64)

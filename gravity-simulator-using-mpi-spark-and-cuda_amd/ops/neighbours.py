@@ -30,9 +30,7 @@ def _cpu_k_nearest(pos, n: int, k: int, dtype: str):
     X[:, :3] = pos  # (fp32: rounded as the engines round; mixed: split natively)
     r2 = np.empty((n, k), T)
     idx = np.empty((n, k), np.int32)
-    fn = {"fp64": lib.gs_cpu_knn_f64, "fp32": lib.gs_cpu_knn_f32,
-          "mixed": lib.gs_cpu_knn_mixed}[dtype]
-    ptr = _native.fptr if dtype == "fp32" else _native.dptr
+    fn, ptr = _native.cpu_entry(lib, "knn", dtype)
     _native.check(lib, fn(ptr(X), n, 0, n, k, ptr(r2), idx.ctypes.data_as(_native.PI32)),
                   "cpu k_nearest")
     return r2.astype(np.float64), idx

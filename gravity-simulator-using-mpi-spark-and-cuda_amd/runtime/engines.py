@@ -375,10 +375,8 @@ class CpuEngine:
         self.V = np.zeros((L.n_local, 4), self.np_dtype)
         self.k = 0
         self.mass = np.zeros(cfg.n)
-        suf = "f64" if cfg.dtype == "fp64" else "f32"
-        self._step = getattr(self.lib, f"gs_cpu_step_{suf}")
-        self._accel = getattr(self.lib, f"gs_cpu_accel_{suf}")
-        self._ptr = _native.dptr if cfg.dtype == "fp64" else _native.fptr
+        self._step, self._ptr = _native.cpu_entry(self.lib, "step", cfg.dtype)
+        self._accel = _native.cpu_entry(self.lib, "accel", cfg.dtype)[0]
         if cfg.threads:
             self.lib.gs_cpu_set_threads(int(cfg.threads))
 

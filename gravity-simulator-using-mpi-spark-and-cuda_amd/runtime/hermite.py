@@ -473,12 +473,10 @@ class HermiteCpuEngine:
         self.A, self.J = np.zeros((n, 4), T), np.zeros((n, 4), T)
         self._scratch = np.zeros((4 * n, 4), T)
         self.mass = np.zeros(n)
-        suf = {"fp32": "f32", "fp64": "f64", "mixed": "mixed"}[cfg.dtype]
-        self._step = getattr(self.lib, f"gs_cpu_hermite_step_{suf}")
-        self._accjerk = getattr(self.lib, f"gs_cpu_accjerk_{suf}")
-        self._accjerk_idx = getattr(self.lib, f"gs_cpu_accjerk_idx_{suf}")
-        self._first_dt = getattr(
-            self.lib, "gs_cpu_hermite_first_dt_" + ("f32" if cfg.dtype == "fp32" else "f64"))
+        self._step, self._ptr = _native.cpu_entry(self.lib, "hermite_step", cfg.dtype)
+        self._accjerk, self._accjerk_idx, self._first_dt, self._nn, self._nn_idx = (
+            _native.cpu_entry(self.lib, stem, cfg.dtype)[0]
+            for stem in ("accjerk", "accjerk_idx", "hermite_first_dt", "nn", "nn_idx"))
         self.block = bool(cfg.block_steps)
         self.L = int(cfg.max_level)
         self.tb = np.zeros(n, dtype=np.int64)       # body times [ticks of dt 2^-L]
@@ -486,15 +484,12 @@ class HermiteCpuEngine:
         self.block_log: list[tuple[int, int]] = []  # (t_ticks, n_active) per block step
         self.body_steps = self.level_clamped = self.level_max = 0
         self._macro0 = 0
-        self._ptr = _native.fptr if cfg.dtype == "fp32" else _native.dptr
         self._cut2 = T(cfg.cutoff ** 2)
         self._eps2 = T(cfg.softening ** 2)
         self.t, self.dt_last, self.dt_min, self.k = 0.0, 0.0, math.inf, 0
         self._next = math.inf  # min_i dt_i of the last step (adaptive)
         # collisions: the records of the GPU engine (latest and closest (q, nn), overlap count)
         self.collisions = cfg.collisions != "off"
-        self._nn = getattr(self.lib, f"gs_cpu_nn_{suf}")
-        self._nn_idx = getattr(self.lib, f"gs_cpu_nn_idx_{suf}")
         self.radius = np.zeros(n)
         self._R = np.zeros(n, T)
         self._clear_records()

@@ -12,18 +12,24 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# The stand-alone programs under csrc/tests/ (each has its own main and prints "<name> ok").
+SELFTESTS = sorted(f[:-4] for f in os.listdir(os.path.join(ROOT, "csrc", "tests"))
+                   if f.endswith(".cpp"))
+
+
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
-def test_cpu_engine_asan_ubsan(tmp_path):
-    exe = tmp_path / "cpu_selftest"
+@pytest.mark.parametrize("name", SELFTESTS)
+def test_cpu_engine_asan_ubsan(tmp_path, name):
+    exe = tmp_path / name
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-fopenmp", "-fsanitize=address,undefined",
            "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined",
-           f"-I{ROOT}/csrc/include", f"{ROOT}/csrc/tests/cpu_selftest.cpp",
+           f"-I{ROOT}/csrc/include", f"{ROOT}/csrc/tests/{name}.cpp",
            f"{ROOT}/csrc/common/layout.cpp", f"{ROOT}/csrc/cpu/cpu_engine.cpp", "-o", str(exe)]
     subprocess.run(cmd, check=True, capture_output=True, timeout=300)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", OMP_NUM_THREADS="4")
     r = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "cpu_selftest ok" in r.stdout
+    assert f"{name} ok" in r.stdout
 
 
 def test_openmp_engine_deterministic_across_thread_counts():
