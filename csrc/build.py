@@ -35,7 +35,8 @@ HEADERS = sorted((CSRC / "include").glob("*.h"))
 CPU_SRC = [CSRC / "common" / "layout.cpp", CSRC / "cpu" / "cpu_engine.cpp"]
 HIP_SRC = [CSRC / "common" / "layout.cpp", CSRC / "hip" / "nbody_kernels.hip",
            CSRC / "hip" / "nbody_sym.hip", CSRC / "hip" / "nbody_hermite.hip",
-           CSRC / "hip" / "hermite.hip", CSRC / "hip" / "nbody_knn.hip",
+           CSRC / "hip" / "nbody_hermite6.hip", CSRC / "hip" / "hermite.hip",
+           CSRC / "hip" / "nbody_knn.hip",
            CSRC / "hip" / "nbody_mfma.hip", CSRC / "hip" / "comm_model.hip",
            CSRC / "hip" / "ipc.hip", CSRC / "hip" / "stepper.hip",
            CSRC / "hip" / "stepper_comm.hip", CSRC / "hip" / "stepper_plan.hip"]

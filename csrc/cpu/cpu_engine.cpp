@@ -24,6 +24,7 @@
 #endif
 
 #include "gravsim.h"
+#include "gs_hermite6.h"
 
 void gs_set_error(const char* msg);
 
@@ -562,9 +563,145 @@ int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chun
   return 0;
 }
 
+// ---- 6th-order Hermite (Nitadori & Makino 2008; gs_hermite6.h) ------------------------------
+// Acceleration, jerk, snap and potential of body i at (X4, V4, A4): the arithmetic of the GPU
+// kernel (nbody_hermite6.hip h6interact; its first part is accjerk_one's), chunk sums from zero
+// in j order, added in chunk order.
+template <typename T>
+inline void accjerksnap_one(const T* X4, const T* V4, const T* A4, int64_t n_real, int64_t i,
+                            int32_t chunk, T cut2, T eps2, T a4[4], T j4[4], T s4[4]) {
+  const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
+  const T ui = V4[4 * i], vi = V4[4 * i + 1], wi = V4[4 * i + 2];
+  const T bxi = A4[4 * i], byi = A4[4 * i + 1], bzi = A4[4 * i + 2];
+  const int64_t n_chunks = (n_real + chunk - 1) / chunk;
+  T tot[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t c = 0; c < n_chunks; ++c) {
+    T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0, sx = 0, sy = 0, sz = 0;
+    const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
+    for (int64_t j = j0; j < j1; ++j) {
+      const T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
+      const T wx = V4[4 * j] - ui, wy = V4[4 * j + 1] - vi, wz = V4[4 * j + 2] - wi;
+      const T qx = A4[4 * j] - bxi, qy = A4[4 * j + 1] - byi, qz = A4[4 * j + 2] - bzi;
+      const T r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
+      const T inv = (r2 >= cut2) ? rsqrt_ref(r2) : T(0);
+      const T inv2 = inv * inv;
+      const T mi = X4[4 * j + 3] * inv;
+      const T s = mi * inv2;
+      const T dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
+      const T i3 = T(3) * inv2;
+      const T al3 = dw * i3;
+      const T ww = std::fma(wz, wz, std::fma(wy, wy, wx * wx));
+      const T dq = std::fma(dz, qz, std::fma(dy, qy, dx * qx));
+      const T al = dw * inv2;
+      const T be3 = std::fma(al3, al, (ww + dq) * i3);
+      const T al6 = al3 + al3;
+      const T ux = std::fma(-al3, dx, wx), uy = std::fma(-al3, dy, wy),
+              uz = std::fma(-al3, dz, wz);
+      ax = std::fma(s, dx, ax);
+      ay = std::fma(s, dy, ay);
+      az = std::fma(s, dz, az);
+      jx = std::fma(s, ux, jx);
+      jy = std::fma(s, uy, jy);
+      jz = std::fma(s, uz, jz);
+      sx = std::fma(s, std::fma(-al6, ux, std::fma(-be3, dx, qx)), sx);
+      sy = std::fma(s, std::fma(-al6, uy, std::fma(-be3, dy, qy)), sy);
+      sz = std::fma(s, std::fma(-al6, uz, std::fma(-be3, dz, qz)), sz);
+      ph += mi;
+    }
+    const T part[10] = {ax, ay, az, ph, jx, jy, jz, sx, sy, sz};
+    for (int k = 0; k < 10; ++k) tot[k] += part[k];
+  }
+  a4[0] = tot[0]; a4[1] = tot[1]; a4[2] = tot[2]; a4[3] = -tot[3];
+  j4[0] = tot[4]; j4[1] = tot[5]; j4[2] = tot[6]; j4[3] = 0;
+  s4[0] = tot[7]; s4[1] = tot[8]; s4[2] = tot[9]; s4[3] = 0;
+}
+
+template <typename T>
+int accjerksnap_rows(const T* X4, const T* V4, const T* A4, int64_t n_real, int64_t i0,
+                     int64_t i1, int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4, T* snap4) {
+  if (!rows_ok("cpu_accjerksnap", chunk > 0 && X4 && V4 && A4 && acc4 && jerk4 && snap4, nullptr,
+               i0, i1 - i0, n_real))
+    return -1;
+#pragma omp parallel for schedule(static)
+  for (int64_t i = i0; i < i1; ++i)
+    accjerksnap_one<T>(X4, V4, A4, n_real, i, chunk, cut2, eps2, acc4 + 4 * (i - i0),
+                       jerk4 + 4 * (i - i0), snap4 + 4 * (i - i0));
+  return 0;
+}
+
+// One 6th-order step of size h in place (the GPU chain's predict / evaluate / correct
+// arithmetic, gs_hermite6.h). scratch: xp, vp, ap, a1, j1, s1 (n * 4 each).
+template <typename T>
+int hermite6_step(T* X4, T* V4, T* A4, T* J4, T* S4, T* C4, T* scratch, int64_t n, int32_t chunk,
+                  double hd, T cut2, T eps2, double eta, double* dt_min_out) {
+  if (chunk <= 0 || n < 1 || !(hd > 0.0) || !scratch || !X4 || !V4 || !A4 || !J4 || !S4 || !C4) {
+    gs_set_error("cpu_hermite6_step: bad arguments");
+    return -1;
+  }
+  T *XP = scratch, *VP = scratch + 4 * n, *AP = scratch + 8 * n, *A1 = scratch + 12 * n,
+    *J1 = scratch + 16 * n, *S1 = scratch + 20 * n;
+  const T h = (T)hd;
+  const gs::H6Taylor<T> tl = gs::h6_taylor(h);
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) {
+      const int64_t k = 4 * i + d;
+      gs::h6_predict(tl, X4[k], V4[k], A4[k], J4[k], S4[k], C4[k], XP[k], VP[k], AP[k]);
+    }
+    XP[4 * i + 3] = X4[4 * i + 3];
+    VP[4 * i + 3] = 0;
+    AP[4 * i + 3] = 0;
+  }
+  if (accjerksnap_rows<T>(XP, VP, AP, n, 0, n, chunk, cut2, eps2, A1, J1, S1)) return -1;
+  double dtm = INFINITY;
+#pragma omp parallel for schedule(static) reduction(min : dtm)
+  for (int64_t i = 0; i < n; ++i) {
+    double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
+    for (int d = 0; d < 3; ++d) {
+      const int64_t k = 4 * i + d;
+      T x1, v1;
+      gs::h6_correct(h, X4[k], V4[k], A4[k], J4[k], S4[k], A1[k], J1[k], S1[k], x1, v1);
+      a1[d] = A1[k]; j1[d] = J1[k]; s1[d] = S1[k];
+      gs::h6_high(hd, A4[k], J4[k], S4[k], a1[d], j1[d], s1[d], c1[d], p1[d], a5[d]);
+      X4[k] = x1; V4[k] = v1;
+      A4[k] = A1[k]; J4[k] = J1[k]; S4[k] = S1[k]; C4[k] = (T)c1[d];
+    }
+    A4[4 * i + 3] = 0; J4[4 * i + 3] = 0; S4[4 * i + 3] = 0; C4[4 * i + 3] = 0;
+    double d;
+    if (eta > 0.0 && gs::h6_dt(eta, a1, j1, s1, c1, p1, a5, d) && d < dtm) dtm = d;
+  }
+  if (dt_min_out) *dt_min_out = dtm;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gs_cpu_accjerksnap_f64(const double* X4, const double* V4, const double* A4, int64_t n_real,
+                           int64_t i0, int64_t i1, int32_t chunk, double cut2, double eps2,
+                           double* acc4, double* jerk4, double* snap4) {
+  return accjerksnap_rows<double>(X4, V4, A4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4,
+                                  snap4);
+}
+int gs_cpu_accjerksnap_f32(const float* X4, const float* V4, const float* A4, int64_t n_real,
+                           int64_t i0, int64_t i1, int32_t chunk, float cut2, float eps2,
+                           float* acc4, float* jerk4, float* snap4) {
+  return accjerksnap_rows<float>(X4, V4, A4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4,
+                                 snap4);
+}
+int gs_cpu_hermite6_step_f64(double* X4, double* V4, double* A4, double* J4, double* S4,
+                             double* C4, double* scratch, int64_t n_real, int32_t chunk, double h,
+                             double cut2, double eps2, double eta, double* dt_min_out) {
+  return hermite6_step<double>(X4, V4, A4, J4, S4, C4, scratch, n_real, chunk, h, cut2, eps2, eta,
+                               dt_min_out);
+}
+int gs_cpu_hermite6_step_f32(float* X4, float* V4, float* A4, float* J4, float* S4, float* C4,
+                             float* scratch, int64_t n_real, int32_t chunk, double h, float cut2,
+                             float eps2, double eta, double* dt_min_out) {
+  return hermite6_step<float>(X4, V4, A4, J4, S4, C4, scratch, n_real, chunk, h, cut2, eps2, eta,
+                              dt_min_out);
+}
 
 int gs_cpu_accel_abs_f64(const double* X4, int64_t n_real, int64_t i0, int64_t i1, double cut2,
                          double eps2, double* out8) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "gs_hermite.h"
+#include "gs_hermite6.h"
 #include "gs_stepper.h"
 
 struct gs_hermite {
@@ -68,6 +69,10 @@ struct gs_hermite {
   // bounded waits (RCCL runs): an event per chain in a ring; `seen` of `rec` have completed
   std::vector<hipEvent_t> ring;
   int64_t rec = 0, seen = 0;
+  // 6th-order scheme (gs_hermite_set_order): snap and crackle rows, the predicted acceleration,
+  // the snap partials and output
+  int32_t order = 4;
+  void *S = nullptr, *C = nullptr, *AP = nullptr, *PS = nullptr, *s_out = nullptr;
 };
 
 namespace {
@@ -299,6 +304,11 @@ int check_group(gs_hermite* const* sh, int P) {
   if (!sh || P < 1) { gs_set_error("hermite group: bad arguments"); return -1; }
   for (int r = 0; r < P; ++r)
     if (!sh[r]) { gs_set_error("hermite group: null shard"); return -1; }
+  for (int r = 0; r < P; ++r)
+    if (sh[r]->order != 4) {
+      gs_set_error("hermite group: order 6 runs on one rank (no virtual group, gs_hermite_group_*)");
+      return -1;
+    }
   if (P == 1) return 0;
   for (int r = 0; r < P; ++r) {
     const gs_hermite* h = sh[r];
@@ -632,7 +642,125 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   return write_bctrl(h, keep);
 }
 
+// ---- 6th order (one rank, fp32 or fp64, shared steps) ------------------------------------
+
+template <typename F>
+int by_dtype6(const gs_hermite* h, F f) {
+  return h->esz == 4 ? f(float()) : f(double());
+}
+
+template <typename T>
+gs::H6Args<T> make_args6(const gs_hermite* h, int mode, bool phi) {
+  gs::H6Args<T> a{};
+  a.X = static_cast<T*>(h->X); a.V = static_cast<T*>(h->V);
+  a.A = static_cast<T*>(h->A); a.J = static_cast<T*>(h->J);
+  a.S = static_cast<T*>(h->S); a.C = static_cast<T*>(h->C);
+  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.AP = static_cast<T*>(h->AP);
+  a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ); a.PS = static_cast<T*>(h->PS);
+  a.a_out = static_cast<T*>(h->a_out); a.j_out = static_cast<T*>(h->j_out);
+  a.s_out = static_cast<T*>(h->s_out);
+  a.ctrl = h->ctrl;
+  a.wgmin = h->wgmin;
+  a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
+  a.mode = mode;
+  a.phi = phi ? 1 : 0;
+  a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
+  a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
+  return a;
+}
+
+// Launch shape of the order-6 evaluate (any choice gives the same bits): 2 i-bodies per lane in
+// fp32 while that leaves about four workgroups per CU, else 1; chunk groups as launch_shape().
+int launch_shape6(gs_hermite* h) {
+  const int fp64 = h->cfg.dtype == GS_FP64;
+  const int64_t want = 1024;
+  int ipl = h->cfg.ipl;
+  if (ipl == 0)
+    ipl = !fp64 && h->n_pad / (gs::kForceBlock * 2) * h->n_chunks >= want ? 2 : 1;
+  if (!gs::hermite6_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
+    gs_set_error("hermite order 6: ipl must be 1 (or 2 for fp32)");
+    return -1;
+  }
+  h->ipl = ipl;
+  const int64_t blocks = h->n_pad / (gs::kForceBlock * ipl);
+  int64_t groups =
+      h->cfg.split_groups > 0 ? h->cfg.split_groups : (2 * want + blocks - 1) / blocks;
+  if (groups > h->n_chunks) groups = h->n_chunks;
+  if (groups < 1) groups = 1;
+  h->groups = (int32_t)groups;
+  return 0;
+}
+
+void free_order6(gs_hermite* h) {
+  for (void** p : {&h->S, &h->C, &h->AP, &h->PS, &h->s_out}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+}
+
+// a, j, s (and phi) of the current (x, v) through the step's own kernel, in two passes: the
+// first with ap = 0 gives a (and j), the second with ap = a gives s; then the reduce in `mode`
+// (HM_INIT: into the carried rows, c <- 0, and the first step's minima; HM_OUT: the outputs).
+template <typename T>
+int eval6_current(gs_hermite* h, int mode, bool phi) {
+  gs::H6Args<T> a = make_args6<T>(h, mode, false);
+  a.XP = a.X;
+  a.VP = a.V;
+  GS_HIP(hipMemsetAsync(h->AP, 0, rows_bytes(h), h->stream));
+  GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, false, h->stream)));
+  GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
+  GS_HIP(hipMemcpyAsync(h->AP, mode == gs::HM_INIT ? h->A : h->a_out, rows_bytes(h),
+                        hipMemcpyDeviceToDevice, h->stream));
+  a.phi = phi ? 1 : 0;
+  GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, false, h->stream)));
+  GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
+  return 0;
+}
+
+template <typename T>
+int step6_t(gs_hermite* h, int32_t nsteps) {
+  const gs::H6Args<T> a = make_args6<T>(h, gs::HM_STEP, false);
+  gs::HArgs<T, T> c{};  // (the control kernel reads these three)
+  c.ctrl = h->ctrl;
+  c.wgmin = h->wgmin;
+  c.n_pad = h->n_pad;
+  for (int32_t k = 0; k < nsteps; ++k) {
+    GS_HIP((gs::launch_hermite_ctrl<T, T>(c, h->stream)));
+    GS_HIP((gs::launch_hermite6_predict<T>(a, h->stream)));
+    GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, true, h->stream)));
+    GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
+  }
+  return 0;
+}
+
+int start6(gs_hermite* h) {
+  if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) return -1;
+  return by_dtype6(h, [&](auto t) {
+    return eval6_current<decltype(t)>(h, gs::HM_INIT, false);
+  });
+}
+
+int derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4) {
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (by_dtype6(h, [&](auto t) { return eval6_current<decltype(t)>(h, gs::HM_OUT, true); }))
+    return -1;
+  return download_rows(h, h->a_out, h->n, acc4, 4) || download_rows(h, h->j_out, h->n, jerk4, 4) ||
+                 download_rows(h, h->s_out, h->n, snap4, 4)
+             ? -1
+             : 0;
+}
+
+const char* refuse6(const gs_hermite* h) {
+  if (multi(h)) return "hermite order 6 runs on one rank (nranks > 1, --gpus, is refused)";
+  if (h->cfg.dtype == GS_MIXED)
+    return "hermite order 6 has no mixed precision (GS_MIXED, --dtype mixed, is refused)";
+  if (h->block) return "hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)";
+  if (h->nn) return "hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)";
+  return nullptr;
+}
+
 int start_from_state(gs_hermite* h) {
+  if (h->order == 6) return start6(h);
   if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) return -1;
   if (clear_records(h, true)) return -1;
   if (by_dtype(h, [&](auto t, auto s) {
@@ -816,6 +944,7 @@ int gs_hermite_destroy(gs_hermite* h) {
     if (p) (void)hipFree(p);
   free_block(h);
   free_nn(h);
+  free_order6(h);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -869,6 +998,10 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
                          const double* acc, const double* jerk, double t, double dt_next,
                          double dt_min) {
   if (!pos || !vel || !mass) { gs_set_error("hermite set_state: null argument"); return -1; }
+  // (order 6 carries a, j, s, c: without the last two the derivatives start afresh)
+  if (h->order == 6)
+    return gs_hermite_set_state6(h, pos, vel, mass, nullptr, nullptr, nullptr, nullptr, t, dt_next,
+                                 dt_min);
   GS_HIP(hipSetDevice(h->cfg.device));
   if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
     return -1;
@@ -908,11 +1041,14 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
 
 int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn) {
   if ((q || nn) && !h->nn) { gs_set_error("hermite derivs_nn: collisions are off"); return -1; }
+  if (h->order == 6) return derivs6(h, acc4, jerk4, nullptr);
   return derivs_group(&h, 1, acc4, jerk4, q, nn);
 }
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
+  if (h->order == 6)
+    return by_dtype6(h, [&](auto t) { return step6_t<decltype(t)>(h, nsteps); });
   return by_dtype(h, [&](auto t, auto s) {
     return h->block ? block_step_t<decltype(t), decltype(s)>(h, nsteps)
                     : step_t<decltype(t), decltype(s)>(&h, 1, nsteps);
@@ -987,6 +1123,10 @@ int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
   }
   if (multi(h)) {
     gs_set_error("hermite block steps (block_steps) run on one rank");
+    return -1;
+  }
+  if (h->order == 6) {
+    gs_set_error("hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)");
     return -1;
   }
   if (max_level < 0 || max_level > 40) {
@@ -1127,6 +1267,10 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
     gs_set_error("hermite collisions run on one rank");
     return -1;
   }
+  if (h->order == 6) {
+    gs_set_error("hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)");
+    return -1;
+  }
   if (h->n_pad > (int64_t)std::numeric_limits<int32_t>::max()) {
     gs_set_error("hermite set_collisions: too many bodies for int32 neighbour indices");
     return -1;
@@ -1169,6 +1313,80 @@ int gs_hermite_set_radii(gs_hermite* h, const double* r) {
     GS_HIP(hipStreamSynchronize(h->stream));
     return 0;
   });
+}
+
+int gs_hermite_set_order(gs_hermite* h, int32_t order) {
+  if (!h || (order != 4 && order != 6)) {
+    gs_set_error("hermite set_order: the order must be 4 or 6");
+    return -1;
+  }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  GS_HIP(hipStreamSynchronize(h->stream));
+  if (order == 4) {
+    free_order6(h);
+    h->order = 4;
+    return launch_shape(h);
+  }
+  if (const char* why = refuse6(h)) { gs_set_error(why); return -1; }
+  const int32_t ipl = h->ipl, groups = h->groups;
+  if (launch_shape6(h)) {
+    h->ipl = ipl;
+    h->groups = groups;
+    return -1;
+  }
+  if (h->order != 6) {
+    const size_t rb = rows_bytes(h);
+    for (void** p : {&h->S, &h->C, &h->AP, &h->s_out}) {
+      GS_HIP(hipMalloc(p, rb));
+      GS_HIP(hipMemsetAsync(*p, 0, rb, h->stream));
+    }
+    GS_HIP(hipMalloc(&h->PS, rb * (size_t)h->n_chunks));
+    GS_HIP(hipStreamSynchronize(h->stream));
+  }
+  h->order = 6;
+  return 0;
+}
+
+int32_t gs_hermite_get_order(gs_hermite* h) { return h ? h->order : 0; }
+
+int32_t gs_hermite6_ipl_ok(int32_t fp64, int32_t ipl) {
+  return gs::hermite6_ipl_ok(fp64, ipl) ? 1 : 0;
+}
+
+int gs_hermite_set_state6(gs_hermite* h, const double* pos, const double* vel, const double* mass,
+                          const double* acc, const double* jerk, const double* snap,
+                          const double* crackle, double t, double dt_next, double dt_min) {
+  if (!h || h->order != 6) { gs_set_error("hermite set_state6: the order is not 6"); return -1; }
+  if (!pos || !vel || !mass) { gs_set_error("hermite set_state6: null argument"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
+    return -1;
+  h->mass_host.assign(mass, mass + h->n);
+  const double dmin = dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity();
+  if (!acc || !jerk || !snap || !crackle) {
+    if (start6(h)) return -1;
+    gs::HermiteCtrl c;
+    if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
+    return write_ctrl(h, t, 0, 0.0, dmin, 0);
+  }
+  // A resumed run: a, j, s, c as the last step left them, and the step its criterion chose.
+  if (upload_rows(h, h->A, acc, nullptr, 0.0) || upload_rows(h, h->J, jerk, nullptr, 0.0) ||
+      upload_rows(h, h->S, snap, nullptr, 0.0) || upload_rows(h, h->C, crackle, nullptr, 0.0))
+    return -1;
+  if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
+  return write_ctrl(h, t, 0, 0.0, dmin, 0);
+}
+
+int gs_hermite_get_carried6(gs_hermite* h, double* snap, double* crackle) {
+  if (!h || h->order != 6) { gs_set_error("hermite get_carried6: the order is not 6"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return download_rows(h, h->S, h->n, snap, 3) || download_rows(h, h->C, h->n, crackle, 3) ? -1
+                                                                                            : 0;
+}
+
+int gs_hermite_derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4) {
+  if (!h || h->order != 6) { gs_set_error("hermite derivs6: the order is not 6"); return -1; }
+  return derivs6(h, acc4, jerk4, snap4);
 }
 
 int gs_hermite_neighbours(gs_hermite* h, double* q, int32_t* nn) {

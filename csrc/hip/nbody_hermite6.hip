@@ -1,0 +1,383 @@
+// gfx950 kernels of the 6th-order Hermite scheme (Nitadori & Makino 2008; gs_hermite6.h).
+//
+// The hot kernel evaluates, for every body i at the predicted state (xp, vp, ap),
+//     a_i = sum_j A_ij,   A_ij = mu_j d r^-3
+//     j_i = sum_j J_ij,   J_ij = mu_j w r^-3 - 3 alpha A_ij
+//     s_i = sum_j S_ij,   S_ij = mu_j q r^-3 - 6 alpha J_ij - 3 beta A_ij
+//     d = xp_j - xp_i, w = vp_j - vp_i, q = ap_j - ap_i, r^2 = |d|^2 + eps^2,
+//     alpha = (d.w) r^-2, beta = (|w|^2 + d.q) r^-2 + alpha^2
+// (and phi_i = -sum_j mu_j / r where asked), with the project's pair law: a pair contributes
+// exactly zero to all of them when r^2 < cutoff^2.
+//   * It follows hermite_eval_kernel (nbody_hermite.hip): one-sided, i-owned, no atomics; a lane
+//     owns IPL i-bodies and keeps their 9 sums (and phi) in registers.
+//   * A j-body is three rows, (x, y, z, mu), (v, 0) and (ap, 0), staged into double-buffered LDS
+//     tiles by LDS-DMA (tile_fill; 3 x 2 x 4 KiB = 24 KiB) and read back as broadcast
+//     ds_read_b128.
+//   * The pair term shares the acceleration and jerk arithmetic of the 4th-order kernel bit for
+//     bit (s = mu r^-1 r^-2, 3 alpha = (d.w)(3 r^-2), u = w - 3 alpha d) and adds
+//     S_ij = s (q - 6 alpha u - 3 beta d): never r^-5 or G m_i m_j. fp32 runs over pairs of i as
+//     2-vectors (v_pk_*), fp64 through rsqrt_dev.
+//   * Canonical chunked summation: every chunk is summed from zero in j order into
+//     PA / PJ / PS[chunk][i], and the reduce kernel adds the chunk sums in chunk order, so IPL
+//     and the number of chunk groups change the grid, never the bits.
+// Step chain (one stream, no host round trip): control (hermite_ctrl_kernel, shared with the
+// 4th-order chain) -> predict -> evaluate -> reduce + correct + next-step minima.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "gs_common.h"
+#include "gs_hermite6.h"
+#include "gs_tile.h"
+
+namespace gs {
+
+__device__ __forceinline__ float fmav(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fmav(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ f2 fmav(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+
+// 1 / sqrt(r2) where the pair law keeps the pair, else 0.
+__device__ __forceinline__ float inv_cut(float r2, float cut2) {
+  return r2 >= cut2 ? rsqrt_dev(r2) : 0.0f;
+}
+__device__ __forceinline__ f2 inv_cut(f2 r2, float cut2) {
+  f2 inv;
+  inv.x = r2.x >= cut2 ? rsqrt_dev(r2.x) : 0.0f;
+  inv.y = r2.y >= cut2 ? rsqrt_dev(r2.y) : 0.0f;
+  return inv;
+}
+__device__ __forceinline__ double inv_cut(double r2, double cut2) {
+  // Branch-free (as the 4th-order kernel): the refinement runs on 1 below the cutoff.
+  const bool ok = r2 >= cut2;
+  const double inv = rsqrt_dev(ok ? r2 : 1.0);
+  return ok ? inv : 0.0;
+}
+
+// The sums and the predicted rows of one i-body (V = T) or of a pair of them (V = f2).
+template <typename V>
+struct H6Body {
+  V x, y, z, u, v, w, bx, by, bz;                 // predicted position, velocity, acceleration
+  V ax, ay, az, ph, jx, jy, jz, sx, sy, sz;       // current chunk
+};
+
+template <typename V>
+__device__ __forceinline__ void h6reset(H6Body<V>& b) {
+  b.ax = b.ay = b.az = b.ph = b.jx = b.jy = b.jz = b.sx = b.sy = b.sz = V(0.0f);
+}
+
+// One i-j interaction (per element of V). The first 26 operations are hinteract()'s; the snap
+// adds 3 sub (q), 2 fma + mul (|w|^2), 2 fma + mul (d.q), add, mul, mul, fma (3 beta), add
+// (6 alpha), and 3 fma per component.
+template <bool PHI, typename V, typename T>
+__device__ __forceinline__ void h6interact(H6Body<V>& b, const V4<T>& xj, const V4<T>& vj,
+                                           const V4<T>& aj, T cut2, T eps2) {
+  const V dx = V(xj.x) - b.x, dy = V(xj.y) - b.y, dz = V(xj.z) - b.z;
+  const V wx = V(vj.x) - b.u, wy = V(vj.y) - b.v, wz = V(vj.z) - b.w;
+  const V qx = V(aj.x) - b.bx, qy = V(aj.y) - b.by, qz = V(aj.z) - b.bz;
+  const V r2 = fmav(dz, dz, fmav(dy, dy, fmav(dx, dx, V(eps2))));
+  const V inv = inv_cut(r2, cut2);
+  const V inv2 = inv * inv;
+  const V mi = V(xj.w) * inv;
+  const V s = mi * inv2;
+  const V dw = fmav(dz, wz, fmav(dy, wy, dx * wx));
+  const V i3 = V(T(3)) * inv2;
+  const V al3 = dw * i3;  // 3 alpha
+  const V ww = fmav(wz, wz, fmav(wy, wy, wx * wx));
+  const V dq = fmav(dz, qz, fmav(dy, qy, dx * qx));
+  const V al = dw * inv2;
+  const V be3 = fmav(al3, al, (ww + dq) * i3);  // 3 beta
+  const V al6 = al3 + al3;
+  const V ux = fmav(-al3, dx, wx), uy = fmav(-al3, dy, wy), uz = fmav(-al3, dz, wz);
+  b.ax = fmav(s, dx, b.ax);
+  b.ay = fmav(s, dy, b.ay);
+  b.az = fmav(s, dz, b.az);
+  b.jx = fmav(s, ux, b.jx);
+  b.jy = fmav(s, uy, b.jy);
+  b.jz = fmav(s, uz, b.jz);
+  b.sx = fmav(s, fmav(-al6, ux, fmav(-be3, dx, qx)), b.sx);
+  b.sy = fmav(s, fmav(-al6, uy, fmav(-be3, dy, qy)), b.sy);
+  b.sz = fmav(s, fmav(-al6, uz, fmav(-be3, dz, qz)), b.sz);
+  if constexpr (PHI) b.ph += mi;
+}
+
+// The lane's bodies: IPL of them as scalars, or (fp32, even IPL) IPL / 2 pairs as 2-vectors.
+template <typename T, int IPL>
+struct H6Lane {
+  static constexpr bool PK = sizeof(T) == 4 && IPL % 2 == 0;
+  using V = std::conditional_t<PK, f2, T>;
+  static constexpr int NB = PK ? IPL / 2 : IPL;
+  H6Body<V> b[NB];
+};
+
+template <typename V, typename T>
+__device__ __forceinline__ void h6set(V& dst, int e, T v) {
+  if constexpr (std::is_same<V, f2>::value) {
+    if (e == 0) dst.x = v; else dst.y = v;
+  } else {
+    dst = v;
+  }
+}
+
+template <typename V>
+__device__ __forceinline__ auto h6get(const V& src, int e) {
+  if constexpr (std::is_same<V, f2>::value) return e == 0 ? src.x : src.y;
+  else return src;
+}
+
+// EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
+// stores one partial per chunk and i-body: PA[c][i] = (ax, ay, az, sum mu / r),
+// PJ[c][i] = (jx, jy, jz, 0), PS[c][i] = (sx, sy, sz, 0).
+template <typename T, bool PHI, int IPL>
+__global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int gated) {
+  constexpr int TB = Tile<T>::kBodies;
+  using Lane = H6Lane<T, IPL>;
+  using V = typename Lane::V;
+  constexpr int E = Lane::PK ? 2 : 1;  // i-bodies per element group
+  __shared__ __attribute__((aligned(16))) V4<T> tx[2][TB];
+  __shared__ __attribute__((aligned(16))) V4<T> tv[2][TB];
+  __shared__ __attribute__((aligned(16))) V4<T> ta[2][TB];
+  if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
+  const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);
+  const int per = (a.n_chunks + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int c0 = (int)blockIdx.y * per;
+  const int c1 = min(c0 + per, a.n_chunks);
+  const int tpc = (int)(a.chunk / TB);  // tiles per chunk
+  const int ntiles = (c1 - c0) * tpc;
+  if (ntiles <= 0) return;
+  const V4<T>* XP = reinterpret_cast<const V4<T>*>(a.XP);
+  const V4<T>* VP = reinterpret_cast<const V4<T>*>(a.VP);
+  const V4<T>* AP = reinterpret_cast<const V4<T>*>(a.AP);
+  V4<T>* PA = reinterpret_cast<V4<T>*>(a.PA);
+  V4<T>* PJ = reinterpret_cast<V4<T>*>(a.PJ);
+  V4<T>* PS = reinterpret_cast<V4<T>*>(a.PS);
+  Lane ln;
+#pragma unroll
+  for (int k = 0; k < IPL; ++k) {
+    const int64_t row = ib + threadIdx.x + k * kBlock;
+    const V4<T> x = XP[row], v = VP[row], p = AP[row];
+    H6Body<V>& b = ln.b[k / E];
+    h6set(b.x, k % E, x.x); h6set(b.y, k % E, x.y); h6set(b.z, k % E, x.z);
+    h6set(b.u, k % E, v.x); h6set(b.v, k % E, v.y); h6set(b.w, k % E, v.z);
+    h6set(b.bx, k % E, p.x); h6set(b.by, k % E, p.y); h6set(b.bz, k % E, p.z);
+  }
+  auto fill = [&](int t) {
+    const int64_t j0 = (int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB;
+    tile_fill<T>(XP + j0, tx[t & 1]);
+    tile_fill<T>(VP + j0, tv[t & 1]);
+    tile_fill<T>(AP + j0, ta[t & 1]);
+  };
+  fill(0);
+#pragma unroll
+  for (int k = 0; k < Lane::NB; ++k) h6reset(ln.b[k]);
+  for (int t = 0; t < ntiles; ++t) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // tile t is in LDS for every wave; buffer (t+1)&1 is free
+    if (t + 1 < ntiles) fill(t + 1);
+    const V4<T>* cx = tx[t & 1];
+    const V4<T>* cv = tv[t & 1];
+    const V4<T>* ca = ta[t & 1];
+#pragma unroll 4
+    for (int j = 0; j < TB; ++j) {
+      const V4<T> xj = cx[j], vj = cv[j], aj = ca[j];  // uniform addresses: broadcast ds_reads
+#pragma unroll
+      for (int k = 0; k < Lane::NB; ++k) h6interact<PHI>(ln.b[k], xj, vj, aj, a.cut2, a.eps2);
+    }
+    if ((t + 1) % tpc == 0) {
+      const int c = c0 + t / tpc;
+#pragma unroll
+      for (int k = 0; k < IPL; ++k) {
+        const H6Body<V>& b = ln.b[k / E];
+        V4<T> oa, oj, os;
+        oa.x = h6get(b.ax, k % E); oa.y = h6get(b.ay, k % E); oa.z = h6get(b.az, k % E);
+        oa.w = h6get(b.ph, k % E);
+        oj.x = h6get(b.jx, k % E); oj.y = h6get(b.jy, k % E); oj.z = h6get(b.jz, k % E);
+        oj.w = T(0);
+        os.x = h6get(b.sx, k % E); os.y = h6get(b.sy, k % E); os.z = h6get(b.sz, k % E);
+        os.w = T(0);
+        const int64_t o = (int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock;
+        PA[o] = oa;
+        PJ[o] = oj;
+        PS[o] = os;
+      }
+#pragma unroll
+      for (int k = 0; k < Lane::NB; ++k) h6reset(ln.b[k]);
+    }
+  }
+}
+
+// PREDICT over the step's h (ghost rows stay zero).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(H6Args<T> a) {
+  if (!a.ctrl->active) return;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n_pad) return;
+  V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp, ap = xp;
+  if (i < a.n_real) {
+    const H6Taylor<T> t = h6_taylor((T)a.ctrl->h);
+    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
+    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
+    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
+    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const V4<T> sn = reinterpret_cast<const V4<T>*>(a.S)[i];
+    const V4<T> cr = reinterpret_cast<const V4<T>*>(a.C)[i];
+    T px, pv, pa;
+    h6_predict(t, x.x, v.x, ac.x, jk.x, sn.x, cr.x, px, pv, pa);
+    xp.x = px; vp.x = pv; ap.x = pa;
+    h6_predict(t, x.y, v.y, ac.y, jk.y, sn.y, cr.y, px, pv, pa);
+    xp.y = px; vp.y = pv; ap.y = pa;
+    h6_predict(t, x.z, v.z, ac.z, jk.z, sn.z, cr.z, px, pv, pa);
+    xp.z = px; vp.z = pv; ap.z = pa;
+    xp.w = x.w;
+  }
+  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
+  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
+  reinterpret_cast<V4<T>*>(a.AP)[i] = ap;
+}
+
+__device__ __forceinline__ double wave_min6(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
+  return v;
+}
+
+// REDUCE (+ CORRECT): one thread per body adds its chunk partials in chunk order, then HM_STEP
+// applies the corrector, stores a1, j1, s1, c1 and the body's wish for the next step, HM_INIT
+// starts a run (a, j, s <- sums, c <- 0; the first step (eta / 2) |a| / |j|), HM_OUT returns the
+// derivatives. Per-workgroup dt minima go to wgmin (+inf when no body of the workgroup takes
+// part: ghost rows, a zero or non-finite ratio, or a fixed-step run).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
+  __shared__ double red[kBlock / 64];
+  if (a.mode == HM_STEP && !a.ctrl->active) return;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad: a multiple of 256)
+  const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
+  const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
+  const V4<T>* PS = reinterpret_cast<const V4<T>*>(a.PS);
+  T m[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ph = 0;  // a1, j1, s1
+  for (int c = 0; c < a.n_chunks; ++c) {
+    const int64_t o = (int64_t)c * a.n_pad + i;
+    const V4<T> pa = PA[o], pj = PJ[o], ps = PS[o];
+    m[0][0] += pa.x; m[0][1] += pa.y; m[0][2] += pa.z; ph += pa.w;
+    m[1][0] += pj.x; m[1][1] += pj.y; m[1][2] += pj.z;
+    m[2][0] += ps.x; m[2][1] += ps.y; m[2][2] += ps.z;
+  }
+  const V4<T> z = {T(0), T(0), T(0), T(0)};
+  V4<T> oa = {m[0][0], m[0][1], m[0][2], T(0)}, oj = {m[1][0], m[1][1], m[1][2], T(0)},
+        os = {m[2][0], m[2][1], m[2][2], T(0)};
+  if (a.mode == HM_OUT) {
+    oa.w = -ph;
+    reinterpret_cast<V4<T>*>(a.a_out)[i] = oa;
+    reinterpret_cast<V4<T>*>(a.j_out)[i] = oj;
+    reinterpret_cast<V4<T>*>(a.s_out)[i] = os;
+    return;
+  }
+  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
+  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
+  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
+  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
+  V4<T>* S = reinterpret_cast<V4<T>*>(a.S);
+  V4<T>* C = reinterpret_cast<V4<T>*>(a.C);
+  const double eta = a.ctrl->eta;
+  double dti = INFINITY;
+  if (i >= a.n_real) {
+    A[i] = z; J[i] = z; S[i] = z; C[i] = z;
+    if (a.mode == HM_STEP) {
+      X[i] = z;
+      V[i] = z;
+    }
+  } else if (a.mode == HM_INIT) {
+    A[i] = oa; J[i] = oj; S[i] = os; C[i] = z;
+    if (eta > 0.0) {
+      const double an = h6_norm3(m[0][0], m[0][1], m[0][2]);
+      const double jn = h6_norm3(m[1][0], m[1][1], m[1][2]);
+      const double d = 0.5 * eta * an / jn;
+      if (jn > 0.0 && isfinite(d)) dti = d;
+    }
+  } else {
+    const double hd = a.ctrl->h;
+    const T h = (T)hd;
+    const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i], s0 = S[i];
+    const T xs[3] = {x.x, x.y, x.z}, vs[3] = {v.x, v.y, v.z};
+    const T as[3] = {a0.x, a0.y, a0.z}, js[3] = {j0.x, j0.y, j0.z}, ss[3] = {s0.x, s0.y, s0.z};
+    T x1[3], v1[3];
+    double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      h6_correct(h, xs[d], vs[d], as[d], js[d], ss[d], m[0][d], m[1][d], m[2][d], x1[d], v1[d]);
+      a1[d] = m[0][d]; j1[d] = m[1][d]; s1[d] = m[2][d];
+      h6_high(hd, as[d], js[d], ss[d], a1[d], j1[d], s1[d], c1[d], p1[d], a5[d]);
+    }
+    const V4<T> ox = {x1[0], x1[1], x1[2], x.w}, ov = {v1[0], v1[1], v1[2], T(0)};
+    const V4<T> oc = {(T)c1[0], (T)c1[1], (T)c1[2], T(0)};
+    X[i] = ox; V[i] = ov; A[i] = oa; J[i] = oj; S[i] = os; C[i] = oc;
+    if (eta > 0.0) {
+      double d;
+      if (h6_dt(eta, a1, j1, s1, c1, p1, a5, d)) dti = d;
+    }
+  }
+  dti = wave_min6(dti);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dti;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kBlock / 64; ++w) dti = fmin(dti, red[w]);
+    a.wgmin[blockIdx.x] = dti;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Host launchers: validate, compute the grid, dispatch.
+
+// The forms that are built: 1 or 2 i-bodies per lane in fp32, 1 in fp64.
+bool hermite6_ipl_ok(int fp64, int ipl) { return ipl == 1 || (ipl == 2 && !fp64); }
+
+template <typename T>
+static bool geometry6_ok(const H6Args<T>& a) {
+  return a.n_chunks >= 1 && a.n_pad % kBlock == 0 && a.chunk % Tile<T>::kBodies == 0 &&
+         (int64_t)a.n_chunks * a.chunk == a.n_pad && a.n_real >= 1 && a.n_real <= a.n_pad;
+}
+
+template <typename T, bool PHI, int IPL>
+static hipError_t eval6_go(const H6Args<T>& a, dim3 grid, bool gated, hipStream_t s) {
+  hipLaunchKernelGGL((hermite6_eval_kernel<T, PHI, IPL>), grid, dim3(kBlock), 0, s, a, (int)gated);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool gated,
+                                hipStream_t s) {
+  if (!geometry6_ok(a) || !hermite6_ipl_ok(sizeof(T) == 8, ipl) || a.n_pad % (kBlock * ipl) ||
+      (gated && !a.ctrl) || !a.XP || !a.VP || !a.AP || !a.PA || !a.PJ || !a.PS)
+    return hipErrorInvalidValue;
+  const int g = groups < 1 ? 1 : groups > a.n_chunks ? a.n_chunks : groups;
+  const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)g);
+  if constexpr (sizeof(T) == 4) {
+    if (ipl == 2)
+      return a.phi ? eval6_go<T, true, 2>(a, grid, gated, s) : eval6_go<T, false, 2>(a, grid, gated, s);
+  }
+  return a.phi ? eval6_go<T, true, 1>(a, grid, gated, s) : eval6_go<T, false, 1>(a, grid, gated, s);
+}
+
+template <typename T>
+hipError_t launch_hermite6_predict(const H6Args<T>& a, hipStream_t s) {
+  if (!geometry6_ok(a) || !a.ctrl) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hermite6_predict_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
+                     0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s) {
+  if (!geometry6_ok(a) || !a.ctrl || !a.wgmin) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(hermite6_reduce_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
+                     0, s, a);
+  return hipGetLastError();
+}
+
+#define GS_HERMITE6_INSTANTIATE(T)                                                          \
+  template hipError_t launch_hermite6_predict<T>(const H6Args<T>&, hipStream_t);             \
+  template hipError_t launch_hermite6_eval<T>(const H6Args<T>&, int, int, bool, hipStream_t); \
+  template hipError_t launch_hermite6_reduce<T>(const H6Args<T>&, hipStream_t);
+GS_HERMITE6_INSTANTIATE(float)
+GS_HERMITE6_INSTANTIATE(double)
+
+}  // namespace gs

@@ -230,6 +230,27 @@ int gs_cpu_knn_f32(const float* X4, int64_t n_real, int64_t i0, int64_t i1, int3
                    int32_t* idx);
 int gs_cpu_knn_mixed(const double* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k,
                      double* r2, int32_t* idx);
+// 6th-order Hermite (Nitadori & Makino 2008). Derivatives of global bodies [i0, i1) at
+// (X4, V4, A4 = ax, ay, az, 0 the acceleration the snap is taken at): acc4 (ax, ay, az, phi),
+// jerk4, snap4 with s_i = sum mu q / r^3 - 6 alpha J_ij - 3 beta A_ij (q = a_j - a_i,
+// alpha = (d.w) / r^2, beta = (|w|^2 + d.q) / r^2 + alpha^2); the pair law, the chunk order and
+// the operations of the GPU pair term (nbody_hermite6.hip), a and j bit-equal to gs_cpu_accjerk_*.
+int gs_cpu_accjerksnap_f64(const double* X4, const double* V4, const double* A4, int64_t n_real,
+                           int64_t i0, int64_t i1, int32_t chunk, double cut2, double eps2,
+                           double* acc4, double* jerk4, double* snap4);
+int gs_cpu_accjerksnap_f32(const float* X4, const float* V4, const float* A4, int64_t n_real,
+                           int64_t i0, int64_t i1, int32_t chunk, float cut2, float eps2,
+                           float* acc4, float* jerk4, float* snap4);
+// One 6th-order step of size h on the n_real bodies, in place: predict (x, v, a), evaluate,
+// correct; A4, J4, S4, C4 carry a, j, snap and crackle from step to step (scratch: 6 arrays of
+// n_real * 4: the predicted x, v, a rows, then a1, j1, s1). *dt_min_out (if given and eta > 0)
+// gets min_i of the criterion of gs_hermite_set_order (+inf when no body takes part).
+int gs_cpu_hermite6_step_f64(double* X4, double* V4, double* A4, double* J4, double* S4,
+                             double* C4, double* scratch, int64_t n_real, int32_t chunk, double h,
+                             double cut2, double eps2, double eta, double* dt_min_out);
+int gs_cpu_hermite6_step_f32(float* X4, float* V4, float* A4, float* J4, float* S4, float* C4,
+                             float* scratch, int64_t n_real, int32_t chunk, double h, float cut2,
+                             float eps2, double eta, double* dt_min_out);
 int gs_cpu_num_threads(void);
 int gs_cpu_set_threads(int32_t n);  // OpenMP threads for the CPU engine (returns the new max)
 
@@ -436,6 +457,33 @@ int gs_hermite_clear_overlap(gs_hermite* h);  // overlaps <- 0: a stopped run st
 int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn);
 int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                                 double* acc4, double* jerk4, double* q, int32_t* nn);
+
+// 6th-order scheme (Nitadori & Makino 2008; gs_hermite6.h, nbody_hermite6.hip): the state also
+// carries the snap s = a'' and the crackle c = a''', and the one force pass of a step returns
+// a, j and s at the predicted (x, v, a). One shared step (fixed, or adaptive with
+//   dt_i = eta ((|a||s| + |j|^2) / (|c||a^(5)| + |a^(4)|^2))^(1/6),
+// eta linear: useful values are 0.2 to 0.5), fp32 or fp64, one rank. gs_hermite_set_order(h, 6)
+// refuses GS_MIXED, nranks > 1, block steps and collisions, and once the order is 6
+// gs_hermite_set_block, gs_hermite_set_collisions and the gs_hermite_group_* calls refuse. Call
+// it before the state is set (like gs_hermite_set_block); order 4 frees the extra arrays again.
+// cfg's ipl: 0 auto, 1, or 2 for fp32 (gs_hermite6_ipl_ok). A run starts with c = 0 and two
+// evaluate passes: with ap = 0 for a and j, then with ap = a for s.
+// gs_hermite_step, _sync, _status, _get_state, _set_adaptive and _count_nonfinite work as for
+// order 4; gs_hermite_set_state starts the derivatives afresh from (pos, vel) at time t, and
+// gs_hermite_derivs returns a and j of gs_hermite_derivs6.
+int gs_hermite_set_order(gs_hermite* h, int32_t order);
+int32_t gs_hermite_get_order(gs_hermite* h);
+int32_t gs_hermite6_ipl_ok(int32_t fp64, int32_t ipl);  // 1 if that evaluate form is compiled
+// gs_hermite_set_state with the carried snap and crackle too (n*3 each): with all four of acc,
+// jerk, snap, crackle a resumed run continues bit for bit; with any of them NULL all start afresh.
+int gs_hermite_set_state6(gs_hermite* h, const double* pos, const double* vel, const double* mass,
+                          const double* acc, const double* jerk, const double* snap,
+                          const double* crackle, double t, double dt_next, double dt_min);
+// The carried snap and crackle, n*3 each (either may be NULL); a, j: gs_hermite_get_state.
+int gs_hermite_get_carried6(gs_hermite* h, double* snap, double* crackle);
+// (ax, ay, az, phi), (jx, jy, jz, 0) and (sx, sy, sz, 0) of the current (x, v), the snap at the
+// acceleration of that state, through the step's own kernel (any pointer may be NULL).
+int gs_hermite_derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4);
 
 // ---------------------------------------------------------------- k nearest neighbours
 // (nbody_knn.hip; the Casertano & Hut local density and the cluster read-outs rest on it.)

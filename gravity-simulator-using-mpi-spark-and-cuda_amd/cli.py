@@ -43,7 +43,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "step also runs on --gpus P)")
     p.add_argument("--eta", type=float, default=d.eta,
                    help="hermite: accuracy parameter of the shared adaptive step (Aarseth's "
-                        "criterion; --dt is then the largest step); 0 = fixed step")
+                        "criterion; --dt is then the largest step); 0 = fixed step. "
+                        "--hermite-order 6 takes it linearly (Nitadori & Makino): 0.2 to 0.5 "
+                        "there, where order 4 takes about 0.02")
+    p.add_argument("--hermite-order", dest="hermite_order", type=int, choices=[4, 6],
+                   default=d.hermite_order,
+                   help="hermite: 4 (Makino & Aarseth 1992) or 6 (Nitadori & Makino 2008: one "
+                        "acceleration+jerk+snap pass per step). Order 6 takes --eta linearly in "
+                        "its criterion: useful values are 0.2 to 0.5, not the 0.02 of order 4. "
+                        "It runs one shared step in fp32 or fp64 on one rank (not with "
+                        "--block-steps, --dtype mixed, --collisions or --gpus > 1). Adaptive "
+                        "runs of systems with a wide range of timescales want --dtype fp64: "
+                        "with fp32 rows the criterion's 5th derivative is rounding noise once "
+                        "the shared step is far below a body's own timescale, and the step "
+                        "shrinks without end (docs/DESIGN.md section 21)")
     p.add_argument("--t-end", dest="t_end", type=float, default=d.t_end,
                    help="hermite: stop at this time [s], reached exactly (--steps caps the count)")
     p.add_argument("--block-steps", dest="block_steps", action="store_true",
@@ -152,7 +165,7 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
                      cutoff_mode=a.cutoff_mode, integrator=a.integrator, eta=a.eta,
                      t_end=a.t_end, block_steps=a.block_steps, max_level=a.max_level,
                      collisions=a.collisions, body_density=a.body_density,
-                     kernel=a.kernel,
+                     hermite_order=a.hermite_order, kernel=a.kernel,
                      mode=a.mode, ipl=a.ipl, chunk=a.chunk, graph=a.graph, graph_comm=a.graph_comm,
                      strategy=a.strategy, step_timeout_s=a.step_timeout_s, overlap=a.overlap,
                      threads=a.threads,
@@ -179,6 +192,9 @@ def run_one(cfg: SimConfig, dist, log, quiet: bool = False, final: bool = True,
     try:
         if log and dist.is_root:
             log.header(dist.world, cfg.n, cfg.steps, cfg.dt)
+            if sim.order_restart:
+                log.line(f"checkpoint of the other hermite order resumed under order "
+                         f"{cfg.hermite_order}: derivatives restarted from x, v, t")
         if guard:
             guard.stage("run", None)  # bounded by the native step timeout (progress)
         m = sim.run(cfg.steps, log if dist.is_root else None)

@@ -47,6 +47,10 @@ class SimConfig:
     collisions: str = "off"       # hermite: off | detect (nearest neighbours, closest approaches
                                   # and overlaps recorded and reported) | merge (overlapping
                                   # bodies become one at the next synchronised state)
+    hermite_order: int = 4        # hermite: 4 (Makino & Aarseth 1992) | 6 (Nitadori & Makino
+                                  # 2008: the state carries snap and crackle; eta enters its
+                                  # criterion linearly, useful values 0.2 to 0.5; one shared
+                                  # step, fp32 or fp64, one rank)
     body_density: Optional[float] = None  # hermite collisions: radii R = (3 m / 4 pi rho)^(1/3)
                                   # [kg/m^3] for bodies without a given radius (massless: 0)
     kernel: str = "auto"          # GPU j-source variant: lds | smem
@@ -146,6 +150,22 @@ class SimConfig:
             if self.t_end is not None and self.dt > 0 and \
                     round(self.t_end / self.dt) * self.dt != self.t_end:
                 raise ValueError("block steps: t_end must be a whole multiple of dt")
+        if self.hermite_order not in (4, 6):
+            raise ValueError("hermite_order must be 4 or 6")
+        if self.hermite_order == 6:
+            if self.integrator != "hermite":
+                raise ValueError("hermite_order belongs to integrator hermite")
+            if self.block_steps:
+                raise ValueError("hermite order 6 has no block steps (--block-steps): a follow-up")
+            if self.dtype == "mixed":
+                raise ValueError("hermite order 6 has no mixed precision (--dtype mixed): fp32 or "
+                                 "fp64")
+            if self.collisions != "off":
+                raise ValueError("hermite order 6 has no collisions (--collisions): a follow-up")
+            if self.gpus > 1:
+                raise ValueError("hermite order 6 runs on one rank: not with --gpus > 1")
+            if self.ipl == 4 or (self.ipl == 2 and self.dtype == "fp64"):
+                raise ValueError("hermite order 6: ipl must be 0, 1 (or 2 for fp32)")
         if self.integrator == "hermite":
             if not self.eta >= 0:
                 raise ValueError("eta must be >= 0")

@@ -151,6 +151,10 @@ def cpu_lib():
                 _sig(lib, f"gs_cpu_hermite_first_dt_{t}", c_double, [P, P, L, c_double])
             for stem, args in ops.items():
                 _sig(lib, f"gs_cpu_{stem}_{t}", c_int32, args)
+        for t, P, T in (("f64", _PD, c_double), ("f32", _PF, c_float)):  # 6th-order Hermite
+            _sig(lib, f"gs_cpu_accjerksnap_{t}", c_int32, [P, P, P, L, L, L, I, T, T, P, P, P])
+            _sig(lib, f"gs_cpu_hermite6_step_{t}", c_int32,
+                 [P, P, P, P, P, P, P, L, I, c_double, T, T, c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
                                                     c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_ld", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -256,6 +260,13 @@ def hip_lib():
         _sig(lib, "gs_hermite_set_step_timeout", c_int32, [S, c_double])
         _sig(lib, "gs_hermite_derivs_active_nn", c_int32, [S, PI, c_int32, c_int32, _PD, _PD,
                                                            _PD, PI])
+        _sig(lib, "gs_hermite_set_order", c_int32, [S, c_int32])
+        _sig(lib, "gs_hermite_get_order", c_int32, [S])
+        _sig(lib, "gs_hermite6_ipl_ok", c_int32, [c_int32, c_int32])
+        _sig(lib, "gs_hermite_set_state6", c_int32, [S, _PD, _PD, _PD, _PD, _PD, _PD, _PD,
+                                                     c_double, c_double, c_double])
+        _sig(lib, "gs_hermite_get_carried6", c_int32, [S, _PD, _PD])
+        _sig(lib, "gs_hermite_derivs6", c_int32, [S, _PD, _PD, _PD])
         _sig(lib, "gs_hip_knn", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, _PD, PI32])
         _sig(lib, "gs_hip_knn_time", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,

@@ -90,3 +90,34 @@ def acc_jerk(pos, vel, mass, device: str = "cpu", dtype: str = "fp64", G: float 
     finally:
         eng.close()
     return a4[:, :3], j4[:, :3], a4[:, 3]
+
+
+def acc_jerk_snap(pos, vel, mass, device: str = "cpu", dtype: str = "fp64", G: float = G_SI,
+                  cutoff: float = 1e-10, softening: float = 0.0, chunk: int = 0, ipl: int = 0,
+                  split_groups: int = 0):
+    """One-shot 6th-order Hermite derivatives of a state: (acc, jerk, snap (n,3), phi (n,)) as
+    float64 arrays, the snap at the acceleration of the state itself (two passes: a, then s).
+
+    device "oracle": NumPy fp64; "cpu": the native C++ engine; "gpu": the gfx950
+    acceleration+jerk+snap kernel (raises if the HIP path is unavailable). dtype "fp32" or
+    "fp64"."""
+    pos, vel = np.asarray(pos, np.float64), np.asarray(vel, np.float64)
+    mass = np.asarray(mass, np.float64)
+    n = int(mass.shape[0])
+    if device == "oracle":
+        a = oracle.acc_jerk_snap(pos, vel, np.zeros_like(pos), mass, G, cutoff, softening)[0]
+        return oracle.acc_jerk_snap(pos, vel, a, mass, G, cutoff, softening, with_potential=True)
+    if device not in ("cpu", "gpu"):
+        raise ValueError(f"unknown device {device!r}")
+    from ..runtime.hermite import HermiteCpuEngine, HermiteHipEngine
+
+    cfg = SimConfig(n=n, dtype=dtype, G=G, cutoff=cutoff, softening=softening, chunk=chunk,
+                    ipl=ipl, split_groups=split_groups, device=device, integrator="hermite",
+                    hermite_order=6).validate()
+    eng = HermiteCpuEngine(cfg) if device == "cpu" else HermiteHipEngine(cfg)
+    try:
+        eng.load(BodySet(pos, vel, mass))
+        a4, j4, s4 = eng.derivs()
+    finally:
+        eng.close()
+    return a4[:, :3], j4[:, :3], s4[:, :3], a4[:, 3]

@@ -414,6 +414,159 @@ def simulate_hermite(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=
     return x, v, traj, t, taken
 
 
+# ---- 6th-order Hermite (Nitadori & Makino 2008) -----------------------------------------------
+def acc_jerk_snap(pos, vel, acc_in, mass, G: float = G_SI, cutoff: float = 1e-10,
+                  softening: float = 0.0, block: int = 256, with_potential: bool = False,
+                  with_abs: bool = False):
+    """Direct-sum accelerations, jerks and snaps (n, 3) in fp64; optionally phi (n,) too.
+
+        A_ij = mu_j d / r^3,  J_ij = mu_j w / r^3 - 3 alpha A_ij,
+        S_ij = mu_j q / r^3 - 6 alpha J_ij - 3 beta A_ij,
+        d = x_j - x_i, w = v_j - v_i, q = acc_in_j - acc_in_i, r^2 = |d|^2 + eps^2,
+        alpha = (d.w) / r^2,  beta = (|w|^2 + d.q) / r^2 + alpha^2,
+
+    a pair contributing zero to all when r^2 < cutoff^2. acc_in is the acceleration the snap is
+    taken at (the snap of a state is acc_jerk_snap(x, v, a(x), ...)). with_abs also returns the
+    rounding scales (n, 3) of the three sums: those of acc_jerk and, per component c of the snap,
+    sum_j mu_j r^-3 [|q_c| + 6 al (|w_c| + 3 al |d_c|) + 3 be |d_c|] with
+    al = sum_k |d_k w_k| / r^2 and be = (sum_k w_k^2 + sum_k |d_k q_k|) / r^2 + al^2."""
+    pos = np.asarray(pos, dtype=np.float64)
+    vel = np.asarray(vel, dtype=np.float64)
+    ain = np.asarray(acc_in, dtype=np.float64)
+    mu = G * np.asarray(mass, dtype=np.float64)
+    n = pos.shape[0]
+    acc, jerk, snap = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    absacc, absjerk, abssnap = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3))
+    phi = np.zeros(n)
+    cut2 = cutoff * cutoff
+    eps2 = softening * softening
+
+    def rows(i0: int) -> None:
+        i1 = min(n, i0 + block)
+        d = pos[None, :, :] - pos[i0:i1, None, :]            # (b, n, 3)  x_j - x_i
+        w = vel[None, :, :] - vel[i0:i1, None, :]
+        q = ain[None, :, :] - ain[i0:i1, None, :]
+        r2 = (d * d).sum(-1) + eps2
+        ok = r2 >= cut2
+        inv = np.zeros_like(r2)
+        inv[ok] = 1.0 / np.sqrt(r2[ok])
+        inv2 = inv * inv
+        mi = mu[None, :] * inv
+        s = (mi * inv2)[:, :, None]
+        al = ((d * w).sum(-1) * inv2)[:, :, None]
+        be = (((w * w).sum(-1) + (d * q).sum(-1)) * inv2)[:, :, None] + al * al
+        A = s * d
+        Jt = s * w - 3.0 * al * A
+        acc[i0:i1] = A.sum(1)
+        jerk[i0:i1] = Jt.sum(1)
+        snap[i0:i1] = (s * q - 6.0 * al * Jt - 3.0 * be * A).sum(1)
+        phi[i0:i1] = -mi.sum(1)
+        if with_abs:
+            ad, aw = np.abs(d), np.abs(w)
+            aal = (np.abs(d * w).sum(-1) * inv2)[:, :, None]
+            abe = (((w * w).sum(-1) + np.abs(d * q).sum(-1)) * inv2)[:, :, None] + aal * aal
+            absacc[i0:i1] = (s * ad).sum(1)
+            absjerk[i0:i1] = (s * (aw + 3.0 * aal * ad)).sum(1)
+            abssnap[i0:i1] = (s * (np.abs(q) + 6.0 * aal * (aw + 3.0 * aal * ad)
+                                   + 3.0 * abe * ad)).sum(1)
+
+    starts = range(0, n, block)
+    if n * n >= 1 << 22 and len(starts) > 1:
+        # (independent row blocks on a few threads, as in accelerations())
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
+            list(ex.map(rows, starts))
+    else:
+        for i0 in starts:
+            rows(i0)
+    out = (acc, jerk, snap)
+    if with_potential:
+        out += (phi,)
+    if with_abs:
+        out += (absacc, absjerk, abssnap)
+    return out
+
+
+def hermite6_high(a0, j0, s0, a1, j1, s1, h):
+    """The 3rd, 4th and 5th derivatives of a at t1 = t0 + h of the quintic that takes
+    (a0, j0, s0) at t0 and (a1, j1, s1) at t1: (c1, p1, a5), a5 being constant over the step.
+    h a scalar, or one value per row."""
+    h = np.asarray(h, dtype=np.float64)
+    hp = 0.5 * (h[:, None] if h.ndim else h)
+    hp2 = hp * hp
+    Am, Jm, Jp = a1 - a0, hp * (j1 - j0), hp * (j1 + j0)
+    Sm, Sp = hp2 * (s1 - s0), hp2 * (s1 + s0)
+    ih = 1.0 / hp
+    ih3 = ih * ih * ih
+    ih4 = ih3 * ih
+    ih5 = ih4 * ih
+    a3 = (6.0 * ih3) * (-5.0 * Am + 5.0 * Jp - Sm) / 8.0
+    a4 = (24.0 * ih4) * (-Jm + Sp) / 16.0
+    a5 = (120.0 * ih5) * (3.0 * Am - 3.0 * Jp + Sm) / 16.0
+    return a3 + hp * a4 + hp2 * a5 / 2.0, a4 + hp * a5, a5
+
+
+def hermite6_dt(a0, j0, s0, a1, j1, s1, h, eta):
+    """Nitadori & Makino's criterion after a 6th-order step of size h: min over the bodies of
+    eta ((|a1||s1| + |j1|^2) / (|c1||a5| + |p1|^2))^(1/6) with the higher derivatives of
+    hermite6_high (eta enters linearly: useful values are 0.2 to 0.5); bodies with a zero or
+    non-finite ratio are skipped (inf when none is left)."""
+    c1, p1, a5 = hermite6_high(a0, j0, s0, a1, j1, s1, h)
+    nrm = lambda y: np.sqrt((y * y).sum(1))  # noqa: E731
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = (nrm(a1) * nrm(s1) + nrm(j1) ** 2) / (nrm(c1) * nrm(a5) + nrm(p1) ** 2)
+        dt = eta * ratio ** (1.0 / 6.0)
+    dt = dt[(ratio > 0) & np.isfinite(dt)]
+    return float(dt.min()) if dt.size else float("inf")
+
+
+def hermite6_start(pos, vel, mass, G=G_SI, cutoff=1e-10, softening=0.0):
+    """a, j, s of a state in the two passes a 6th-order run starts with: the first with
+    acc_in = 0 gives a and j, the second with acc_in = a gives s."""
+    a, _, _ = acc_jerk_snap(pos, vel, np.zeros_like(np.asarray(pos, dtype=np.float64)), mass, G,
+                            cutoff, softening)
+    return acc_jerk_snap(pos, vel, a, mass, G, cutoff, softening)
+
+
+def simulate_hermite6(pos, vel, mass, dt, steps, G=G_SI, cutoff=1e-10, softening=0.0, eta=0.0,
+                      t_end=None, record_every=0):
+    """6th-order Hermite predictor-corrector (Nitadori & Makino 2008), one evaluation per step
+    at the predicted (x, v, a); the state carries a, j, s and the crackle c (0 at the start).
+    eta > 0: one shared step h = min(dt, min_i dt_i) chosen each step (hermite6_dt; the first from
+    hermite_first_dt); t_end: the step is cut to reach it exactly and the run stops there
+    (`steps` caps the count). Returns (pos, vel, traj, t, list of steps), as simulate_hermite."""
+    x = np.array(pos, dtype=np.float64, copy=True)
+    v = np.array(vel, dtype=np.float64, copy=True)
+    a, j, s = hermite6_start(x, v, mass, G, cutoff, softening)
+    c = np.zeros_like(a)
+    t, taken, traj = 0.0, [], []
+    nxt = hermite_first_dt(a, j, eta) if eta > 0 else dt
+    while len(taken) < steps and (t_end is None or t < t_end):
+        h = min(dt, nxt)
+        cut = t_end is not None and h >= t_end - t
+        if cut:
+            h = t_end - t
+        h2, h3, h4, h5 = (h * h) / 2, (h * h * h) / 6, (h * h * h * h) / 24, \
+            (h * h * h * h * h) / 120
+        xp = x + (v * h + (a * h2 + (j * h3 + (s * h4 + c * h5))))
+        vp = v + (a * h + (j * h2 + (s * h3 + c * h4)))
+        ap = a + (j * h + (s * h2 + c * h3))
+        a1, j1, s1 = acc_jerk_snap(xp, vp, ap, mass, G, cutoff, softening)
+        hh, h10, h120 = h / 2, (h * h) / 10, (h * h * h) / 120
+        v1 = v + ((a + a1) * hh + ((j - j1) * h10 + (s + s1) * h120))
+        x = x + ((v + v1) * hh + ((a - a1) * h10 + (j + j1) * h120))
+        if eta > 0:
+            nxt = hermite6_dt(a, j, s, a1, j1, s1, h, eta)
+        c = hermite6_high(a, j, s, a1, j1, s1, h)[0]
+        v, a, j, s = v1, a1, j1, s1
+        t = t_end if cut else t + h
+        taken.append(h)
+        if record_every and len(taken) % record_every == 0:
+            traj.append(x.copy())
+    return x, v, traj, t, taken
+
+
 def step(pos, vel, mass, dt, G=G_SI, cutoff=1e-10, softening=0.0):
     """One synchronous kick-drift step; returns new (pos, vel)."""
     a = accelerations(pos, mass, G, cutoff, softening)

@@ -25,6 +25,13 @@ x1 = x + (v + v1) h/2 + (a - a1) h^2/12; a1, j1 become the next step's a, j. Wit
 step takes h = min(dt, min_i dt_i) of Aarseth's criterion; with t_end set the last step is cut
 to reach it exactly and further steps are no-ops.
 
+Order 6 (cfg.hermite_order; Nitadori & Makino 2008): the state also carries the snap s and the
+crackle c, the predictor runs to h^5 in x and also predicts a, the one evaluation returns a1, j1
+and s1 at (xp, vp, ap), and the corrector is v1 = v + (a + a1) h/2 - (j1 - j) h^2/10 +
+(s + s1) h^3/120, x1 likewise from v, a, j (ops/oracle.py simulate_hermite6). eta enters its step
+criterion linearly (0.2 to 0.5). load() then also takes snap and crackle, carried() returns
+(acc, jerk, snap, crackle) and derivs() (a4, j4, s4). One shared step, fp32 or fp64, one rank.
+
 Block mode (cfg.block_steps; Makino 1991): body i steps by dt 2^-k_i, time is an integer count
 of ticks of dt 2^-max_level, and a block step predicts every body to the earliest due time,
 evaluates the due bodies against all and corrects them (the rules: ops/oracle.py
@@ -108,6 +115,11 @@ class HermiteHipEngine:
         _native.check(self.lib, self.lib.gs_hermite_set_adaptive(
             self._h, float(cfg.eta), float(cfg.dt),
             -1.0 if cfg.t_end is None else float(cfg.t_end)), "set_adaptive")
+        self.order = int(cfg.hermite_order)
+        if self.order == 6:
+            _native.check(self.lib, self.lib.gs_hermite_set_order(self._h, 6), "set_order")
+            _native.check(self.lib, self.lib.gs_hermite_layout(self._h, ctypes.byref(L)), "layout")
+            self.native_layout = L.as_dict()
         self.block = bool(cfg.block_steps)
         if self.block:
             _native.check(self.lib, self.lib.gs_hermite_set_block(self._h, 1, int(cfg.max_level)),
@@ -198,13 +210,25 @@ class HermiteHipEngine:
 
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
              dt_next: Optional[float] = None, dt_min: Optional[float] = None,
-             levels=None, body_times=None) -> None:
+             levels=None, body_times=None, snap=None, crackle=None) -> None:
         """Set the state at time t. acc, jerk None: evaluated from (pos, vel); given (with the
         dt_next and dt_min a status() reported): a run continues as if never interrupted.
-        Block mode: t is a whole multiple of dt; levels (and body_times, ticks) None: afresh."""
+        Block mode: t is a whole multiple of dt; levels (and body_times, ticks) None: afresh.
+        Order 6: a run continues only with all of acc, jerk, snap, crackle; else all afresh."""
         pos = np.ascontiguousarray(b.pos, dtype=np.float64)
         vel = np.ascontiguousarray(b.vel, dtype=np.float64)
         mass = np.ascontiguousarray(b.mass, dtype=np.float64)
+        if self.order == 6:
+            four = [acc, jerk, snap, crackle]
+            have = all(y is not None for y in four)
+            four = [np.ascontiguousarray(y, dtype=np.float64) if have else None for y in four]
+            _native.check(self.lib, self.lib.gs_hermite_set_state6(
+                self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
+                *[_native.dptr(y) if have else None for y in four], float(t),
+                float(dt_next) if dt_next is not None and math.isfinite(dt_next) else -1.0,
+                float(dt_min) if dt_min is not None and math.isfinite(dt_min) else -1.0),
+                "set_state6")
+            return
         have = acc is not None and jerk is not None
         a = np.ascontiguousarray(acc, dtype=np.float64) if have else None
         j = np.ascontiguousarray(jerk, dtype=np.float64) if have else None
@@ -293,10 +317,16 @@ class HermiteHipEngine:
     def state(self) -> BodySet:
         return self._get(False)[0]
 
-    def carried(self) -> tuple[np.ndarray, np.ndarray]:
+    def carried(self):
         """(acc, jerk) (n, 3) as the integrator carries them (evaluated at the last predicted
-        state): what a checkpoint keeps so that a resumed run is bit-exact."""
+        state): what a checkpoint keeps so that a resumed run is bit-exact. Order 6:
+        (acc, jerk, snap, crackle)."""
         _, a, j = self._get(True)
+        if self.order == 6:
+            s, c = np.zeros((self.cfg.n, 3)), np.zeros((self.cfg.n, 3))
+            _native.check(self.lib, self.lib.gs_hermite_get_carried6(
+                self._h, _native.dptr(s), _native.dptr(c)), "get_carried6")
+            return a, j, s, c
         return a, j
 
     def derivs(self, active=None, path: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
@@ -312,6 +342,11 @@ class HermiteHipEngine:
             return a4, j4
         n = self.cfg.n
         a4, j4 = np.zeros((n, 4)), np.zeros((n, 4))
+        if self.order == 6:  # (and the snap at that acceleration: (a4, j4, s4))
+            s4 = np.zeros((n, 4))
+            _native.check(self.lib, self.lib.gs_hermite_derivs6(
+                self._h, _native.dptr(a4), _native.dptr(j4), _native.dptr(s4)), "derivs6")
+            return a4, j4, s4
         _native.check(self.lib, self.lib.gs_hermite_derivs(self._h, _native.dptr(a4),
                                                            _native.dptr(j4)), "derivs")
         return a4, j4
@@ -474,6 +509,13 @@ class HermiteCpuEngine:
         self._scratch = np.zeros((4 * n, 4), T)
         self.mass = np.zeros(n)
         self._step, self._ptr = _native.cpu_entry(self.lib, "hermite_step", cfg.dtype)
+        self.order = int(cfg.hermite_order)
+        if self.order == 6:  # (the refusals of SimConfig.validate for a bare engine)
+            cfg.validate()
+            self.S, self.C = np.zeros((n, 4), T), np.zeros((n, 4), T)
+            self._scratch = np.zeros((6 * n, 4), T)
+            self._step6 = _native.cpu_entry(self.lib, "hermite6_step", cfg.dtype)[0]
+            self._ajs = _native.cpu_entry(self.lib, "accjerksnap", cfg.dtype)[0]
         self._accjerk, self._accjerk_idx, self._first_dt, self._nn, self._nn_idx = (
             _native.cpu_entry(self.lib, stem, cfg.dtype)[0]
             for stem in ("accjerk", "accjerk_idx", "hermite_first_dt", "nn", "nn_idx"))
@@ -558,6 +600,20 @@ class HermiteCpuEngine:
         q, nn = self._nearest(self.X, active)
         return a4, j4, q.astype(np.float64), nn
 
+    def _derivs6(self):
+        """(a4, j4, s4) of the current (x, v) in the two passes a 6th-order run starts with:
+        ap = 0 for a, then ap = a for the snap."""
+        n, T = self.cfg.n, self.np_dtype
+        a4, j4, s4 = np.zeros((n, 4), T), np.zeros((n, 4), T), np.zeros((n, 4), T)
+        ap = np.zeros((n, 4), T)
+        for _ in range(2):
+            rc = self._ajs(self._ptr(self.X), self._ptr(self.V), self._ptr(ap), n, 0, n,
+                           self.layout.chunk, self._cut2, self._eps2, self._ptr(a4),
+                           self._ptr(j4), self._ptr(s4))
+            _native.check(self.lib, rc, "cpu accjerksnap")
+            ap = a4.copy()
+        return a4, j4, s4
+
     def _derivs(self) -> tuple[np.ndarray, np.ndarray]:
         n, T = self.cfg.n, self.np_dtype
         a4, j4 = np.zeros((n, 4), T), np.zeros((n, 4), T)
@@ -640,7 +696,9 @@ class HermiteCpuEngine:
 
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
              dt_next: Optional[float] = None, dt_min: Optional[float] = None,
-             levels=None, body_times=None) -> None:
+             levels=None, body_times=None, snap=None, crackle=None) -> None:
+        if self.order == 6:
+            return self._load6(b, acc, jerk, snap, crackle, t, dt_next, dt_min)
         self.X[:, :3] = b.pos
         self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
         self.V[:] = 0
@@ -671,6 +729,27 @@ class HermiteCpuEngine:
         if self.block:
             self._block_start(float(t), levels, body_times)
 
+    def _load6(self, b, acc, jerk, snap, crackle, t, dt_next, dt_min) -> None:
+        self.X[:, :3] = b.pos
+        self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
+        self.V[:] = 0
+        self.V[:, :3] = b.vel
+        self.mass = np.array(b.mass, dtype=np.float64)
+        for y in (self.A, self.J, self.S, self.C):
+            y[:] = 0
+        if all(y is not None for y in (acc, jerk, snap, crackle)):
+            self.A[:, :3], self.J[:, :3], self.S[:, :3], self.C[:, :3] = acc, jerk, snap, crackle
+            self._next = math.inf if dt_next is None else float(dt_next)
+        else:
+            a4, j4, s4 = self._derivs6()
+            self.A[:, :3], self.J[:, :3], self.S[:, :3] = a4[:, :3], j4[:, :3], s4[:, :3]
+            self._next = math.inf
+            if self.cfg.eta > 0:
+                self._next = float(self._first_dt(self._ptr(self.A), self._ptr(self.J),
+                                                  self.cfg.n, float(self.cfg.eta)))
+        self.t, self.dt_last, self.k = float(t), 0.0, 0
+        self.dt_min = math.inf if dt_min is None else float(dt_min)
+
     def step(self, n: int) -> None:
         cfg = self.cfg
         if self.block:  # n macro steps of dt
@@ -694,10 +773,16 @@ class HermiteCpuEngine:
             cut = cfg.t_end is not None and h >= cfg.t_end - self.t
             if cut:
                 h = cfg.t_end - self.t
-            rc = self._step(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
-                            self._ptr(self.J), self._ptr(self._scratch), cfg.n,
-                            self.layout.chunk, h, self._cut2, self._eps2, float(cfg.eta),
-                            ctypes.byref(out))
+            if self.order == 6:
+                rc = self._step6(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
+                                 self._ptr(self.J), self._ptr(self.S), self._ptr(self.C),
+                                 self._ptr(self._scratch), cfg.n, self.layout.chunk, h,
+                                 self._cut2, self._eps2, float(cfg.eta), ctypes.byref(out))
+            else:
+                rc = self._step(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
+                                self._ptr(self.J), self._ptr(self._scratch), cfg.n,
+                                self.layout.chunk, h, self._cut2, self._eps2, float(cfg.eta),
+                                ctypes.byref(out))
             _native.check(self.lib, rc, "cpu hermite step")
             if self.collisions:  # (the step leaves its predicted rows at the scratch's head)
                 self._see(self._scratch[: cfg.n])
@@ -728,10 +813,13 @@ class HermiteCpuEngine:
         return BodySet(self.X[:, :3].astype(np.float64), self.V[:, :3].astype(np.float64),
                        self.mass.copy(), self.radius.copy() if self.collisions else None)
 
-    def carried(self) -> tuple[np.ndarray, np.ndarray]:
-        return self.A[:, :3].astype(np.float64), self.J[:, :3].astype(np.float64)
+    def carried(self):
+        rows = (self.A, self.J) + ((self.S, self.C) if self.order == 6 else ())
+        return tuple(y[:, :3].astype(np.float64) for y in rows)
 
-    def derivs(self, active=None, path: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
+    def derivs(self, active=None, path: Optional[str] = None):
+        if self.order == 6:
+            return tuple(y.astype(np.float64) for y in self._derivs6())
         a4, j4 = self._derivs() if active is None else self._derivs_idx(self.X, self.V, active)
         return a4.astype(np.float64), j4.astype(np.float64)
 

@@ -30,6 +30,9 @@ design:
   conserved quantities are formed from the gathered rows in the one-rank order and are the
   one-rank values bit for bit; a checkpoint resumes at any P. Block steps, collisions and the
   CPU engine stay on one rank.
+  hermite_order 6 (Nitadori & Makino 2008) carries the snap and the crackle too: a checkpoint
+  keeps all four of a, j, s, c and the order, and a checkpoint of the other order restarts its
+  derivatives from x, v, t (the log says so).
   With block_steps every body has its own step dt 2^-k and `steps` counts macro steps of dt, at
   which all bodies stand at the same time: all periodic work lands on synchronised states, and a
   checkpoint also keeps the levels.
@@ -174,11 +177,28 @@ class Simulation:
         self.step0 = 0
         self.trajectory: list[np.ndarray] = []
         self.staggered = False  # velocities held as v_{k-1/2} (leapfrog)
+        self.order_restart = False  # a hermite checkpoint of the other order was resumed
         if cfg.resume:
             c = self._resume
             if c.bodies.n != ecfg.n:
                 raise ValueError(f"checkpoint has n={c.bodies.n}, config n={cfg.n}")
-            if self.hermite and c.meta.get("integrator") == "hermite" and \
+            same_order = int(c.meta.get("hermite_order", 4)) == cfg.hermite_order
+            self.order_restart = self.hermite and c.meta.get("integrator") == "hermite" and \
+                not same_order
+            if self.order_restart:
+                warnings.warn(f"resuming a hermite checkpoint of order "
+                              f"{int(c.meta.get('hermite_order', 4))} under order "
+                              f"{cfg.hermite_order}: the derivatives restart from x, v, t",
+                              stacklevel=2)
+            if self.hermite and cfg.hermite_order == 6 and same_order and \
+                    c.meta.get("integrator") == "hermite" and \
+                    all(k in c.extra for k in ("acc", "jerk", "snap", "crackle")):
+                self.engine.load(c.bodies, c.extra["acc"], c.extra["jerk"],
+                                 t=float(c.meta.get("time", 0.0)), dt_next=c.meta.get("dt_next"),
+                                 dt_min=c.meta.get("dt_min"), snap=c.extra["snap"],
+                                 crackle=c.extra["crackle"])
+            elif self.hermite and same_order and cfg.hermite_order == 4 and \
+                    c.meta.get("integrator") == "hermite" and \
                     "acc" in c.extra and "jerk" in c.extra:
                 # the carried a, j (evaluated at the last predicted state) and the step size
                 # the criterion chose: the run continues bit for bit
@@ -395,11 +415,10 @@ class Simulation:
         extra = None
         if self.hermite:
             st = self.engine.status()
-            acc, jerk = carried
-            extra = {"acc": acc, "jerk": jerk}
+            extra = dict(zip(("acc", "jerk", "snap", "crackle"), carried))
             fin = lambda y: y if np.isfinite(y) else None  # noqa: E731
             meta.update(time=st.time, dt_next=fin(st.dt_next), dt_min=fin(st.dt_min),
-                        eta=cfg.eta)
+                        eta=cfg.eta, hermite_order=cfg.hermite_order)
             if cfg.collisions != "off":
                 col = np.zeros((b.n, 3))
                 col[:, 0], col[:, 1] = b.radii(), self.ids
@@ -530,7 +549,7 @@ class Simulation:
             gone = self._counts_gone  # (of the engines that mergers have replaced)
             # the steps this run took (none past t_end or past an overlap)
             steps = self._steps_gone - steps_gone0 + st.steps - st0.steps
-            herm = dict(time_reached=st.time, steps_taken=steps,
+            herm = dict(time_reached=st.time, steps_taken=steps, hermite_order=cfg.hermite_order,
                         dt_min=st.dt_min if np.isfinite(st.dt_min) else None)
             if cfg.block_steps:
                 body = gone["body_steps"] + st.body_steps - st0.body_steps

@@ -50,6 +50,8 @@ class RunMetrics:
     # --structure: {"k", "samples": [{"step", "time", "density_centre", "core_radius",
     # "density_max", "lagrangian_radii", "degenerate"}]} (None, and left out, otherwise)
     structure: dict | None = None
+    # integrator hermite: the order of the scheme, 4 or 6 (None, and left out, otherwise)
+    hermite_order: int | None = None
 
     @property
     def ms_per_step(self) -> float:
@@ -74,7 +76,7 @@ class RunMetrics:
         d = asdict(self)
         for k in ("time_reached", "steps_taken", "dt_min", "block_steps", "body_steps",
                   "pair_evals", "level_max", "level_clamped", "mergers", "bodies_left",
-                  "closest_q_min", "overlaps_seen", "structure"):
+                  "closest_q_min", "overlaps_seen", "structure", "hermite_order"):
             if d[k] is None:
                 del d[k]
         d.update(ms_per_step=self.ms_per_step, body_updates_per_s=self.body_updates_per_s,
