@@ -14,7 +14,9 @@ The thread count is OMP_NUM_THREADS of the caller; no result depends on it.
 Cases: n in 1, 2, 3, 257, 1024, 1031, 2055, 5000 with chunk 1024 and the automatic one. Per n and
 chunk: accel, accel_abs and two plain steps (fp64, fp32); accjerk over all rows, over a sub-range
 with i0 > 0 and over a permuted list with repeats and an empty list; first_dt; three Hermite
-steps with a fixed and three with an adaptive step (fp64, fp32, mixed); nn with zero and non-zero
+steps with a fixed and three with an adaptive step (fp64, fp32, mixed); accjerksnap over all rows
+and over a sub-range with i0 > 0, and three 6th-order steps fixed and three adaptive (fp64, fp32;
+a build without the 6th-order entries fails the run); nn with zero and non-zero
 radii over rows and a list; knn with k = 1, 3, 8 over all rows and a sub-range.
 """
 from __future__ import annotations
@@ -111,6 +113,32 @@ def cases() -> dict:
                         if eta > 0.0 and np.isfinite(dt.value):
                             h = min(3600.0, dt.value)
                     out[f"hermite_step/{tag}/eta{eta}"] = digest(x, v, a, j, np.array(dts))
+
+                if dtype == "mixed":  # (the 6th-order scheme has no mixed precision)
+                    continue
+                # accjerksnap at ap = a: all rows and a sub-range
+                A0 = A.copy()
+                A0[:, 3] = 0
+                d = []
+                for rows in ((0, n), sub):
+                    o = [np.zeros((rows[1] - rows[0], 4), T) for _ in range(3)]
+                    ok(entry("accjerksnap")[0](p(X), p(V), p(A0), n, *rows, chunk, cut2, eps2,
+                                               *map(p, o)))
+                    d += o
+                out[f"accjerksnap/{tag}"] = digest(*d)
+                # 6th-order steps (eta linear in this criterion)
+                for eta in (0.0, 0.25):
+                    x, v, a, j, s = X.copy(), V.copy(), A0.copy(), d[1].copy(), d[2].copy()
+                    c = np.zeros((n, 4), T)
+                    scratch, h, dts = np.zeros((6 * n, 4), T), 3600.0, []
+                    for _ in range(3):
+                        dt = ctypes.c_double(0.0)
+                        ok(entry("hermite6_step")[0](p(x), p(v), p(a), p(j), p(s), p(c), p(scratch),
+                                                     n, chunk, h, cut2, eps2, eta, ctypes.byref(dt)))
+                        dts.append(dt.value)
+                        if eta > 0.0 and np.isfinite(dt.value):
+                            h = min(3600.0, dt.value)
+                    out[f"hermite6_step/{tag}/eta{eta}"] = digest(x, v, a, j, s, c, np.array(dts))
 
             # nn and knn take no chunk
             if chunk != 1024:

@@ -16,6 +16,9 @@ Cases (fp32, fp64, mixed): derivs() at n = 3, 257, 2049, 5000 and, at 5000, ever
 x chunk-group shape; 3 shared steps fixed and adaptive; derivs_nn() and 3 detect-mode steps; the
 block path's derivs / derivs_nn of three active sets on both evaluate paths; two block macro
 steps under three narrow_max; the shared step on 2 and 3 virtual ranks (n = 3000, 3100, 4097).
+Order 6 (fp32, fp64): derivs() (a4, j4, s4) at the same n and, at 5000, every built bodies-per-lane
+x chunk-group (1, 3, 7, 20) shape; 3 steps fixed and 3 adaptive (eta 0.25) with state(), the four
+carried rows and (time, dt_next); a resume from the four carried rows, then 2 more steps.
 """
 from __future__ import annotations
 
@@ -158,6 +161,46 @@ def cases() -> dict:
                                                             status(g.status()), *g.derivs())
                 finally:
                     g.close()
+
+    # order 6 (fp32 and fp64 only)
+    for dtype in ("fp32", "fp64"):
+        six = dict(hermite_order=6, dt=3600.0)
+        for n in (3, 257, 2049, 5000):
+            run(f"derivs6/{dtype}/n{n}", engine(n, dtype, **six), bodies(n),
+                lambda e: digest(*e.derivs()))
+        for ipl in (1, 2):
+            if ipl == 2 and dtype == "fp64":
+                continue  # (not built)
+            for groups in (1, 3, 7, 20):
+                run(f"derivs6/{dtype}/n5000/ipl{ipl}/groups{groups}",
+                    engine(5000, dtype, ipl=ipl, split_groups=groups, **six), bodies(5000),
+                    lambda e: digest(*e.derivs()))
+
+        def stepped6(e, k=3):
+            e.step(k)
+            e.sync()
+            s, st = e.state(), e.status()
+            return digest(s.pos, s.vel, *e.carried(), np.array([st.time, st.dt_next]))
+
+        run(f"step6/{dtype}/fixed", engine(5000, dtype, **six), bodies(5000), stepped6)
+        run(f"step6/{dtype}/eta0.25", engine(5000, dtype, eta=0.25, **six), bodies(5000),
+            stepped6)
+
+        # a resume: the state and the four carried rows of a run after 3 steps, 2 more steps
+        e = engine(5000, dtype, eta=0.25, **six)
+        try:
+            e.load(bodies(5000))
+            e.step(3)
+            e.sync()
+            s, (a, j, sn, cr), st = e.state(), e.carried(), e.status()
+        finally:
+            e.close()
+        e = engine(5000, dtype, eta=0.25, **six)
+        try:
+            e.load(s, a, j, t=st.time, dt_next=st.dt_next, dt_min=st.dt_min, snap=sn, crackle=cr)
+            out[f"resume6/{dtype}"] = stepped6(e, 2)
+        finally:
+            e.close()
     return out
 
 

@@ -24,7 +24,7 @@
 #endif
 
 #include "gravsim.h"
-#include "gs_hermite6.h"
+#include "gs_hermite_scheme.h"
 
 void gs_set_error(const char* msg);
 
@@ -317,21 +317,28 @@ bool rows_ok(const char* what, bool args_ok, const int32_t* idx, int64_t i0, int
   return !why;
 }
 
-// ---- 4th-order Hermite (Makino & Aarseth 1992) --------------------------------------------
-// Acceleration, jerk and potential of body i at the rows r: the arithmetic of the GPU kernel
-// (nbody_hermite.hip hinteract), chunk sums in T from zero in j order, added in chunk order into
-// totals of type O (T, or double for mixed: the GPU's reduce). MIXED: the separation is
+// ---- the Hermite pair term (both orders) ----------------------------------------------------
+// Acceleration, jerk and potential of body i at the rows r, and (SNAP, the 6th-order scheme) the
+// snap at the predicted acceleration rows A4: the arithmetic of the GPU kernels
+// (nbody_hermite.hip hinteract, nbody_hermite6.hip h6interact, whose first 26 operations are the
+// same), chunk sums in T from zero in j order, added in chunk order into totals of type O (T, or
+// double for mixed: the GPU's reduce). MIXED (order 4 only): the separation is
 // (h_j - h_i) + (l_j - l_i).
-template <typename T, bool MIXED, typename O>
-inline void accjerk_one(const Rows<T>& r, int64_t n_real, int64_t i, int32_t chunk, T cut2, T eps2,
-                        O a4[4], O j4[4]) {
+template <typename T, bool MIXED, bool SNAP, typename O>
+inline void accjerk_one(const Rows<T>& r, const T* A4, int64_t n_real, int64_t i, int32_t chunk,
+                        T cut2, T eps2, O a4[4], O j4[4], O* s4) {
+  static_assert(!(MIXED && SNAP), "the 6th-order scheme has no mixed precision");
   const T *X4 = r.X, *L4 = r.L, *V4 = r.V;
   const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
   const T ui = V4[4 * i], vi = V4[4 * i + 1], wi = V4[4 * i + 2];
+  T bxi = 0, byi = 0, bzi = 0;
+  if constexpr (SNAP) {
+    bxi = A4[4 * i]; byi = A4[4 * i + 1]; bzi = A4[4 * i + 2];
+  }
   const int64_t n_chunks = (n_real + chunk - 1) / chunk;
-  O tx = 0, ty = 0, tz = 0, tp = 0, sx = 0, sy = 0, sz = 0;
+  O ta[4] = {0, 0, 0, 0}, tj[3] = {0, 0, 0}, ts[3] = {0, 0, 0};
   for (int64_t c = 0; c < n_chunks; ++c) {
-    T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0;
+    T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0, sx = 0, sy = 0, sz = 0;
     const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
     for (int64_t j = j0; j < j1; ++j) {
       T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
@@ -347,33 +354,59 @@ inline void accjerk_one(const Rows<T>& r, int64_t n_real, int64_t i, int32_t chu
       const T mi = X4[4 * j + 3] * inv;
       const T s = mi * inv2;
       const T dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
-      const T al = dw * (T(3) * inv2);
+      const T i3 = T(3) * inv2;
+      const T al3 = dw * i3;  // 3 alpha
+      const T ux = std::fma(-al3, dx, wx), uy = std::fma(-al3, dy, wy),
+              uz = std::fma(-al3, dz, wz);
       ax = std::fma(s, dx, ax);
       ay = std::fma(s, dy, ay);
       az = std::fma(s, dz, az);
-      jx = std::fma(s, std::fma(-al, dx, wx), jx);
-      jy = std::fma(s, std::fma(-al, dy, wy), jy);
-      jz = std::fma(s, std::fma(-al, dz, wz), jz);
+      jx = std::fma(s, ux, jx);
+      jy = std::fma(s, uy, jy);
+      jz = std::fma(s, uz, jz);
       ph += mi;
+      if constexpr (SNAP) {
+        const T qx = A4[4 * j] - bxi, qy = A4[4 * j + 1] - byi, qz = A4[4 * j + 2] - bzi;
+        const T ww = std::fma(wz, wz, std::fma(wy, wy, wx * wx));
+        const T dq = std::fma(dz, qz, std::fma(dy, qy, dx * qx));
+        const T al = dw * inv2;
+        const T be3 = std::fma(al3, al, (ww + dq) * i3);  // 3 beta
+        const T al6 = al3 + al3;
+        sx = std::fma(s, std::fma(-al6, ux, std::fma(-be3, dx, qx)), sx);
+        sy = std::fma(s, std::fma(-al6, uy, std::fma(-be3, dy, qy)), sy);
+        sz = std::fma(s, std::fma(-al6, uz, std::fma(-be3, dz, qz)), sz);
+      }
     }
-    tx += ax; ty += ay; tz += az; tp += ph;
-    sx += jx; sy += jy; sz += jz;
+    ta[0] += ax; ta[1] += ay; ta[2] += az; ta[3] += ph;
+    tj[0] += jx; tj[1] += jy; tj[2] += jz;
+    if constexpr (SNAP) {
+      ts[0] += sx; ts[1] += sy; ts[2] += sz;
+    }
   }
-  a4[0] = tx; a4[1] = ty; a4[2] = tz; a4[3] = -tp;
-  j4[0] = sx; j4[1] = sy; j4[2] = sz; j4[3] = 0;
+  a4[0] = ta[0]; a4[1] = ta[1]; a4[2] = ta[2]; a4[3] = -ta[3];
+  j4[0] = tj[0]; j4[1] = tj[1]; j4[2] = tj[2]; j4[3] = 0;
+  if constexpr (SNAP) {
+    s4[0] = ts[0]; s4[1] = ts[1]; s4[2] = ts[2]; s4[3] = 0;
+  }
 }
 
 // Row k of the output is body idx[k] (a block step's active set), or (idx null) body i0 + k.
-template <typename S, bool MIXED>
+// SNAP: A4 the predicted acceleration rows, snap4 the third output (both null otherwise).
+template <typename S, bool MIXED, bool SNAP = false>
 int accjerk_rows(const S* X4, const S* V4, int64_t n_real, const int32_t* idx, int64_t i0,
-                 int64_t n_idx, int32_t chunk, S cut2, S eps2, S* acc4, S* jerk4) {
+                 int64_t n_idx, int32_t chunk, S cut2, S eps2, S* acc4, S* jerk4,
+                 const S* A4 = nullptr, S* snap4 = nullptr) {
   using T = pair_t<S, MIXED>;
-  if (!rows_ok("cpu_accjerk", chunk > 0, idx, i0, n_idx, n_real)) return -1;
+  const bool args_ok = chunk > 0 && (!SNAP || (X4 && V4 && A4 && acc4 && jerk4 && snap4));
+  if (!rows_ok(SNAP ? "cpu_accjerksnap" : "cpu_accjerk", args_ok, idx, i0, n_idx, n_real))
+    return -1;
   const Rows<T> r = make_rows<S, MIXED>(X4, V4, n_real);
+  const T* AP = nullptr;
+  if constexpr (SNAP) AP = A4;
 #pragma omp parallel for schedule(static)
   for (int64_t k = 0; k < n_idx; ++k)
-    accjerk_one<T, MIXED, S>(r, n_real, idx ? idx[k] : i0 + k, chunk, (T)cut2, (T)eps2,
-                             acc4 + 4 * k, jerk4 + 4 * k);
+    accjerk_one<T, MIXED, SNAP, S>(r, AP, n_real, idx ? idx[k] : i0 + k, chunk, (T)cut2, (T)eps2,
+                                   acc4 + 4 * k, jerk4 + 4 * k, SNAP ? snap4 + 4 * k : nullptr);
   return 0;
 }
 
@@ -491,17 +524,15 @@ int knn_rows(const S* X4, int64_t n_real, int64_t i0, int64_t i1, int32_t k, S* 
   return 0;
 }
 
-inline double norm3(double x, double y, double z) { return std::sqrt(x * x + y * y + z * z); }
-
 template <typename T>
 double hermite_first_dt(const T* A4, const T* J4, int64_t n, double eta) {
   double dtm = INFINITY;
 #pragma omp parallel for schedule(static) reduction(min : dtm)
   for (int64_t i = 0; i < n; ++i) {
-    const double an = norm3(A4[4 * i], A4[4 * i + 1], A4[4 * i + 2]);
-    const double jn = norm3(J4[4 * i], J4[4 * i + 1], J4[4 * i + 2]);
-    const double d = 0.5 * eta * an / jn;
-    if (jn > 0.0 && std::isfinite(d) && d < dtm) dtm = d;
+    const double a[3] = {A4[4 * i], A4[4 * i + 1], A4[4 * i + 2]};
+    const double j[3] = {J4[4 * i], J4[4 * i + 1], J4[4 * i + 2]};
+    double d;
+    if (gs::hermite_first_dt(eta, a, j, d) && d < dtm) dtm = d;
   }
   return dtm;
 }
@@ -523,114 +554,39 @@ int hermite_step(T* X4, T* V4, T* A4, T* J4, T* scratch, int64_t n, int32_t chun
   for (int64_t i = 0; i < n; ++i) {
     for (int d = 0; d < 3; ++d) {
       const int64_t k = 4 * i + d;
-      XP[k] = X4[k] + (V4[k] * h + (A4[k] * h2 + J4[k] * h3));
-      VP[k] = V4[k] + (A4[k] * h + J4[k] * h2);
+      gs::h4_predict(h, h2, h3, X4[k], V4[k], A4[k], J4[k], XP[k], VP[k]);
     }
     XP[4 * i + 3] = X4[4 * i + 3];
     VP[4 * i + 3] = 0;
   }
   if (accjerk_rows<T, MIXED>(XP, VP, n, nullptr, 0, n, chunk, cut2, eps2, A1, J1)) return -1;
   const T hh = h / T(2), h12 = (h * h) / T(12);
-  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
   double dtm = INFINITY;
 #pragma omp parallel for schedule(static) reduction(min : dtm)
   for (int64_t i = 0; i < n; ++i) {
-    double s2[3], s3[3];
+    double a0[3], j0[3], a1[3], j1[3];
     for (int d = 0; d < 3; ++d) {
       const int64_t k = 4 * i + d;
-      const T a0 = A4[k], j0 = J4[k], a1 = A1[k], j1 = J1[k], v = V4[k];
-      const T v1 = v + ((a0 + a1) * hh + (j0 - j1) * h12);
-      X4[k] = X4[k] + ((v + v1) * hh + (a0 - a1) * h12);
+      a0[d] = A4[k]; j0[d] = J4[k]; a1[d] = A1[k]; j1[d] = J1[k];
+      T x1, v1;
+      gs::h4_correct(hh, h12, X4[k], V4[k], A4[k], J4[k], A1[k], J1[k], x1, v1);
+      X4[k] = x1;
       V4[k] = v1;
-      A4[k] = a1;
-      J4[k] = j1;
-      const double da = (double)a0 - (double)a1;
-      const double a2 = (-6.0 * da - hd * (4.0 * (double)j0 + 2.0 * (double)j1)) * ih2;
-      s3[d] = (12.0 * da + 6.0 * hd * ((double)j0 + (double)j1)) * ih3;
-      s2[d] = a2 + hd * s3[d];
+      A4[k] = A1[k];
+      J4[k] = J1[k];
     }
     A4[4 * i + 3] = 0;
     J4[4 * i + 3] = 0;
-    if (eta > 0.0) {
-      const double an = norm3(A4[4 * i], A4[4 * i + 1], A4[4 * i + 2]);
-      const double jn = norm3(J4[4 * i], J4[4 * i + 1], J4[4 * i + 2]);
-      const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
-      const double d = std::sqrt(eta * (an * n2 + jn * jn) / (jn * n3 + n2 * n2));
-      if (jn > 0.0 && std::isfinite(d) && d < dtm) dtm = d;
-    }
+    double d;
+    if (eta > 0.0 && gs::h4_dt(hd, eta, a0, j0, a1, j1, d) && d < dtm) dtm = d;
   }
   if (dt_min_out) *dt_min_out = dtm;
   return 0;
 }
 
-// ---- 6th-order Hermite (Nitadori & Makino 2008; gs_hermite6.h) ------------------------------
-// Acceleration, jerk, snap and potential of body i at (X4, V4, A4): the arithmetic of the GPU
-// kernel (nbody_hermite6.hip h6interact; its first part is accjerk_one's), chunk sums from zero
-// in j order, added in chunk order.
-template <typename T>
-inline void accjerksnap_one(const T* X4, const T* V4, const T* A4, int64_t n_real, int64_t i,
-                            int32_t chunk, T cut2, T eps2, T a4[4], T j4[4], T s4[4]) {
-  const T xi = X4[4 * i], yi = X4[4 * i + 1], zi = X4[4 * i + 2];
-  const T ui = V4[4 * i], vi = V4[4 * i + 1], wi = V4[4 * i + 2];
-  const T bxi = A4[4 * i], byi = A4[4 * i + 1], bzi = A4[4 * i + 2];
-  const int64_t n_chunks = (n_real + chunk - 1) / chunk;
-  T tot[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int64_t c = 0; c < n_chunks; ++c) {
-    T ax = 0, ay = 0, az = 0, ph = 0, jx = 0, jy = 0, jz = 0, sx = 0, sy = 0, sz = 0;
-    const int64_t j0 = c * chunk, j1 = j0 + chunk < n_real ? j0 + chunk : n_real;
-    for (int64_t j = j0; j < j1; ++j) {
-      const T dx = X4[4 * j] - xi, dy = X4[4 * j + 1] - yi, dz = X4[4 * j + 2] - zi;
-      const T wx = V4[4 * j] - ui, wy = V4[4 * j + 1] - vi, wz = V4[4 * j + 2] - wi;
-      const T qx = A4[4 * j] - bxi, qy = A4[4 * j + 1] - byi, qz = A4[4 * j + 2] - bzi;
-      const T r2 = std::fma(dz, dz, std::fma(dy, dy, std::fma(dx, dx, eps2)));
-      const T inv = (r2 >= cut2) ? rsqrt_ref(r2) : T(0);
-      const T inv2 = inv * inv;
-      const T mi = X4[4 * j + 3] * inv;
-      const T s = mi * inv2;
-      const T dw = std::fma(dz, wz, std::fma(dy, wy, dx * wx));
-      const T i3 = T(3) * inv2;
-      const T al3 = dw * i3;
-      const T ww = std::fma(wz, wz, std::fma(wy, wy, wx * wx));
-      const T dq = std::fma(dz, qz, std::fma(dy, qy, dx * qx));
-      const T al = dw * inv2;
-      const T be3 = std::fma(al3, al, (ww + dq) * i3);
-      const T al6 = al3 + al3;
-      const T ux = std::fma(-al3, dx, wx), uy = std::fma(-al3, dy, wy),
-              uz = std::fma(-al3, dz, wz);
-      ax = std::fma(s, dx, ax);
-      ay = std::fma(s, dy, ay);
-      az = std::fma(s, dz, az);
-      jx = std::fma(s, ux, jx);
-      jy = std::fma(s, uy, jy);
-      jz = std::fma(s, uz, jz);
-      sx = std::fma(s, std::fma(-al6, ux, std::fma(-be3, dx, qx)), sx);
-      sy = std::fma(s, std::fma(-al6, uy, std::fma(-be3, dy, qy)), sy);
-      sz = std::fma(s, std::fma(-al6, uz, std::fma(-be3, dz, qz)), sz);
-      ph += mi;
-    }
-    const T part[10] = {ax, ay, az, ph, jx, jy, jz, sx, sy, sz};
-    for (int k = 0; k < 10; ++k) tot[k] += part[k];
-  }
-  a4[0] = tot[0]; a4[1] = tot[1]; a4[2] = tot[2]; a4[3] = -tot[3];
-  j4[0] = tot[4]; j4[1] = tot[5]; j4[2] = tot[6]; j4[3] = 0;
-  s4[0] = tot[7]; s4[1] = tot[8]; s4[2] = tot[9]; s4[3] = 0;
-}
-
-template <typename T>
-int accjerksnap_rows(const T* X4, const T* V4, const T* A4, int64_t n_real, int64_t i0,
-                     int64_t i1, int32_t chunk, T cut2, T eps2, T* acc4, T* jerk4, T* snap4) {
-  if (!rows_ok("cpu_accjerksnap", chunk > 0 && X4 && V4 && A4 && acc4 && jerk4 && snap4, nullptr,
-               i0, i1 - i0, n_real))
-    return -1;
-#pragma omp parallel for schedule(static)
-  for (int64_t i = i0; i < i1; ++i)
-    accjerksnap_one<T>(X4, V4, A4, n_real, i, chunk, cut2, eps2, acc4 + 4 * (i - i0),
-                       jerk4 + 4 * (i - i0), snap4 + 4 * (i - i0));
-  return 0;
-}
-
+// ---- 6th-order Hermite (Nitadori & Makino 2008; gs_hermite_scheme.h) ----------------------
 // One 6th-order step of size h in place (the GPU chain's predict / evaluate / correct
-// arithmetic, gs_hermite6.h). scratch: xp, vp, ap, a1, j1, s1 (n * 4 each).
+// arithmetic, gs_hermite_scheme.h). scratch: xp, vp, ap, a1, j1, s1 (n * 4 each).
 template <typename T>
 int hermite6_step(T* X4, T* V4, T* A4, T* J4, T* S4, T* C4, T* scratch, int64_t n, int32_t chunk,
                   double hd, T cut2, T eps2, double eta, double* dt_min_out) {
@@ -652,7 +608,8 @@ int hermite6_step(T* X4, T* V4, T* A4, T* J4, T* S4, T* C4, T* scratch, int64_t 
     VP[4 * i + 3] = 0;
     AP[4 * i + 3] = 0;
   }
-  if (accjerksnap_rows<T>(XP, VP, AP, n, 0, n, chunk, cut2, eps2, A1, J1, S1)) return -1;
+  if (accjerk_rows<T, false, true>(XP, VP, n, nullptr, 0, n, chunk, cut2, eps2, A1, J1, AP, S1))
+    return -1;
   double dtm = INFINITY;
 #pragma omp parallel for schedule(static) reduction(min : dtm)
   for (int64_t i = 0; i < n; ++i) {
@@ -681,14 +638,14 @@ extern "C" {
 int gs_cpu_accjerksnap_f64(const double* X4, const double* V4, const double* A4, int64_t n_real,
                            int64_t i0, int64_t i1, int32_t chunk, double cut2, double eps2,
                            double* acc4, double* jerk4, double* snap4) {
-  return accjerksnap_rows<double>(X4, V4, A4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4,
-                                  snap4);
+  return accjerk_rows<double, false, true>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2,
+                                           acc4, jerk4, A4, snap4);
 }
 int gs_cpu_accjerksnap_f32(const float* X4, const float* V4, const float* A4, int64_t n_real,
                            int64_t i0, int64_t i1, int32_t chunk, float cut2, float eps2,
                            float* acc4, float* jerk4, float* snap4) {
-  return accjerksnap_rows<float>(X4, V4, A4, n_real, i0, i1, chunk, cut2, eps2, acc4, jerk4,
-                                 snap4);
+  return accjerk_rows<float, false, true>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2,
+                                          acc4, jerk4, A4, snap4);
 }
 int gs_cpu_hermite6_step_f64(double* X4, double* V4, double* A4, double* J4, double* S4,
                              double* C4, double* scratch, int64_t n_real, int32_t chunk, double h,

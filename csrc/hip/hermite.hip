@@ -1,9 +1,13 @@
-// Runtime of the 4th-order Hermite integrator (gs_hermite_* in gravsim.h).
+// Runtime of the Hermite integrators, 4th and 6th order (gs_hermite_* in gravsim.h).
 //
 // Device-resident state x, v, a, j (4 components per body, n_pad rows, ghost rows zero) and a
 // control block (t, h, steps; gs_hermite.h). A step is four launches on one stream: control,
 // predict, evaluate (the hot acceleration+jerk kernel, nbody_hermite.hip), reduce + correct.
 // The step size and the time live on the device, so enqueueing steps never waits for one.
+// The order is a property of the run (gs_hermite_set_order): order 6 also carries snap and
+// crackle rows, its chain is the same four launches with the kernels of nbody_hermite6.hip, and
+// the one path below asks the order where the two differ (with_args, launch_shape, eval_current,
+// the carried rows). It runs on one rank in fp32 or fp64 with shared steps (refuse6).
 // Block mode (gs_hermite_set_block): per-body times and levels, an active list and a second
 // control block; a block step is a chain of seven launches, and gs_hermite_step advances whole
 // macro steps of dt against a device-side target time, one status read per 32 chains.
@@ -26,7 +30,6 @@
 #include <vector>
 
 #include "gs_hermite.h"
-#include "gs_hermite6.h"
 #include "gs_stepper.h"
 
 struct gs_hermite {
@@ -96,9 +99,9 @@ int nwg(const gs_hermite* h) { return (int)(h->n_pad / gs::kForceBlock); }
 bool multi(const gs_hermite* h) { return h->cfg.nranks > 1; }
 constexpr int64_t kUnit = 1024;  // rows per ownership unit (gs_hermite_partition)
 
+// The kernel arguments of a launch: order 4 (T the pair type, S the state type) and order 6.
 template <typename T, typename S>
-gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
-  gs::HArgs<T, S> a{};
+void set_args(const gs_hermite* h, int mode, bool phi, gs::HArgs<T, S>& a) {
   a.X = static_cast<S*>(h->X); a.V = static_cast<S*>(h->V);
   a.A = static_cast<S*>(h->A); a.J = static_cast<S*>(h->J);
   a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.XL = static_cast<T*>(h->XL);
@@ -118,27 +121,105 @@ gs::HArgs<T, S> make_args(const gs_hermite* h, int mode, bool phi) {
   a.nn_q = h->nn_q; a.nn_i = h->nn_i; a.ca_q = h->ca_q; a.ca_i = h->ca_i;
   a.q_out = h->q_out; a.nn_out = h->nn_out;
   a.row0 = h->row0; a.n_loc = h->n_loc;
+}
+
+template <typename T>
+void set_args(const gs_hermite* h, int mode, bool phi, gs::H6Args<T>& a) {
+  a.X = static_cast<T*>(h->X); a.V = static_cast<T*>(h->V);
+  a.A = static_cast<T*>(h->A); a.J = static_cast<T*>(h->J);
+  a.S = static_cast<T*>(h->S); a.C = static_cast<T*>(h->C);
+  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.AP = static_cast<T*>(h->AP);
+  a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ); a.PS = static_cast<T*>(h->PS);
+  a.a_out = static_cast<T*>(h->a_out); a.j_out = static_cast<T*>(h->j_out);
+  a.s_out = static_cast<T*>(h->s_out);
+  a.ctrl = h->ctrl;
+  a.wgmin = h->wgmin;
+  a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
+  a.mode = mode;
+  a.phi = phi ? 1 : 0;
+  a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
+  a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
+}
+
+template <typename A>
+A make_args(const gs_hermite* h, int mode, bool phi) {
+  A a{};
+  set_args(h, mode, phi, a);
   return a;
+}
+
+// f(the kernel arguments of the run's precision and order): HArgs<T, S>, or H6Args<T> for a run
+// of order 6 (fp32 or fp64: refuse6).
+template <typename F>
+int with_args(const gs_hermite* h, int mode, bool phi, F f) {
+  if (h->order == 6)
+    return h->esz == 4 ? f(make_args<gs::H6Args<float>>(h, mode, phi))
+                       : f(make_args<gs::H6Args<double>>(h, mode, phi));
+  return by_dtype(h, [&](auto t, auto s) {
+    return f(make_args<gs::HArgs<decltype(t), decltype(s)>>(h, mode, phi));
+  });
+}
+
+// The four launches of a shared step, by the type of the kernel arguments.
+template <typename T, typename S>
+hipError_t launch_ctrl(const gs::HArgs<T, S>& a, hipStream_t s) {
+  return gs::launch_hermite_ctrl<T, S>(a, s);
+}
+template <typename T, typename S>
+hipError_t launch_predict(const gs::HArgs<T, S>& a, hipStream_t s) {
+  return gs::launch_hermite_predict<T, S>(a, s);
+}
+template <typename T, typename S>
+hipError_t launch_eval(const gs::HArgs<T, S>& a, int ipl, int groups, bool gated, hipStream_t s) {
+  return gs::launch_hermite_eval<T, S>(a, ipl, groups, gated, s);
+}
+template <typename T, typename S>
+hipError_t launch_reduce(const gs::HArgs<T, S>& a, hipStream_t s) {
+  return gs::launch_hermite_reduce<T, S>(a, s);
+}
+template <typename T>
+hipError_t launch_ctrl(const gs::H6Args<T>& a, hipStream_t s) {
+  gs::HArgs<T, T> c{};  // (the control kernel, shared with order 4, reads these three)
+  c.ctrl = a.ctrl;
+  c.wgmin = a.wgmin;
+  c.n_pad = a.n_pad;
+  return gs::launch_hermite_ctrl<T, T>(c, s);
+}
+template <typename T>
+hipError_t launch_predict(const gs::H6Args<T>& a, hipStream_t s) {
+  return gs::launch_hermite6_predict<T>(a, s);
+}
+template <typename T>
+hipError_t launch_eval(const gs::H6Args<T>& a, int ipl, int groups, bool gated, hipStream_t s) {
+  return gs::launch_hermite6_eval<T>(a, ipl, groups, gated, s);
+}
+template <typename T>
+hipError_t launch_reduce(const gs::H6Args<T>& a, hipStream_t s) {
+  return gs::launch_hermite6_reduce<T>(a, s);
 }
 
 int read_ctrl(gs_hermite* h, gs::HermiteCtrl* c);
 
 // Launch shape (any choice gives the same bits): the widest lane tile that still leaves about
-// four workgroups per CU, then as many chunk groups as reach that count. Mixed precision with
-// collisions on has no 4-body tile (it would need all 256 VGPRs): 2 bodies per lane there,
-// also where the configuration asks for 4, and the layout reports what runs.
+// four workgroups per CU, then as many chunk groups as reach that count. Order 4: mixed
+// precision with collisions on has no 4-body tile (it would need all 256 VGPRs): 2 bodies per
+// lane there, also where the configuration asks for 4, and the layout reports what runs.
+// Order 6 is built with 1 or (fp32) 2 bodies per lane.
 int launch_shape(gs_hermite* h) {
   const int fp64 = h->cfg.dtype == GS_FP64;
-  const int top = fp64 || (is_mixed(h) && h->nn) ? 2 : 4;
+  const bool six = h->order == 6;
+  const int top = six ? (fp64 ? 1 : 2) : (fp64 || (is_mixed(h) && h->nn) ? 2 : 4);
+  const int low = six || fp64 ? 1 : 2;  // (the automatic choice goes no narrower)
   const int64_t want = 1024;
   int ipl = h->cfg.ipl;
   if (ipl == 0) {
     ipl = top;
-    while (ipl > (fp64 ? 1 : 2) && h->n_loc / (gs::kForceBlock * ipl) * h->n_chunks < want)
-      ipl >>= 1;
+    while (ipl > low && h->n_loc / (gs::kForceBlock * ipl) * h->n_chunks < want) ipl >>= 1;
   }
-  if (!gs::hermite_ipl_ok(fp64, ipl) || h->n_loc % (gs::kForceBlock * ipl)) {
-    gs_set_error("hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
+  if (!(six ? gs::hermite6_ipl_ok(fp64, ipl) : gs::hermite_ipl_ok(fp64, ipl)) ||
+      h->n_loc % (gs::kForceBlock * ipl)) {
+    gs_set_error(six ? "hermite order 6: ipl must be 1 (or 2 for fp32)"
+                     : "hermite: ipl must be 1, 2 (or 4 for fp32 and mixed)");
     return -1;
   }
   if (ipl > top) ipl = top;
@@ -205,14 +286,49 @@ int point_at_current(gs_hermite* h, gs::HArgs<T, S>& a) {
   return 0;
 }
 
-// Derivatives of the current (x, v) through the step's own kernel, then the reduce in `mode`.
-template <typename T, typename S>
-int eval_current(gs_hermite* h, int mode, bool phi) {
-  gs::HArgs<T, S> a = make_args<T, S>(h, mode, phi);
-  if (point_at_current(h, a)) return -1;
-  GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));
-  GS_HIP((gs::launch_hermite_reduce<T, S>(a, h->stream)));
+template <typename T>
+int point_at_current(gs_hermite*, gs::H6Args<T>& a) {
+  a.XP = a.X;
+  a.VP = a.V;
   return 0;
+}
+
+// Derivatives of the current (x, v) through the step's own kernel, then the reduce in a.mode
+// (HM_INIT: into the carried rows, and the first step's minima; HM_OUT: the outputs).
+template <typename A>
+int eval_current(gs_hermite* h, A a) {
+  if (point_at_current(h, a)) return -1;
+  if constexpr (std::is_same<A, gs::H6Args<float>>::value ||
+                std::is_same<A, gs::H6Args<double>>::value) {
+    // Order 6 takes two passes: this one with ap = 0 gives a (and j), the one below with ap = a
+    // gives s (and phi where asked).
+    A first = a;
+    first.phi = 0;
+    GS_HIP(hipMemsetAsync(h->AP, 0, rows_bytes(h), h->stream));
+    GS_HIP(launch_eval(first, h->ipl, h->groups, false, h->stream));
+    GS_HIP(launch_reduce(first, h->stream));
+    GS_HIP(hipMemcpyAsync(h->AP, a.mode == gs::HM_INIT ? h->A : h->a_out, rows_bytes(h),
+                          hipMemcpyDeviceToDevice, h->stream));
+  }
+  GS_HIP(launch_eval(a, h->ipl, h->groups, false, h->stream));
+  GS_HIP(launch_reduce(a, h->stream));
+  return 0;
+}
+
+// What order 6 does not run with, each stated once: the settings of the engine itself, then
+// what a caller is about to switch on (`asked`). Null: nothing stands in the way.
+enum { R6_NONE, R6_BLOCK, R6_NN, R6_GROUP };
+const char* refuse6(const gs_hermite* h, int asked = R6_NONE) {
+  if (multi(h)) return "hermite order 6 runs on one rank (nranks > 1, --gpus, is refused)";
+  if (h->cfg.dtype == GS_MIXED)
+    return "hermite order 6 has no mixed precision (GS_MIXED, --dtype mixed, is refused)";
+  if (h->block || asked == R6_BLOCK)
+    return "hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)";
+  if (h->nn || asked == R6_NN)
+    return "hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)";
+  if (asked == R6_GROUP)
+    return "hermite group: order 6 runs on one rank (no virtual group, gs_hermite_group_*)";
+  return nullptr;
 }
 
 // ---- ranks -----------------------------------------------------------------------------
@@ -305,8 +421,8 @@ int check_group(gs_hermite* const* sh, int P) {
   for (int r = 0; r < P; ++r)
     if (!sh[r]) { gs_set_error("hermite group: null shard"); return -1; }
   for (int r = 0; r < P; ++r)
-    if (sh[r]->order != 4) {
-      gs_set_error("hermite group: order 6 runs on one rank (no virtual group, gs_hermite_group_*)");
+    if (sh[r]->order == 6) {
+      gs_set_error(refuse6(sh[r], R6_GROUP));
       return -1;
     }
   if (P == 1) return 0;
@@ -339,24 +455,24 @@ int close_wgmin(gs_hermite* const* sh, int P) {
 
 int wait_seen(gs_hermite* h, int64_t target);
 
-template <typename T, typename S>
+// nsteps shared steps of the P shards; A: the kernel arguments (with_args; order 6: P is 1).
+template <typename A>
 int step_t(gs_hermite* const* sh, int P, int32_t nsteps) {
   if (close_wgmin(sh, P)) return -1;
-  std::vector<gs::HArgs<T, S>> a;
-  for (int r = 0; r < P; ++r) a.push_back(make_args<T, S>(sh[r], gs::HM_STEP, false));
+  std::vector<A> a;
+  for (int r = 0; r < P; ++r) a.push_back(make_args<A>(sh[r], gs::HM_STEP, false));
   const bool mixed = is_mixed(sh[0]);
   for (int32_t k = 0; k < nsteps; ++k) {
     for (int r = 0; r < P; ++r) {
-      GS_HIP((gs::launch_hermite_ctrl<T, S>(a[r], sh[r]->stream)));
-      GS_HIP((gs::launch_hermite_predict<T, S>(a[r], sh[r]->stream)));
+      GS_HIP(launch_ctrl(a[r], sh[r]->stream));
+      GS_HIP(launch_predict(a[r], sh[r]->stream));
     }
     // (the same collectives on every rank whatever ctrl->active is: a chain past t_end gathers
     // stale rows and changes nothing)
     if (mixed ? gather(sh, P, {G_XP, G_VP, G_XL}) : gather(sh, P, {G_XP, G_VP})) return -1;
     for (int r = 0; r < P; ++r) {
-      GS_HIP((gs::launch_hermite_eval<T, S>(a[r], sh[r]->ipl, sh[r]->groups, true,
-                                            sh[r]->stream)));
-      GS_HIP((gs::launch_hermite_reduce<T, S>(a[r], sh[r]->stream)));
+      GS_HIP(launch_eval(a[r], sh[r]->ipl, sh[r]->groups, true, sh[r]->stream));
+      GS_HIP(launch_reduce(a[r], sh[r]->stream));
     }
     if (gather(sh, P, {G_WGMIN})) return -1;
     gs_hermite* h = sh[0];
@@ -558,7 +674,7 @@ int reset_bctrl(gs_hermite* h, int64_t macro) {
 template <typename T, typename S>
 int block_start_t(gs_hermite* h, int64_t macro) {
   if (reset_bctrl(h, macro)) return -1;
-  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+  const gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_STEP, false);
   GS_HIP((gs::launch_block_init<T, S>(a, macro << h->max_level, h->stream)));
   return 0;
 }
@@ -594,7 +710,7 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
   if (target <= c.t_ticks) return 0;
   c.target = target;
   if (write_bctrl(h, c)) return -1;
-  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+  const gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_STEP, false);
   while (c.t_ticks < target) {
     const int64_t before = c.t_ticks;
     for (int k = 0; k < 32; ++k)
@@ -621,7 +737,7 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
                         h->stream));
   if (write_bctrl(h, c)) return -1;
-  gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_OUT, true);
+  gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_OUT, true);
   if (point_at_current(h, a)) return -1;
   EventTimer timer;
   if (ms && (timer.create() || timer.start(h->stream))) return -1;
@@ -642,131 +758,32 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   return write_bctrl(h, keep);
 }
 
-// ---- 6th order (one rank, fp32 or fp64, shared steps) ------------------------------------
-
-template <typename F>
-int by_dtype6(const gs_hermite* h, F f) {
-  return h->esz == 4 ? f(float()) : f(double());
-}
-
-template <typename T>
-gs::H6Args<T> make_args6(const gs_hermite* h, int mode, bool phi) {
-  gs::H6Args<T> a{};
-  a.X = static_cast<T*>(h->X); a.V = static_cast<T*>(h->V);
-  a.A = static_cast<T*>(h->A); a.J = static_cast<T*>(h->J);
-  a.S = static_cast<T*>(h->S); a.C = static_cast<T*>(h->C);
-  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.AP = static_cast<T*>(h->AP);
-  a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ); a.PS = static_cast<T*>(h->PS);
-  a.a_out = static_cast<T*>(h->a_out); a.j_out = static_cast<T*>(h->j_out);
-  a.s_out = static_cast<T*>(h->s_out);
-  a.ctrl = h->ctrl;
-  a.wgmin = h->wgmin;
-  a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
-  a.mode = mode;
-  a.phi = phi ? 1 : 0;
-  a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
-  a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
-  return a;
-}
-
-// Launch shape of the order-6 evaluate (any choice gives the same bits): 2 i-bodies per lane in
-// fp32 while that leaves about four workgroups per CU, else 1; chunk groups as launch_shape().
-int launch_shape6(gs_hermite* h) {
-  const int fp64 = h->cfg.dtype == GS_FP64;
-  const int64_t want = 1024;
-  int ipl = h->cfg.ipl;
-  if (ipl == 0)
-    ipl = !fp64 && h->n_pad / (gs::kForceBlock * 2) * h->n_chunks >= want ? 2 : 1;
-  if (!gs::hermite6_ipl_ok(fp64, ipl) || h->n_pad % (gs::kForceBlock * ipl)) {
-    gs_set_error("hermite order 6: ipl must be 1 (or 2 for fp32)");
-    return -1;
-  }
-  h->ipl = ipl;
-  const int64_t blocks = h->n_pad / (gs::kForceBlock * ipl);
-  int64_t groups =
-      h->cfg.split_groups > 0 ? h->cfg.split_groups : (2 * want + blocks - 1) / blocks;
-  if (groups > h->n_chunks) groups = h->n_chunks;
-  if (groups < 1) groups = 1;
-  h->groups = (int32_t)groups;
-  return 0;
-}
-
-void free_order6(gs_hermite* h) {
-  for (void** p : {&h->S, &h->C, &h->AP, &h->PS, &h->s_out}) {
+// The arrays order 6 adds to the run's (snap and crackle rows, the predicted acceleration, the
+// snap output, the snap partials), the one place that frees and allocates them: they exist
+// exactly while the order is 6 (`on`).
+int size_order6(gs_hermite* h, bool on) {
+  for (void** p : {&h->S, &h->C, &h->AP, &h->s_out, &h->PS}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
+    if (!on) continue;
+    const bool rows = p != &h->PS;  // (the partials: a row per chunk, written before they are read)
+    GS_HIP(hipMalloc(p, rows_bytes(h) * (rows ? 1 : (size_t)h->n_chunks)));
+    if (rows) GS_HIP(hipMemsetAsync(*p, 0, rows_bytes(h), h->stream));
   }
-}
-
-// a, j, s (and phi) of the current (x, v) through the step's own kernel, in two passes: the
-// first with ap = 0 gives a (and j), the second with ap = a gives s; then the reduce in `mode`
-// (HM_INIT: into the carried rows, c <- 0, and the first step's minima; HM_OUT: the outputs).
-template <typename T>
-int eval6_current(gs_hermite* h, int mode, bool phi) {
-  gs::H6Args<T> a = make_args6<T>(h, mode, false);
-  a.XP = a.X;
-  a.VP = a.V;
-  GS_HIP(hipMemsetAsync(h->AP, 0, rows_bytes(h), h->stream));
-  GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, false, h->stream)));
-  GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
-  GS_HIP(hipMemcpyAsync(h->AP, mode == gs::HM_INIT ? h->A : h->a_out, rows_bytes(h),
-                        hipMemcpyDeviceToDevice, h->stream));
-  a.phi = phi ? 1 : 0;
-  GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, false, h->stream)));
-  GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
+  if (on) GS_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
 
-template <typename T>
-int step6_t(gs_hermite* h, int32_t nsteps) {
-  const gs::H6Args<T> a = make_args6<T>(h, gs::HM_STEP, false);
-  gs::HArgs<T, T> c{};  // (the control kernel reads these three)
-  c.ctrl = h->ctrl;
-  c.wgmin = h->wgmin;
-  c.n_pad = h->n_pad;
-  for (int32_t k = 0; k < nsteps; ++k) {
-    GS_HIP((gs::launch_hermite_ctrl<T, T>(c, h->stream)));
-    GS_HIP((gs::launch_hermite6_predict<T>(a, h->stream)));
-    GS_HIP((gs::launch_hermite6_eval<T>(a, h->ipl, h->groups, true, h->stream)));
-    GS_HIP((gs::launch_hermite6_reduce<T>(a, h->stream)));
-  }
-  return 0;
-}
-
-int start6(gs_hermite* h) {
-  if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) return -1;
-  return by_dtype6(h, [&](auto t) {
-    return eval6_current<decltype(t)>(h, gs::HM_INIT, false);
-  });
-}
-
-int derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4) {
-  GS_HIP(hipSetDevice(h->cfg.device));
-  if (by_dtype6(h, [&](auto t) { return eval6_current<decltype(t)>(h, gs::HM_OUT, true); }))
-    return -1;
-  return download_rows(h, h->a_out, h->n, acc4, 4) || download_rows(h, h->j_out, h->n, jerk4, 4) ||
-                 download_rows(h, h->s_out, h->n, snap4, 4)
-             ? -1
-             : 0;
-}
-
-const char* refuse6(const gs_hermite* h) {
-  if (multi(h)) return "hermite order 6 runs on one rank (nranks > 1, --gpus, is refused)";
-  if (h->cfg.dtype == GS_MIXED)
-    return "hermite order 6 has no mixed precision (GS_MIXED, --dtype mixed, is refused)";
-  if (h->block) return "hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)";
-  if (h->nn) return "hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)";
-  return nullptr;
+// The state rows a run carries from step to step beside x, v: (A, J), order 6 (A, J, S, C).
+std::vector<void*> carried_rows(const gs_hermite* h) {
+  if (h->order == 6) return {h->A, h->J, h->S, h->C};
+  return {h->A, h->J};
 }
 
 int start_from_state(gs_hermite* h) {
-  if (h->order == 6) return start6(h);
   if (write_ctrl(h, 0.0, 0, 0.0, std::numeric_limits<double>::infinity(), 0)) return -1;
   if (clear_records(h, true)) return -1;
-  if (by_dtype(h, [&](auto t, auto s) {
-        return eval_current<decltype(t), decltype(s)>(h, gs::HM_INIT, false);
-      }))
-    return -1;
+  if (with_args(h, gs::HM_INIT, false, [&](auto a) { return eval_current(h, a); })) return -1;
   if (multi(h)) {
     // every rank holds all of x, v (uploaded or generated whole), so only the step minima of
     // the other ranks' rows are missing: gathered now (RCCL), or by the group's next call
@@ -820,18 +837,18 @@ int get_state_group(gs_hermite* const* sh, int P, double* pos, double* vel, doub
   return 0;
 }
 
-int derivs_group(gs_hermite* const* sh, int P, double* acc4, double* jerk4, double* q,
-                 int32_t* nn) {
+// snap4: order 6 only (null otherwise).
+int derivs_group(gs_hermite* const* sh, int P, double* acc4, double* jerk4, double* snap4,
+                 double* q, int32_t* nn) {
   gs_hermite* h = sh[0];
   GS_HIP(hipSetDevice(h->cfg.device));
   if (gather(sh, P, {G_X, G_V})) return -1;  // (each rank's corrector moved its own rows only)
   for (int r = 0; r < P; ++r)
-    if (by_dtype(sh[r], [&](auto t, auto s) {
-          return eval_current<decltype(t), decltype(s)>(sh[r], gs::HM_OUT, true);
-        }))
+    if (with_args(sh[r], gs::HM_OUT, true, [&](auto a) { return eval_current(sh[r], a); }))
       return -1;
   if (gather(sh, P, {G_AOUT, G_JOUT})) return -1;
-  if (download_rows(h, h->a_out, h->n, acc4, 4) || download_rows(h, h->j_out, h->n, jerk4, 4))
+  if (download_rows(h, h->a_out, h->n, acc4, 4) || download_rows(h, h->j_out, h->n, jerk4, 4) ||
+      (h->order == 6 && download_rows(h, h->s_out, h->n, snap4, 4)))
     return -1;
   for (int r = 1; r < P; ++r) GS_HIP(hipStreamSynchronize(sh[r]->stream));
   return q || nn ? download_pair(h, h->q_out, h->nn_out, h->n, q, nn) : 0;
@@ -840,7 +857,7 @@ int derivs_group(gs_hermite* const* sh, int P, double* acc4, double* jerk4, doub
 // Milliseconds per evaluate launch at the engine's current predicted rows.
 template <typename T, typename S>
 int time_eval_t(gs_hermite* h, int32_t reps, double* ms) {
-  const gs::HArgs<T, S> a = make_args<T, S>(h, gs::HM_STEP, false);
+  const gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_STEP, false);
   EventTimer timer;
   if (timer.create()) return -1;
   GS_HIP((gs::launch_hermite_eval<T, S>(a, h->ipl, h->groups, false, h->stream)));  // warm
@@ -850,6 +867,43 @@ int time_eval_t(gs_hermite* h, int32_t reps, double* ms) {
   if (timer.stop(h->stream, ms)) return -1;
   *ms /= reps;
   return 0;
+}
+
+// The one implementation behind gs_hermite_set_state and gs_hermite_set_state6. given: the
+// carried rows the caller has, in the order of carried_rows(); with every one of the run's
+// order the run resumes, else its derivatives start afresh.
+int set_state(gs_hermite* h, const double* pos, const double* vel, const double* mass,
+              std::initializer_list<const double*> given, double t, double dt_next,
+              double dt_min) {
+  GS_HIP(hipSetDevice(h->cfg.device));
+  if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
+    return -1;
+  h->mass_host.assign(mass, mass + h->n);
+  // block mode: the run stands at a whole number of steps of dt (a synchronised state)
+  const int64_t macro = h->block ? (int64_t)llround(t / h->cfg.dt) : 0;
+  if (h->block && (double)macro * h->cfg.dt != t) {
+    gs_set_error("hermite block steps: the state's time must be a whole multiple of dt");
+    return -1;
+  }
+  const double inf = std::numeric_limits<double>::infinity();
+  const std::vector<void*> rows = carried_rows(h);
+  bool all = true;
+  for (size_t k = 0; k < rows.size(); ++k) all = all && given.begin()[k];
+  if (!all) {
+    if (start_from_state(h)) return -1;
+    if (h->block && block_start(h, macro)) return -1;
+    gs::HermiteCtrl c;
+    if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
+    return write_ctrl(h, t, 0, 0.0, dt_min > 0.0 ? dt_min : inf, c.overlaps);
+  }
+  // A resumed run: the carried rows as the last step left them, and the step size its criterion
+  // chose.
+  if (clear_records(h, true)) return -1;
+  for (size_t k = 0; k < rows.size(); ++k)
+    if (upload_rows(h, rows[k], given.begin()[k], nullptr, 0.0)) return -1;
+  if (set_wgmin(h, dt_next > 0.0 ? dt_next : inf)) return -1;
+  if (h->block && block_start(h, macro)) return -1;  // (levels afresh until set_block_state)
+  return write_ctrl(h, t, 0, 0.0, dt_min > 0.0 ? dt_min : inf, 0);
 }
 
 }  // namespace
@@ -944,7 +998,7 @@ int gs_hermite_destroy(gs_hermite* h) {
     if (p) (void)hipFree(p);
   free_block(h);
   free_nn(h);
-  free_order6(h);
+  (void)size_order6(h, false);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -999,35 +1053,7 @@ int gs_hermite_set_state(gs_hermite* h, const double* pos, const double* vel, co
                          double dt_min) {
   if (!pos || !vel || !mass) { gs_set_error("hermite set_state: null argument"); return -1; }
   // (order 6 carries a, j, s, c: without the last two the derivatives start afresh)
-  if (h->order == 6)
-    return gs_hermite_set_state6(h, pos, vel, mass, nullptr, nullptr, nullptr, nullptr, t, dt_next,
-                                 dt_min);
-  GS_HIP(hipSetDevice(h->cfg.device));
-  if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
-    return -1;
-  h->mass_host.assign(mass, mass + h->n);
-  // block mode: the run stands at a whole number of steps of dt (a synchronised state)
-  const int64_t macro = h->block ? (int64_t)llround(t / h->cfg.dt) : 0;
-  if (h->block && (double)macro * h->cfg.dt != t) {
-    gs_set_error("hermite block steps: the state's time must be a whole multiple of dt");
-    return -1;
-  }
-  if (!acc || !jerk) {
-    if (start_from_state(h)) return -1;
-    if (h->block && block_start(h, macro)) return -1;
-    gs::HermiteCtrl c;
-    if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
-    return write_ctrl(h, t, 0, 0.0,
-                      dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity(), c.overlaps);
-  }
-  // A resumed run: a, j as the last step left them, and the step size its criterion chose.
-  if (clear_records(h, true)) return -1;
-  if (upload_rows(h, h->A, acc, nullptr, 0.0) || upload_rows(h, h->J, jerk, nullptr, 0.0))
-    return -1;
-  if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
-  if (h->block && block_start(h, macro)) return -1;  // (levels afresh until set_block_state)
-  return write_ctrl(h, t, 0, 0.0,
-                    dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity(), 0);
+  return set_state(h, pos, vel, mass, {acc, jerk, nullptr, nullptr}, t, dt_next, dt_min);
 }
 
 int gs_hermite_get_state(gs_hermite* h, double* pos, double* vel, double* mass, double* acc,
@@ -1041,18 +1067,17 @@ int gs_hermite_derivs(gs_hermite* h, double* acc4, double* jerk4) {
 
 int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, int32_t* nn) {
   if ((q || nn) && !h->nn) { gs_set_error("hermite derivs_nn: collisions are off"); return -1; }
-  if (h->order == 6) return derivs6(h, acc4, jerk4, nullptr);
-  return derivs_group(&h, 1, acc4, jerk4, q, nn);
+  return derivs_group(&h, 1, acc4, jerk4, nullptr, q, nn);
 }
 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
-  if (h->order == 6)
-    return by_dtype6(h, [&](auto t) { return step6_t<decltype(t)>(h, nsteps); });
-  return by_dtype(h, [&](auto t, auto s) {
-    return h->block ? block_step_t<decltype(t), decltype(s)>(h, nsteps)
-                    : step_t<decltype(t), decltype(s)>(&h, 1, nsteps);
-  });
+  if (h->block)
+    return by_dtype(h, [&](auto t, auto s) {
+      return block_step_t<decltype(t), decltype(s)>(h, nsteps);
+    });
+  return with_args(h, gs::HM_STEP, false,
+                   [&](auto a) { return step_t<decltype(a)>(&h, 1, nsteps); });
 }
 
 int gs_hermite_sync(gs_hermite* h) {
@@ -1125,10 +1150,7 @@ int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
     gs_set_error("hermite block steps (block_steps) run on one rank");
     return -1;
   }
-  if (h->order == 6) {
-    gs_set_error("hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)");
-    return -1;
-  }
+  if (h->order == 6) { gs_set_error(refuse6(h, R6_BLOCK)); return -1; }
   if (max_level < 0 || max_level > 40) {
     gs_set_error("hermite block steps: max_level must be in 0..40");
     return -1;
@@ -1267,10 +1289,7 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
     gs_set_error("hermite collisions run on one rank");
     return -1;
   }
-  if (h->order == 6) {
-    gs_set_error("hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)");
-    return -1;
-  }
+  if (h->order == 6) { gs_set_error(refuse6(h, R6_NN)); return -1; }
   if (h->n_pad > (int64_t)std::numeric_limits<int32_t>::max()) {
     gs_set_error("hermite set_collisions: too many bodies for int32 neighbour indices");
     return -1;
@@ -1322,29 +1341,15 @@ int gs_hermite_set_order(gs_hermite* h, int32_t order) {
   }
   GS_HIP(hipSetDevice(h->cfg.device));
   GS_HIP(hipStreamSynchronize(h->stream));
-  if (order == 4) {
-    free_order6(h);
-    h->order = 4;
-    return launch_shape(h);
-  }
-  if (const char* why = refuse6(h)) { gs_set_error(why); return -1; }
-  const int32_t ipl = h->ipl, groups = h->groups;
-  if (launch_shape6(h)) {
-    h->ipl = ipl;
-    h->groups = groups;
+  if (order == 6)
+    if (const char* why = refuse6(h)) { gs_set_error(why); return -1; }
+  const int32_t was = h->order;
+  h->order = order;
+  if (launch_shape(h)) {
+    h->order = was;
     return -1;
   }
-  if (h->order != 6) {
-    const size_t rb = rows_bytes(h);
-    for (void** p : {&h->S, &h->C, &h->AP, &h->s_out}) {
-      GS_HIP(hipMalloc(p, rb));
-      GS_HIP(hipMemsetAsync(*p, 0, rb, h->stream));
-    }
-    GS_HIP(hipMalloc(&h->PS, rb * (size_t)h->n_chunks));
-    GS_HIP(hipStreamSynchronize(h->stream));
-  }
-  h->order = 6;
-  return 0;
+  return order == was ? 0 : size_order6(h, order == 6);
 }
 
 int32_t gs_hermite_get_order(gs_hermite* h) { return h ? h->order : 0; }
@@ -1358,23 +1363,7 @@ int gs_hermite_set_state6(gs_hermite* h, const double* pos, const double* vel, c
                           const double* crackle, double t, double dt_next, double dt_min) {
   if (!h || h->order != 6) { gs_set_error("hermite set_state6: the order is not 6"); return -1; }
   if (!pos || !vel || !mass) { gs_set_error("hermite set_state6: null argument"); return -1; }
-  GS_HIP(hipSetDevice(h->cfg.device));
-  if (upload_rows(h, h->X, pos, mass, h->cfg.G) || upload_rows(h, h->V, vel, nullptr, 0.0))
-    return -1;
-  h->mass_host.assign(mass, mass + h->n);
-  const double dmin = dt_min > 0.0 ? dt_min : std::numeric_limits<double>::infinity();
-  if (!acc || !jerk || !snap || !crackle) {
-    if (start6(h)) return -1;
-    gs::HermiteCtrl c;
-    if (read_ctrl(h, &c)) return -1;  // (also waits for the evaluation)
-    return write_ctrl(h, t, 0, 0.0, dmin, 0);
-  }
-  // A resumed run: a, j, s, c as the last step left them, and the step its criterion chose.
-  if (upload_rows(h, h->A, acc, nullptr, 0.0) || upload_rows(h, h->J, jerk, nullptr, 0.0) ||
-      upload_rows(h, h->S, snap, nullptr, 0.0) || upload_rows(h, h->C, crackle, nullptr, 0.0))
-    return -1;
-  if (set_wgmin(h, dt_next > 0.0 ? dt_next : std::numeric_limits<double>::infinity())) return -1;
-  return write_ctrl(h, t, 0, 0.0, dmin, 0);
+  return set_state(h, pos, vel, mass, {acc, jerk, snap, crackle}, t, dt_next, dt_min);
 }
 
 int gs_hermite_get_carried6(gs_hermite* h, double* snap, double* crackle) {
@@ -1386,7 +1375,7 @@ int gs_hermite_get_carried6(gs_hermite* h, double* snap, double* crackle) {
 
 int gs_hermite_derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4) {
   if (!h || h->order != 6) { gs_set_error("hermite derivs6: the order is not 6"); return -1; }
-  return derivs6(h, acc4, jerk4, snap4);
+  return derivs_group(&h, 1, acc4, jerk4, snap4, nullptr, nullptr);
 }
 
 int gs_hermite_neighbours(gs_hermite* h, double* q, int32_t* nn) {
@@ -1445,9 +1434,8 @@ int gs_hermite_group_step(gs_hermite** shards, int32_t P, int32_t nsteps) {
   for (int r = 0; r < P; ++r)
     if (shards[r]->block) { gs_set_error("hermite group: block steps run on one rank"); return -1; }
   GS_HIP(hipSetDevice(shards[0]->cfg.device));
-  return by_dtype(shards[0], [&](auto t, auto s) {
-    return step_t<decltype(t), decltype(s)>(shards, P, nsteps);
-  });
+  return with_args(shards[0], gs::HM_STEP, false,
+                   [&](auto a) { return step_t<decltype(a)>(shards, P, nsteps); });
 }
 
 int gs_hermite_group_get_state(gs_hermite** shards, int32_t P, double* pos, double* vel,
@@ -1458,7 +1446,7 @@ int gs_hermite_group_get_state(gs_hermite** shards, int32_t P, double* pos, doub
 
 int gs_hermite_group_derivs(gs_hermite** shards, int32_t P, double* acc4, double* jerk4) {
   if (check_group(shards, P)) return -1;
-  return derivs_group(shards, P, acc4, jerk4, nullptr, nullptr);
+  return derivs_group(shards, P, acc4, jerk4, nullptr, nullptr, nullptr);
 }
 
 int gs_hermite_group_time_eval(gs_hermite** shards, int32_t P, int32_t reps, double* ms) {

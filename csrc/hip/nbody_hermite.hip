@@ -41,6 +41,7 @@
 
 #include "gs_common.h"
 #include "gs_hermite.h"
+#include "gs_hermite_scheme.h"
 #include "gs_tile.h"
 
 namespace gs {
@@ -120,8 +121,6 @@ __device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, co
 }
 
 // fp32, two i per lane as 2-vectors: each element sees exactly hinteract()'s arithmetic.
-__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-
 template <bool PHI, bool DS, bool NN>
 __device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, f2 wi,
                                              const V4<float>& q, const V4<float>& p, float cut2,
@@ -344,21 +343,6 @@ __global__ __launch_bounds__(kBlock) void hermite_eval_kernel(typename K::Args a
   }
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-  return v;
-}
-
-// Minimum over the workgroup's threads (valid in thread 0).
-__device__ __forceinline__ double block_min(double v, double* red) {
-  v = wave_min(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < kBlock / 64; ++w) v = fmin(v, red[w]);
-  return v;
-}
-
 // CONTROL (one workgroup): the step the chain is about to take. h = min(dt_max, min_i dt_i)
 // from the last reduce's per-workgroup minima (adaptive) or dt_max (fixed), cut to t_end - t;
 // once t >= t_end, or (collisions "stop") once a step has seen an overlap, the chain's other
@@ -400,6 +384,9 @@ __device__ __forceinline__ void hpredict(const HArgs<T, S>& a, int64_t i, S h, V
   const V4<S> v = reinterpret_cast<const V4<S>*>(a.V)[i];
   const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
   const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
+  // h4_predict (gs_hermite_scheme.h) per component, written out: through the helper, in any of
+  // four shapes, the fp32 block_predict_kernel takes 32 to 34 VGPRs against the 35 of this text
+  // (profiles/hermite_scheme_resources.md), and the kernels' resources are held equal.
   xp.x = x.x + (v.x * h + (ac.x * h2 + jk.x * h3));
   xp.y = x.y + (v.y * h + (ac.y * h2 + jk.y * h3));
   xp.z = x.z + (v.z * h + (ac.z * h2 + jk.z * h3));
@@ -478,10 +465,6 @@ __device__ __forceinline__ void nn_record(const HArgs<T, S>& a, int64_t i, T q, 
   if (q < a.eps2) atomicAdd(overlaps, 1ull);
 }
 
-__device__ __forceinline__ double norm3(double x, double y, double z) {
-  return sqrt(x * x + y * y + z * z);
-}
-
 // The derivatives of one body, summed from its partials (state precision), and (NN) the
 // nearest neighbour folded from them.
 template <typename T, typename S>
@@ -531,15 +514,11 @@ __device__ __forceinline__ void hcorrect(V4<S>* X, V4<S>* V, const V4<S>* A, con
   const V4<S> x = X[i], v = V[i];
   a0 = A[i];
   j0 = J[i];
-  V4<S> v1, x1;
-  v1.x = v.x + ((a0.x + m.ax) * hh + (j0.x - m.jx) * h12);
-  v1.y = v.y + ((a0.y + m.ay) * hh + (j0.y - m.jy) * h12);
-  v1.z = v.z + ((a0.z + m.az) * hh + (j0.z - m.jz) * h12);
-  v1.w = S(0);
-  x1.x = x.x + ((v.x + v1.x) * hh + (a0.x - m.ax) * h12);
-  x1.y = x.y + ((v.y + v1.y) * hh + (a0.y - m.ay) * h12);
-  x1.z = x.z + ((v.z + v1.z) * hh + (a0.z - m.az) * h12);
-  x1.w = x.w;
+  S cx[3], cv[3];  // (a vector's component does not bind to a reference)
+  h4_correct<S>(hh, h12, x.x, v.x, a0.x, j0.x, m.ax, m.jx, cx[0], cv[0]);
+  h4_correct<S>(hh, h12, x.y, v.y, a0.y, j0.y, m.ay, m.jy, cx[1], cv[1]);
+  h4_correct<S>(hh, h12, x.z, v.z, a0.z, j0.z, m.az, m.jz, cx[2], cv[2]);
+  const V4<S> x1 = {cx[0], cx[1], cx[2], x.w}, v1 = {cv[0], cv[1], cv[2], S(0)};
   X[i] = x1;
   V[i] = v1;
 }
@@ -549,20 +528,9 @@ __device__ __forceinline__ void hcorrect(V4<S>* X, V4<S>* V, const V4<S>* A, con
 template <typename T, typename S>
 __device__ __forceinline__ bool aarseth_dt(double hd, double eta, const V4<S>& a0,
                                            const V4<S>& j0, const HSum<T, S>& m, double& dt) {
-  const double ih = 1.0 / hd, ih2 = ih * ih, ih3 = ih2 * ih;
-  const double da[3] = {(double)a0.x - (double)m.ax, (double)a0.y - (double)m.ay,
-                        (double)a0.z - (double)m.az};
-  const double jo[3] = {j0.x, j0.y, j0.z}, jn[3] = {m.jx, m.jy, m.jz};
-  double s2[3], s3[3];
-  for (int d = 0; d < 3; ++d) {
-    const double a2 = (-6.0 * da[d] - hd * (4.0 * jo[d] + 2.0 * jn[d])) * ih2;
-    s3[d] = (12.0 * da[d] + 6.0 * hd * (jo[d] + jn[d])) * ih3;
-    s2[d] = a2 + hd * s3[d];
-  }
-  const double an = norm3(m.ax, m.ay, m.az), jnn = norm3(m.jx, m.jy, m.jz);
-  const double n2 = norm3(s2[0], s2[1], s2[2]), n3 = norm3(s3[0], s3[1], s3[2]);
-  dt = sqrt(eta * (an * n2 + jnn * jnn) / (jnn * n3 + n2 * n2));
-  return jnn > 0.0 && isfinite(dt);
+  const double a0d[3] = {a0.x, a0.y, a0.z}, j0d[3] = {j0.x, j0.y, j0.z};
+  const double a1d[3] = {m.ax, m.ay, m.az}, j1d[3] = {m.jx, m.jy, m.jz};
+  return h4_dt(hd, eta, a0d, j0d, a1d, j1d, dt);
 }
 
 // REDUCE (+ CORRECT): one thread per body adds its chunk partials in chunk order, then
@@ -619,9 +587,9 @@ __global__ __launch_bounds__(kBlock) void hermite_reduce_kernel(typename K::Args
     }
   } else if (a.mode == HM_INIT) {
     if (eta > 0.0) {
-      const double an = norm3(m.ax, m.ay, m.az), jn = norm3(m.jx, m.jy, m.jz);
-      const double d = 0.5 * eta * an / jn;
-      if (jn > 0.0 && isfinite(d)) dti = d;
+      const double ad[3] = {m.ax, m.ay, m.az}, jd[3] = {m.jx, m.jy, m.jz};
+      double d;
+      if (hermite_first_dt(eta, ad, jd, d)) dti = d;
     }
   } else {
     const double hd = a.ctrl->h;
@@ -948,9 +916,9 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64
   if (i < a.n_real) {
     const V4<S> ac = reinterpret_cast<const V4<S>*>(a.A)[i];
     const V4<S> jk = reinterpret_cast<const V4<S>*>(a.J)[i];
-    const double an = norm3(ac.x, ac.y, ac.z), jn = norm3(jk.x, jk.y, jk.z);
-    const double want = 0.5 * b.bc->eta * an / jn;
-    if (jn > 0.0 && isfinite(want))
+    const double ad[3] = {ac.x, ac.y, ac.z}, jd[3] = {jk.x, jk.y, jk.z};
+    double want;
+    if (hermite_first_dt(b.bc->eta, ad, jd, want))
       while (k < b.bc->L && ldexp(b.bc->dt_max, -k) > want) ++k;
     if (k > b.bc->level_max) atomicMax(&b.bc->level_max, k);
   }
@@ -1037,8 +1005,8 @@ static bool nn_args_ok(const HArgs<T, S>& a) {
 // The geometry of an evaluate launch: whole chunks of whole tiles, whole workgroups of ipl rows.
 template <typename T, typename S>
 static bool eval_geometry_ok(const HArgs<T, S>& a, int ipl) {
-  return hermite_ipl_ok(sizeof(T) == 8, ipl) && a.n_chunks >= 1 && a.n_pad % (kBlock * ipl) == 0 &&
-         a.chunk % Tile<T>::kBodies == 0 && (int64_t)a.n_chunks * a.chunk == a.n_pad &&
+  return hermite_ipl_ok(sizeof(T) == 8, ipl) &&
+         chunk_geometry_ok<T>(a.n_pad, a.chunk, a.n_chunks, ipl) &&
          (sizeof(S) == sizeof(T) || a.XL) && (!a.nn || nn_args_ok(a));
 }
 

@@ -1,4 +1,4 @@
-// gfx950 kernels of the 6th-order Hermite scheme (Nitadori & Makino 2008; gs_hermite6.h).
+// gfx950 kernels of the 6th-order Hermite scheme (Nitadori & Makino 2008; gs_hermite_scheme.h).
 //
 // The hot kernel evaluates, for every body i at the predicted state (xp, vp, ap),
 //     a_i = sum_j A_ij,   A_ij = mu_j d r^-3
@@ -28,14 +28,18 @@
 #include <type_traits>
 
 #include "gs_common.h"
-#include "gs_hermite6.h"
+#include "gs_hermite.h"
+#include "gs_hermite_scheme.h"
 #include "gs_tile.h"
 
 namespace gs {
 
-__device__ __forceinline__ float fmav(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fmav(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ f2 fmav(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+// The fused multiply-add of the pair term's element type: fma_ (a scalar) or fma2 (a pair).
+template <typename V>
+__device__ __forceinline__ V fmav(V a, V b, V c) {
+  if constexpr (std::is_same<V, f2>::value) return fma2(a, b, c);
+  else return fma_(a, b, c);
+}
 
 // 1 / sqrt(r2) where the pair law keeps the pair, else 0.
 __device__ __forceinline__ float inv_cut(float r2, float cut2) {
@@ -235,11 +239,6 @@ __global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(H6Args<T> a) {
   reinterpret_cast<V4<T>*>(a.AP)[i] = ap;
 }
 
-__device__ __forceinline__ double wave_min6(double v) {
-  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-  return v;
-}
-
 // REDUCE (+ CORRECT): one thread per body adds its chunk partials in chunk order, then HM_STEP
 // applies the corrector, stores a1, j1, s1, c1 and the body's wish for the next step, HM_INIT
 // starts a run (a, j, s <- sums, c <- 0; the first step (eta / 2) |a| / |j|), HM_OUT returns the
@@ -288,10 +287,9 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
   } else if (a.mode == HM_INIT) {
     A[i] = oa; J[i] = oj; S[i] = os; C[i] = z;
     if (eta > 0.0) {
-      const double an = h6_norm3(m[0][0], m[0][1], m[0][2]);
-      const double jn = h6_norm3(m[1][0], m[1][1], m[1][2]);
-      const double d = 0.5 * eta * an / jn;
-      if (jn > 0.0 && isfinite(d)) dti = d;
+      const double ad[3] = {m[0][0], m[0][1], m[0][2]}, jd[3] = {m[1][0], m[1][1], m[1][2]};
+      double d;
+      if (hermite_first_dt(eta, ad, jd, d)) dti = d;
     }
   } else {
     const double hd = a.ctrl->h;
@@ -315,13 +313,8 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
       if (h6_dt(eta, a1, j1, s1, c1, p1, a5, d)) dti = d;
     }
   }
-  dti = wave_min6(dti);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dti;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kBlock / 64; ++w) dti = fmin(dti, red[w]);
-    a.wgmin[blockIdx.x] = dti;
-  }
+  dti = block_min(dti, red);
+  if (threadIdx.x == 0) a.wgmin[blockIdx.x] = dti;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -331,9 +324,9 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
 bool hermite6_ipl_ok(int fp64, int ipl) { return ipl == 1 || (ipl == 2 && !fp64); }
 
 template <typename T>
-static bool geometry6_ok(const H6Args<T>& a) {
-  return a.n_chunks >= 1 && a.n_pad % kBlock == 0 && a.chunk % Tile<T>::kBodies == 0 &&
-         (int64_t)a.n_chunks * a.chunk == a.n_pad && a.n_real >= 1 && a.n_real <= a.n_pad;
+static bool args6_ok(const H6Args<T>& a, int ipl = 1) {
+  return chunk_geometry_ok<T>(a.n_pad, a.chunk, a.n_chunks, ipl) && a.n_real >= 1 &&
+         a.n_real <= a.n_pad;
 }
 
 template <typename T, bool PHI, int IPL>
@@ -345,8 +338,8 @@ static hipError_t eval6_go(const H6Args<T>& a, dim3 grid, bool gated, hipStream_
 template <typename T>
 hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool gated,
                                 hipStream_t s) {
-  if (!geometry6_ok(a) || !hermite6_ipl_ok(sizeof(T) == 8, ipl) || a.n_pad % (kBlock * ipl) ||
-      (gated && !a.ctrl) || !a.XP || !a.VP || !a.AP || !a.PA || !a.PJ || !a.PS)
+  if (!hermite6_ipl_ok(sizeof(T) == 8, ipl) || !args6_ok(a, ipl) || (gated && !a.ctrl) || !a.XP ||
+      !a.VP || !a.AP || !a.PA || !a.PJ || !a.PS)
     return hipErrorInvalidValue;
   const int g = groups < 1 ? 1 : groups > a.n_chunks ? a.n_chunks : groups;
   const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)g);
@@ -359,7 +352,7 @@ hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool ga
 
 template <typename T>
 hipError_t launch_hermite6_predict(const H6Args<T>& a, hipStream_t s) {
-  if (!geometry6_ok(a) || !a.ctrl) return hipErrorInvalidValue;
+  if (!args6_ok(a) || !a.ctrl) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hermite6_predict_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
                      0, s, a);
   return hipGetLastError();
@@ -367,7 +360,7 @@ hipError_t launch_hermite6_predict(const H6Args<T>& a, hipStream_t s) {
 
 template <typename T>
 hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s) {
-  if (!geometry6_ok(a) || !a.ctrl || !a.wgmin) return hipErrorInvalidValue;
+  if (!args6_ok(a) || !a.ctrl || !a.wgmin) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hermite6_reduce_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
                      0, s, a);
   return hipGetLastError();

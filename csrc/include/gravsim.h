@@ -458,7 +458,7 @@ int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, 
 int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                                 double* acc4, double* jerk4, double* q, int32_t* nn);
 
-// 6th-order scheme (Nitadori & Makino 2008; gs_hermite6.h, nbody_hermite6.hip): the state also
+// 6th-order scheme (Nitadori & Makino 2008; gs_hermite_scheme.h, nbody_hermite6.hip): the state also
 // carries the snap s = a'' and the crackle c = a''', and the one force pass of a step returns
 // a, j and s at the predicted (x, v, a). One shared step (fixed, or adaptive with
 //   dt_i = eta ((|a||s| + |j|^2) / (|c||a^(5)| + |a^(4)|^2))^(1/6),

@@ -1,5 +1,6 @@
-// Internal interface between the Hermite kernels (nbody_hermite.hip) and their runtime
-// (hermite.hip). Not part of the C API (gravsim.h).
+// Internal interface between the Hermite kernels (nbody_hermite.hip, nbody_hermite6.hip) and
+// their runtime (hermite.hip). The schemes' arithmetic is in gs_hermite_scheme.h. Not part of
+// the C API (gravsim.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -148,5 +149,39 @@ int32_t hermite_narrow_slice(int64_t n_pad);
 hipError_t launch_hermite_split(const HArgs<float, double>& a, hipStream_t s);
 // ipl values the evaluate kernel is compiled for (fp32 pairs: 1, 2, 4; fp64: 1, 2).
 bool hermite_ipl_ok(int fp64, int ipl);
+
+// ---- 6th order (nbody_hermite6.hip) ---------------------------------------------------------
+// Arrays hold 4 components per body over n_pad rows (ghost rows zero), all of the run's one
+// type T (order 6 has no mixed precision): X = (x, y, z, mu), V, A, J, S, C the state; XP, VP,
+// AP = (ap, 0) the predicted rows the evaluate kernel reads; PA = (a, sum mu / r), PJ, PS the
+// per-chunk partial sums [n_chunks][n_pad]. mode is HM_*: HM_STEP corrects and forms c1 and the
+// per-workgroup dt minima, HM_INIT stores a, j, s (c <- 0) and the minima of the first step,
+// HM_OUT writes (a, phi), j, s to the outputs. The control kernel is the 4th-order chain's.
+template <typename T>
+struct H6Args {
+  T *X, *V, *A, *J, *S, *C;
+  T *XP, *VP, *AP;
+  T *PA, *PJ, *PS;
+  T *a_out, *j_out, *s_out;
+  HermiteCtrl* ctrl;
+  double* wgmin;  // [n_pad / 256]
+  int64_t n_real, n_pad, chunk;
+  int32_t n_chunks;
+  int32_t mode;
+  int32_t phi;
+  T cut2, eps2;
+};
+
+// ipl values the order-6 evaluate kernel is compiled for (fp32: 1, 2; fp64: 1).
+bool hermite6_ipl_ok(int fp64, int ipl);
+template <typename T>
+hipError_t launch_hermite6_predict(const H6Args<T>& a, hipStream_t s);
+// a, j, s (and phi) of every body at (XP, VP, AP) into PA / PJ / PS: grid (n_pad / (256 ipl),
+// groups); always, or (gated) only while ctrl->active.
+template <typename T>
+hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool gated,
+                                hipStream_t s);
+template <typename T>
+hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s);
 
 }  // namespace gs

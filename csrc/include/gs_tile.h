@@ -1,6 +1,7 @@
 // Device helpers shared by the one-sided force kernels (nbody_kernels.hip) and the Hermite
-// acceleration+jerk kernel (nbody_hermite.hip): 4-vectors, the reciprocal square root, and the
-// LDS-DMA tile fill.
+// kernels of both orders (nbody_hermite.hip, nbody_hermite6.hip): 4-vectors, the reciprocal
+// square root, the fused multiply-adds, the workgroup minimum, the LDS-DMA tile fill and the
+// geometry an evaluate launch must have.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,12 +35,36 @@ __device__ __forceinline__ double fma_(double a, double b, double c) { return __
 
 // Two fp32 values per lane as one 2-vector (v_pk_* operands).
 using f2 = float __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+
+__device__ __forceinline__ double wave_min(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
+  return v;
+}
+
+// Minimum over the workgroup's threads (valid in thread 0).
+__device__ __forceinline__ double block_min(double v, double* red) {
+  v = wave_min(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kBlock / 64; ++w) v = fmin(v, red[w]);
+  return v;
+}
 
 // LDS tile geometry: kTileBytes per tile buffer (4 KiB = 256 fp32 / 128 fp64 bodies),
 // double-buffered. Each wave-instruction of the fill moves one 1-KiB piece.
 constexpr int kTileBytes = 4096;
 static_assert(kTileBytes % 1024 == 0, "tile must be whole 1 KiB wave pieces");
 template <typename T> struct Tile { static constexpr int kBodies = kTileBytes / sizeof(V4<T>); };
+
+// The geometry of a chunked evaluate launch over n_pad rows with ipl i-bodies per lane: whole
+// chunks of whole tiles, whole workgroups of ipl rows per lane.
+template <typename T>
+inline bool chunk_geometry_ok(int64_t n_pad, int64_t chunk, int32_t n_chunks, int ipl) {
+  return n_chunks >= 1 && n_pad % (kBlock * ipl) == 0 && chunk % Tile<T>::kBodies == 0 &&
+         (int64_t)n_chunks * chunk == n_pad;
+}
 
 // Issue the LDS-DMA fill of one tile: per round each of the 4 waves moves one 1-KiB piece
 // (64 lanes x 16 B); the LDS destination is the wave-uniform base + lane*16.

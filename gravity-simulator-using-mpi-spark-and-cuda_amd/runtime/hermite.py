@@ -1,4 +1,4 @@
-"""Engines of the 4th-order Hermite integrator (Makino & Aarseth 1992).
+"""Engines of the Hermite integrators: 4th order (Makino & Aarseth 1992) and 6th order.
 
 The same interface as the engines of runtime/engines.py (load / init_ics / step / sync / state /
 accel / nonfinite / steps_done / close) plus status(): the integrator carries x, v, a, j, t and
@@ -79,6 +79,11 @@ _PI32 = ctypes.POINTER(ctypes.c_int32)
 
 def _i32ptr(a):
     return a.ctypes.data_as(_PI32)
+
+
+def _reported(dt: Optional[float]) -> float:
+    """A step size a status() reported, as the native set_state takes it (-1: none)."""
+    return float(dt) if dt is not None and math.isfinite(dt) else -1.0
 
 
 def _require_one_rank(nranks: int) -> None:
@@ -218,30 +223,19 @@ class HermiteHipEngine:
         pos = np.ascontiguousarray(b.pos, dtype=np.float64)
         vel = np.ascontiguousarray(b.vel, dtype=np.float64)
         mass = np.ascontiguousarray(b.mass, dtype=np.float64)
-        if self.order == 6:
-            four = [acc, jerk, snap, crackle]
-            have = all(y is not None for y in four)
-            four = [np.ascontiguousarray(y, dtype=np.float64) if have else None for y in four]
-            _native.check(self.lib, self.lib.gs_hermite_set_state6(
-                self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
-                *[_native.dptr(y) if have else None for y in four], float(t),
-                float(dt_next) if dt_next is not None and math.isfinite(dt_next) else -1.0,
-                float(dt_min) if dt_min is not None and math.isfinite(dt_min) else -1.0),
-                "set_state6")
-            return
-        have = acc is not None and jerk is not None
-        a = np.ascontiguousarray(acc, dtype=np.float64) if have else None
-        j = np.ascontiguousarray(jerk, dtype=np.float64) if have else None
+        # the carried rows of the run's order: it continues only with every one of them
+        rows = [acc, jerk, snap, crackle] if self.order == 6 else [acc, jerk]
+        have = all(y is not None for y in rows)
+        rows = [np.ascontiguousarray(y, dtype=np.float64) if have else None for y in rows]
         if self.collisions:
             self.radius = np.ascontiguousarray(b.radii(self.cfg.body_density), dtype=np.float64)
             _native.check(self.lib, self.lib.gs_hermite_set_radii(
                 self._h, _native.dptr(self.radius)), "set_radii")
-        _native.check(self.lib, self.lib.gs_hermite_set_state(
+        name = "set_state6" if self.order == 6 else "set_state"
+        _native.check(self.lib, getattr(self.lib, "gs_hermite_" + name)(
             self._h, _native.dptr(pos), _native.dptr(vel), _native.dptr(mass),
-            _native.dptr(a) if have else None, _native.dptr(j) if have else None, float(t),
-            float(dt_next) if dt_next is not None and math.isfinite(dt_next) else -1.0,
-            float(dt_min) if dt_min is not None and math.isfinite(dt_min) else -1.0),
-            "set_state")
+            *[_native.dptr(y) if have else None for y in rows], float(t),
+            _reported(dt_next), _reported(dt_min)), name)
         if self.block and (levels is not None or body_times is not None):
             lev = None if levels is None else np.ascontiguousarray(levels, dtype=np.int32)
             tb = None if body_times is None else np.ascontiguousarray(body_times, dtype=np.int64)
@@ -504,17 +498,21 @@ class HermiteCpuEngine:
         self.layout: Layout = make_layout(cfg.n, 0, 1, cfg.chunk)
         self.np_dtype = np.float32 if cfg.dtype == "fp32" else np.float64  # (mixed: fp64 arrays)
         n, T = cfg.n, self.np_dtype
-        self.X, self.V = np.zeros((n, 4), T), np.zeros((n, 4), T)
-        self.A, self.J = np.zeros((n, 4), T), np.zeros((n, 4), T)
-        self._scratch = np.zeros((4 * n, 4), T)
-        self.mass = np.zeros(n)
-        self._step, self._ptr = _native.cpu_entry(self.lib, "hermite_step", cfg.dtype)
         self.order = int(cfg.hermite_order)
-        if self.order == 6:  # (the refusals of SimConfig.validate for a bare engine)
+        six = self.order == 6
+        if six:  # (the refusals of SimConfig.validate for a bare engine)
             cfg.validate()
-            self.S, self.C = np.zeros((n, 4), T), np.zeros((n, 4), T)
-            self._scratch = np.zeros((6 * n, 4), T)
-            self._step6 = _native.cpu_entry(self.lib, "hermite6_step", cfg.dtype)[0]
+        self.X, self.V = np.zeros((n, 4), T), np.zeros((n, 4), T)
+        # the rows the integrator carries beside x, v: (A, J), order 6 (A, J, S, C); the native
+        # step takes them in this order and a scratch of the predicted and the new rows
+        self._rows = [np.zeros((n, 4), T) for _ in range(4 if six else 2)]
+        self.A, self.J = self._rows[:2]
+        self._scratch = np.zeros(((6 if six else 4) * n, 4), T)
+        self.mass = np.zeros(n)
+        self._step, self._ptr = _native.cpu_entry(
+            self.lib, "hermite6_step" if six else "hermite_step", cfg.dtype)
+        if six:
+            self.S, self.C = self._rows[2:]
             self._ajs = _native.cpu_entry(self.lib, "accjerksnap", cfg.dtype)[0]
         self._accjerk, self._accjerk_idx, self._first_dt, self._nn, self._nn_idx = (
             _native.cpu_entry(self.lib, stem, cfg.dtype)[0]
@@ -697,27 +695,25 @@ class HermiteCpuEngine:
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
              dt_next: Optional[float] = None, dt_min: Optional[float] = None,
              levels=None, body_times=None, snap=None, crackle=None) -> None:
-        if self.order == 6:
-            return self._load6(b, acc, jerk, snap, crackle, t, dt_next, dt_min)
         self.X[:, :3] = b.pos
         self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
         self.V[:] = 0
         self.V[:, :3] = b.vel
         self.mass = np.array(b.mass, dtype=np.float64)
-        self.A[:] = 0
-        self.J[:] = 0
+        for y in self._rows:
+            y[:] = 0
         self._clear_records()
         if self.collisions:
             self.radius = np.array(b.radii(self.cfg.body_density), dtype=np.float64)
             self._R = self.radius.astype(self.np_dtype)
-        if acc is not None and jerk is not None:
-            self.A[:, :3] = acc
-            self.J[:, :3] = jerk
+        given = [acc, jerk, snap, crackle][: len(self._rows)]
+        if all(y is not None for y in given):  # a run continues with every carried row
+            for y, g in zip(self._rows, given):
+                y[:, :3] = g
             self._next = math.inf if dt_next is None else float(dt_next)
-        else:
-            a4, j4 = self._derivs()
-            self.A[:, :3] = a4[:, :3]
-            self.J[:, :3] = j4[:, :3]
+        else:  # (order 6: a, j, s of the state; the crackle starts at 0)
+            for y, d in zip(self._rows, self._derivs6() if self.order == 6 else self._derivs()):
+                y[:, :3] = d[:, :3]
             if self.collisions:
                 self._see(self.X)
             self._next = math.inf
@@ -728,27 +724,6 @@ class HermiteCpuEngine:
         self.dt_min = math.inf if dt_min is None else float(dt_min)
         if self.block:
             self._block_start(float(t), levels, body_times)
-
-    def _load6(self, b, acc, jerk, snap, crackle, t, dt_next, dt_min) -> None:
-        self.X[:, :3] = b.pos
-        self.X[:, 3] = self.cfg.G * np.asarray(b.mass, dtype=np.float64)
-        self.V[:] = 0
-        self.V[:, :3] = b.vel
-        self.mass = np.array(b.mass, dtype=np.float64)
-        for y in (self.A, self.J, self.S, self.C):
-            y[:] = 0
-        if all(y is not None for y in (acc, jerk, snap, crackle)):
-            self.A[:, :3], self.J[:, :3], self.S[:, :3], self.C[:, :3] = acc, jerk, snap, crackle
-            self._next = math.inf if dt_next is None else float(dt_next)
-        else:
-            a4, j4, s4 = self._derivs6()
-            self.A[:, :3], self.J[:, :3], self.S[:, :3] = a4[:, :3], j4[:, :3], s4[:, :3]
-            self._next = math.inf
-            if self.cfg.eta > 0:
-                self._next = float(self._first_dt(self._ptr(self.A), self._ptr(self.J),
-                                                  self.cfg.n, float(self.cfg.eta)))
-        self.t, self.dt_last, self.k = float(t), 0.0, 0
-        self.dt_min = math.inf if dt_min is None else float(dt_min)
 
     def step(self, n: int) -> None:
         cfg = self.cfg
@@ -773,16 +748,9 @@ class HermiteCpuEngine:
             cut = cfg.t_end is not None and h >= cfg.t_end - self.t
             if cut:
                 h = cfg.t_end - self.t
-            if self.order == 6:
-                rc = self._step6(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
-                                 self._ptr(self.J), self._ptr(self.S), self._ptr(self.C),
-                                 self._ptr(self._scratch), cfg.n, self.layout.chunk, h,
-                                 self._cut2, self._eps2, float(cfg.eta), ctypes.byref(out))
-            else:
-                rc = self._step(self._ptr(self.X), self._ptr(self.V), self._ptr(self.A),
-                                self._ptr(self.J), self._ptr(self._scratch), cfg.n,
-                                self.layout.chunk, h, self._cut2, self._eps2, float(cfg.eta),
-                                ctypes.byref(out))
+            rc = self._step(self._ptr(self.X), self._ptr(self.V), *map(self._ptr, self._rows),
+                            self._ptr(self._scratch), cfg.n, self.layout.chunk, h, self._cut2,
+                            self._eps2, float(cfg.eta), ctypes.byref(out))
             _native.check(self.lib, rc, "cpu hermite step")
             if self.collisions:  # (the step leaves its predicted rows at the scratch's head)
                 self._see(self._scratch[: cfg.n])
@@ -814,8 +782,7 @@ class HermiteCpuEngine:
                        self.mass.copy(), self.radius.copy() if self.collisions else None)
 
     def carried(self):
-        rows = (self.A, self.J) + ((self.S, self.C) if self.order == 6 else ())
-        return tuple(y[:, :3].astype(np.float64) for y in rows)
+        return tuple(y[:, :3].astype(np.float64) for y in self._rows)
 
     def derivs(self, active=None, path: Optional[str] = None):
         if self.order == 6:

@@ -304,3 +304,38 @@ def test_native_refusals_name_the_option(hip):
     with pytest.raises(ValueError, match="--gpus"):
         HermiteHipEngine(SimConfig(n=2048, device="gpu", integrator="hermite", hermite_order=6),
                          0, 2)
+
+
+# ---- order 6 switched on and off again: the order-4 run is untouched ----------------------
+@pytest.mark.parametrize("dtype", ["fp32", "fp64"])
+def test_order_6_then_4_is_the_fresh_order_4_run(hip, dtype):
+    """gs_hermite_set_order(6) then (4) on an order-4 engine leaves the launch shape and, after
+    load() and 3 adaptive steps, every bit of state(), carried() and status() as a fresh order-4
+    engine has them: the path through the launch shape and the frees of the order's arrays."""
+    n = 2049
+    b = ic.solar_random(n, seed=7 + n)
+
+    def run(switch):
+        eng = _engine(n, dtype, hermite_order=4, dt=3600.0, eta=0.05)
+        try:
+            if switch:
+                for order in (6, 4):
+                    assert hip.gs_hermite_set_order(eng._h, order) == 0, hip.gs_last_error()
+                    assert hip.gs_hermite_get_order(eng._h) == order
+            L = _native.GsLayout()
+            assert hip.gs_hermite_layout(eng._h, ctypes.byref(L)) == 0
+            eng.load(b)
+            eng.step(3)
+            eng.sync()
+            s = eng.state()
+            return (s.pos, s.vel, s.mass) + tuple(eng.carried()), eng.status(), \
+                (L.as_dict()["ipl"], L.as_dict()["split_groups"])
+        finally:
+            eng.close()
+
+    rows_a, st_a, shape_a = run(False)
+    rows_b, st_b, shape_b = run(True)
+    assert shape_a == shape_b
+    assert st_a == st_b and st_a.steps == 3
+    for x, y in zip(rows_a, rows_b):
+        assert x.tobytes() == y.tobytes()
