@@ -79,84 +79,61 @@ __device__ __forceinline__ V hsep(V qh, V xh, V ql, V xl) {
 // false) or the body itself (with softening the law does not zero the self pair) takes no part.
 // The operands of a flag that is off (DS: l, lxi, lyi, lzi; NN: ri, jreal, jg, self, bq, bn) are
 // never read: every caller passes what it has, and the compiler drops them.
-template <bool PHI, bool DS, bool NN, typename T>
-__device__ __forceinline__ void hinteract(T xi, T yi, T zi, T ui, T vi, T wi, const V4<T>& q,
-                                          const V4<T>& p, T cut2, T eps2, T& ax, T& ay, T& az,
-                                          T& ph, T& jx, T& jy, T& jz, const V4<T>& l, T lxi,
-                                          T lyi, T lzi, T ri, bool jreal, int32_t jg,
-                                          int32_t self, T* bq, int32_t* bn) {
-  const T dx = hsep<DS>(q.x, xi, l.x, lxi), dy = hsep<DS>(q.y, yi, l.y, lyi),
-          dz = hsep<DS>(q.z, zi, l.z, lzi);
-  const T wx = p.x - ui, wy = p.y - vi, wz = p.z - wi;
-  const T r2 = fma_(dz, dz, fma_(dy, dy, fma_(dx, dx, eps2)));
-  const bool ok = r2 >= cut2;
-  T inv;
-  if constexpr (sizeof(T) == 8) {
-    // Branch-free (as the one-sided force kernel): the refinement runs on 1 below the cutoff.
-    inv = rsqrt_dev(ok ? r2 : T(1));
-    inv = ok ? inv : T(0);
-  } else {
-    inv = ok ? rsqrt_dev(r2) : T(0);
-  }
-  const T inv2 = inv * inv;
-  const T mi = q.w * inv;
-  const T s = mi * inv2;
-  const T dw = fma_(dz, wz, fma_(dy, wy, dx * wx));
-  const T al = dw * (T(3) * inv2);
-  ax = fma_(s, dx, ax);
-  ay = fma_(s, dy, ay);
-  az = fma_(s, dz, az);
-  jx = fma_(s, fma_(-al, dx, wx), jx);
-  jy = fma_(s, fma_(-al, dy, wy), jy);
-  jz = fma_(s, fma_(-al, dz, wz), jz);
+// Written once over the element type V (gs_tile.h): T for one i-body, f2 for two (fp32: every
+// operation but the v_rsq_f32 and the selects is then a v_pk_*); bq, bn and self point at the
+// entries of the element's first body.
+template <bool PHI, bool DS, bool NN, typename V, typename T>
+__device__ __forceinline__ void hinteract(V xi, V yi, V zi, V ui, V vi, V wi, const V4<T>& q,
+                                          const V4<T>& p, T cut2, T eps2, V& ax, V& ay, V& az,
+                                          V& ph, V& jx, V& jy, V& jz, const V4<T>& l, V lxi,
+                                          V lyi, V lzi, V ri, bool jreal, int32_t jg,
+                                          const int32_t* self, T* bq, int32_t* bn) {
+  const V dx = hsep<DS>(V(q.x), xi, V(l.x), lxi), dy = hsep<DS>(V(q.y), yi, V(l.y), lyi),
+          dz = hsep<DS>(V(q.z), zi, V(l.z), lzi);
+  const V wx = V(p.x) - ui, wy = V(p.y) - vi, wz = V(p.z) - wi;
+  const V r2 = fmav(dz, dz, fmav(dy, dy, fmav(dx, dx, V(eps2))));
+  const V inv = inv_cut(r2, cut2);
+  const V inv2 = inv * inv;
+  const V mi = V(q.w) * inv;
+  const V s = mi * inv2;
+  const V dw = fmav(dz, wz, fmav(dy, wy, dx * wx));
+  const V al = dw * (V(T(3)) * inv2);
+  ax = fmav(s, dx, ax);
+  ay = fmav(s, dy, ay);
+  az = fmav(s, dz, az);
+  jx = fmav(s, fmav(-al, dx, wx), jx);
+  jy = fmav(s, fmav(-al, dy, wy), jy);
+  jz = fmav(s, fmav(-al, dz, wz), jz);
   if constexpr (PHI) ph += mi;
   if constexpr (NN) {
-    const T sr = p.w + ri;
-    const T qv = fma_(-sr, sr, r2);
-    const T qe = (ok && jreal && jg != self) ? qv : T(INFINITY);
-    const bool lt = qe < *bq;
-    *bq = lt ? qe : *bq;
-    *bn = lt ? jg : *bn;
-  }
-}
-
-// fp32, two i per lane as 2-vectors: each element sees exactly hinteract()'s arithmetic.
-template <bool PHI, bool DS, bool NN>
-__device__ __forceinline__ void hinteract_pk(f2 xi, f2 yi, f2 zi, f2 ui, f2 vi, f2 wi,
-                                             const V4<float>& q, const V4<float>& p, float cut2,
-                                             float eps2, f2& ax, f2& ay, f2& az, f2& ph, f2& jx,
-                                             f2& jy, f2& jz, const V4<float>& l, f2 lxi, f2 lyi,
-                                             f2 lzi, f2 ri, bool jreal, int32_t jg,
-                                             const int32_t* self, float* bq, int32_t* bn) {
-  const f2 dx = hsep<DS>(f2(q.x), xi, f2(l.x), lxi), dy = hsep<DS>(f2(q.y), yi, f2(l.y), lyi),
-           dz = hsep<DS>(f2(q.z), zi, f2(l.z), lzi);
-  const f2 wx = f2(p.x) - ui, wy = f2(p.y) - vi, wz = f2(p.z) - wi;
-  const f2 r2 = fma2(dz, dz, fma2(dy, dy, fma2(dx, dx, f2(eps2))));
-  f2 inv;
-  inv.x = r2.x >= cut2 ? rsqrt_dev(r2.x) : 0.0f;
-  inv.y = r2.y >= cut2 ? rsqrt_dev(r2.y) : 0.0f;
-  const f2 inv2 = inv * inv;
-  const f2 mi = f2(q.w) * inv;
-  const f2 s = mi * inv2;
-  const f2 dw = fma2(dz, wz, fma2(dy, wy, dx * wx));
-  const f2 al = dw * (f2(3.0f) * inv2);
-  ax = fma2(s, dx, ax);
-  ay = fma2(s, dy, ay);
-  az = fma2(s, dz, az);
-  jx = fma2(s, fma2(-al, dx, wx), jx);
-  jy = fma2(s, fma2(-al, dy, wy), jy);
-  jz = fma2(s, fma2(-al, dz, wz), jz);
-  if constexpr (PHI) ph += mi;
-  if constexpr (NN) {
-    const f2 sr = f2(p.w) + ri;
-    const f2 qv = fma2(-sr, sr, r2);
-    const float q0 = (r2.x >= cut2 && jreal && jg != self[0]) ? qv.x : INFINITY;
-    const float q1 = (r2.y >= cut2 && jreal && jg != self[1]) ? qv.y : INFINITY;
-    const bool l0 = q0 < bq[0], l1 = q1 < bq[1];
-    bq[0] = l0 ? q0 : bq[0];
-    bn[0] = l0 ? jg : bn[0];
-    bq[1] = l1 ? q1 : bq[1];
-    bn[1] = l1 ? jg : bn[1];
+    const V sr = V(p.w) + ri;
+    const V qv = fmav(-sr, sr, r2);
+    // (Written per element type, and the scalar form through one-element loops: one form for
+    // both, in five shapes, moved the VGPRs of one or two NN kernels by one; these two hold every
+    // kernel at the parent's figures, profiles/tile_sweep_resources.md.)
+    if constexpr (std::is_same<V, f2>::value) {
+      const float q0 = (r2.x >= cut2 && jreal && jg != self[0]) ? qv.x : INFINITY;
+      const float q1 = (r2.y >= cut2 && jreal && jg != self[1]) ? qv.y : INFINITY;
+      const bool l0 = q0 < bq[0], l1 = q1 < bq[1];
+      bq[0] = l0 ? q0 : bq[0];
+      bn[0] = l0 ? jg : bn[0];
+      bq[1] = l1 ? q1 : bq[1];
+      bn[1] = l1 ? jg : bn[1];
+    } else {
+      constexpr int E = 1;
+      T qe[E];
+      bool lt[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e)
+        qe[e] = (vget(r2, e) >= cut2 && jreal && jg != self[e]) ? vget(qv, e) : T(INFINITY);
+#pragma unroll
+      for (int e = 0; e < E; ++e) lt[e] = qe[e] < bq[e];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        bq[e] = lt[e] ? qe[e] : bq[e];
+        bn[e] = lt[e] ? jg : bn[e];
+      }
+    }
   }
 }
 
@@ -224,7 +201,7 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const HLo<T, IP
       f2 ax = {s.ax[k], s.ax[k + 1]}, ay = {s.ay[k], s.ay[k + 1]}, az = {s.az[k], s.az[k + 1]};
       f2 jx = {s.jx[k], s.jx[k + 1]}, jy = {s.jy[k], s.jy[k + 1]}, jz = {s.jz[k], s.jz[k + 1]};
       f2 ph = {s.ph[k], s.ph[k + 1]};
-      hinteract_pk<PHI, DS, NN>(
+      hinteract<PHI, DS, NN>(
           f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
           f2{s.u[k], s.u[k + 1]}, f2{s.v[k], s.v[k + 1]}, f2{s.w[k], s.w[k + 1]}, q, p, cut2,
           eps2, ax, ay, az, ph, jx, jy, jz, l, f2{lo.x[k], lo.x[k + 1]},
@@ -243,7 +220,7 @@ __device__ __forceinline__ void hinteract_all(HState<T, IPL>& s, const HLo<T, IP
     for (int k = 0; k < IPL; ++k)
       hinteract<PHI, DS, NN>(s.x[k], s.y[k], s.z[k], s.u[k], s.v[k], s.w[k], q, p, cut2, eps2,
                              s.ax[k], s.ay[k], s.az[k], s.ph[k], s.jx[k], s.jy[k], s.jz[k], l,
-                             lo.x[k], lo.y[k], lo.z[k], nr.r[k], jreal, jg, nr.self[k], &nr.q[k],
+                             lo.x[k], lo.y[k], lo.z[k], nr.r[k], jreal, jg, &nr.self[k], &nr.q[k],
                              &nr.n[k]);
   }
 }
@@ -740,7 +717,7 @@ __global__ __launch_bounds__(kBlock) void block_compact_kernel(HArgs<T, S> a) {
 // j order; the lanes are folded by a fixed tree (shuffle-down 32..1 in the wave, then the
 // four waves in order through LDS) and one partial per (slice, slot) is stored. Slice length and
 // tree depend on n_pad only, so a body's bits depend neither on the other active bodies nor on
-// its slot. fp32 runs two i-bodies as 2-vectors (hinteract_pk).
+// its slot. fp32 runs two i-bodies as 2-vectors (hinteract over f2).
 // NN: a lane folds its rows with a strict less in j order; the lanes' and the waves' (q, j) fold
 // lexicographically (the smaller q, on a tie the lower j); the partial is (NJ[s][slot].w,
 // NNI[s][slot]).

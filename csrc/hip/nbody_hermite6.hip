@@ -34,30 +34,6 @@
 
 namespace gs {
 
-// The fused multiply-add of the pair term's element type: fma_ (a scalar) or fma2 (a pair).
-template <typename V>
-__device__ __forceinline__ V fmav(V a, V b, V c) {
-  if constexpr (std::is_same<V, f2>::value) return fma2(a, b, c);
-  else return fma_(a, b, c);
-}
-
-// 1 / sqrt(r2) where the pair law keeps the pair, else 0.
-__device__ __forceinline__ float inv_cut(float r2, float cut2) {
-  return r2 >= cut2 ? rsqrt_dev(r2) : 0.0f;
-}
-__device__ __forceinline__ f2 inv_cut(f2 r2, float cut2) {
-  f2 inv;
-  inv.x = r2.x >= cut2 ? rsqrt_dev(r2.x) : 0.0f;
-  inv.y = r2.y >= cut2 ? rsqrt_dev(r2.y) : 0.0f;
-  return inv;
-}
-__device__ __forceinline__ double inv_cut(double r2, double cut2) {
-  // Branch-free (as the 4th-order kernel): the refinement runs on 1 below the cutoff.
-  const bool ok = r2 >= cut2;
-  const double inv = rsqrt_dev(ok ? r2 : 1.0);
-  return ok ? inv : 0.0;
-}
-
 // The sums and the predicted rows of one i-body (V = T) or of a pair of them (V = f2).
 template <typename V>
 struct H6Body {
@@ -114,21 +90,6 @@ struct H6Lane {
   H6Body<V> b[NB];
 };
 
-template <typename V, typename T>
-__device__ __forceinline__ void h6set(V& dst, int e, T v) {
-  if constexpr (std::is_same<V, f2>::value) {
-    if (e == 0) dst.x = v; else dst.y = v;
-  } else {
-    dst = v;
-  }
-}
-
-template <typename V>
-__device__ __forceinline__ auto h6get(const V& src, int e) {
-  if constexpr (std::is_same<V, f2>::value) return e == 0 ? src.x : src.y;
-  else return src;
-}
-
 // EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
 // stores one partial per chunk and i-body: PA[c][i] = (ax, ay, az, sum mu / r),
 // PJ[c][i] = (jx, jy, jz, 0), PS[c][i] = (sx, sy, sz, 0).
@@ -161,9 +122,9 @@ __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int 
     const int64_t row = ib + threadIdx.x + k * kBlock;
     const V4<T> x = XP[row], v = VP[row], p = AP[row];
     H6Body<V>& b = ln.b[k / E];
-    h6set(b.x, k % E, x.x); h6set(b.y, k % E, x.y); h6set(b.z, k % E, x.z);
-    h6set(b.u, k % E, v.x); h6set(b.v, k % E, v.y); h6set(b.w, k % E, v.z);
-    h6set(b.bx, k % E, p.x); h6set(b.by, k % E, p.y); h6set(b.bz, k % E, p.z);
+    vset(b.x, k % E, x.x); vset(b.y, k % E, x.y); vset(b.z, k % E, x.z);
+    vset(b.u, k % E, v.x); vset(b.v, k % E, v.y); vset(b.w, k % E, v.z);
+    vset(b.bx, k % E, p.x); vset(b.by, k % E, p.y); vset(b.bz, k % E, p.z);
   }
   auto fill = [&](int t) {
     const int64_t j0 = (int64_t)(c0 + t / tpc) * a.chunk + (int64_t)(t % tpc) * TB;
@@ -193,11 +154,11 @@ __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int 
       for (int k = 0; k < IPL; ++k) {
         const H6Body<V>& b = ln.b[k / E];
         V4<T> oa, oj, os;
-        oa.x = h6get(b.ax, k % E); oa.y = h6get(b.ay, k % E); oa.z = h6get(b.az, k % E);
-        oa.w = h6get(b.ph, k % E);
-        oj.x = h6get(b.jx, k % E); oj.y = h6get(b.jy, k % E); oj.z = h6get(b.jz, k % E);
+        oa.x = vget(b.ax, k % E); oa.y = vget(b.ay, k % E); oa.z = vget(b.az, k % E);
+        oa.w = vget(b.ph, k % E);
+        oj.x = vget(b.jx, k % E); oj.y = vget(b.jy, k % E); oj.z = vget(b.jz, k % E);
         oj.w = T(0);
-        os.x = h6get(b.sx, k % E); os.y = h6get(b.sy, k % E); os.z = h6get(b.sz, k % E);
+        os.x = vget(b.sx, k % E); os.y = vget(b.sy, k % E); os.z = vget(b.sz, k % E);
         os.w = T(0);
         const int64_t o = (int64_t)c * a.n_pad + ib + threadIdx.x + k * kBlock;
         PA[o] = oa;

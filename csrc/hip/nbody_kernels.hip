@@ -37,12 +37,16 @@ namespace gs {
 //   FM_PHI   : FM_EXACT plus the potential sum (diagnostics / accel queries).
 enum { FM_FAST = 0, FM_EXACT = 1, FM_PHI = 2 };
 
-// One i-j interaction. 3 sub + 3 fma (r^2) + rsq + 3 mul + 3 fma; FM_EXACT adds cmp/select.
-template <typename T, int FM>
-__device__ __forceinline__ void interact(T xi, T yi, T zi, T xj, T yj, T zj, T muj, T cut2,
-                                         T eps2, T& ax, T& ay, T& az, T& ph) {
-  const T dx = xj - xi, dy = yj - yi, dz = zj - zi;
-  const T r2 = fma_(dz, dz, fma_(dy, dy, fma_(dx, dx, eps2)));
+// One i-j interaction per element of V (gs_tile.h): a scalar T or, fp32 with pairs of i per lane,
+// a 2-vector: every op but the rsq is then one v_pk_* for two interactions, and the j scalar is
+// broadcast by op_sel instead of SGPR-pair copies (+10 % over the compiler's own SLP packing,
+// profiles/r1_ab_explicit_pk.jsonl). 3 sub + 3 fma (r^2) + rsq + 3 mul + 3 fma; FM_EXACT adds
+// cmp/select.
+template <int FM, typename V, typename T>
+__device__ __forceinline__ void interact(V xi, V yi, V zi, const V4<T>& q, T cut2, T eps2, V& ax,
+                                         V& ay, V& az, V& ph) {
+  const V dx = V(q.x) - xi, dy = V(q.y) - yi, dz = V(q.z) - zi;
+  const V r2 = fmav(dz, dz, fmav(dy, dy, fmav(dx, dx, V(eps2))));
   if constexpr (sizeof(T) == 8 && FM != FM_PHI) {
     // fp64 step path: refine r^-3 directly instead of r^-1. With y0 = v_rsq_f64(r2) and
     // e = 1 - r2 y0^2 (|e| <= 1.1e-7), r^-3 = y0^3 (1 - e)^(-3/2) = y0^3 (1 + 3/2 e + 15/8 e^2)
@@ -57,58 +61,22 @@ __device__ __forceinline__ void interact(T xi, T yi, T zi, T xj, T yj, T zj, T m
     // v_mov_b32 pairs for a v_fmac in every interaction.
     const T c15 = T(1.5) + eps2 * T(0), c1875 = T(1.875) + eps2 * T(0);
     const T corr = fma_(e, fma_(e, c1875, c15), T(1));
-    T s = (muj * (y2 * y0)) * corr;
+    T s = (q.w * (y2 * y0)) * corr;
     if constexpr (FM == FM_EXACT) s = r2 >= cut2 ? s : T(0);
     ax = fma_(s, dx, ax);
     ay = fma_(s, dy, ay);
     az = fma_(s, dz, az);
     return;
   }
-  T inv;
-  if constexpr (FM == FM_FAST) {
-    inv = rsqrt_dev(r2);
-  } else {
-    const bool ok = r2 >= cut2;
-    if constexpr (sizeof(T) == 8) {
-      // Branch-free: the Newton sequence would otherwise be predicated behind exec-mask jumps.
-      inv = rsqrt_dev(ok ? r2 : T(1));
-      inv = ok ? inv : T(0);
-    } else {
-      inv = ok ? rsqrt_dev(r2) : T(0);
-    }
-  }
-  const T mi = muj * inv;
-  const T s = mi * (inv * inv);
-  ax = fma_(s, dx, ax);
-  ay = fma_(s, dy, ay);
-  az = fma_(s, dz, az);
+  V inv;
+  if constexpr (FM == FM_FAST) inv = rsqrt_dev(r2);
+  else inv = inv_cut(r2, cut2);
+  const V mi = V(q.w) * inv;
+  const V s = mi * (inv * inv);
+  ax = fmav(s, dx, ax);
+  ay = fmav(s, dy, ay);
+  az = fmav(s, dz, az);
   if constexpr (FM == FM_PHI) ph += mi;
-}
-
-// fp32, pairs of i per lane as 2-vectors: every op but the rsq is one v_pk_* for two
-// interactions, and the j scalar is broadcast by op_sel instead of SGPR-pair copies. Each
-// element sees exactly the scalar interact() arithmetic, so results are bit-identical
-// (+10 % over the compiler's own SLP packing: profiles/r1_ab_explicit_pk.jsonl).
-
-template <int FM>
-__device__ __forceinline__ void interact_pk(f2 xi, f2 yi, f2 zi, float xj, float yj, float zj,
-                                            float muj, float cut2, float eps2, f2& ax, f2& ay,
-                                            f2& az) {
-  const f2 dx = f2(xj) - xi, dy = f2(yj) - yi, dz = f2(zj) - zi;
-  const f2 r2 = __builtin_elementwise_fma(
-      dz, dz, __builtin_elementwise_fma(dy, dy, __builtin_elementwise_fma(dx, dx, f2(eps2))));
-  f2 inv;
-  inv.x = rsqrt_dev(r2.x);
-  inv.y = rsqrt_dev(r2.y);
-  if constexpr (FM == FM_EXACT) {
-    inv.x = r2.x >= cut2 ? inv.x : 0.0f;
-    inv.y = r2.y >= cut2 ? inv.y : 0.0f;
-  }
-  const f2 mi = f2(muj) * inv;
-  const f2 s = mi * (inv * inv);
-  ax = __builtin_elementwise_fma(s, dx, ax);
-  ay = __builtin_elementwise_fma(s, dy, ay);
-  az = __builtin_elementwise_fma(s, dz, az);
 }
 
 template <typename T, int IPL>
@@ -130,8 +98,9 @@ __device__ __forceinline__ void interact_all(IState<T, IPL>& s, const V4<T>& q, 
 #pragma unroll
     for (int k = 0; k < IPL; k += 2) {
       f2 ax = {s.ax[k], s.ax[k + 1]}, ay = {s.ay[k], s.ay[k + 1]}, az = {s.az[k], s.az[k + 1]};
-      interact_pk<FM>(f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]},
-                      q.x, q.y, q.z, q.w, cut2, eps2, ax, ay, az);
+      f2 ph;  // (FM_PHI runs the scalar form)
+      interact<FM>(f2{s.x[k], s.x[k + 1]}, f2{s.y[k], s.y[k + 1]}, f2{s.z[k], s.z[k + 1]}, q, cut2,
+                   eps2, ax, ay, az, ph);
       s.ax[k] = ax.x; s.ax[k + 1] = ax.y;
       s.ay[k] = ay.x; s.ay[k + 1] = ay.y;
       s.az[k] = az.x; s.az[k + 1] = az.y;
@@ -140,8 +109,7 @@ __device__ __forceinline__ void interact_all(IState<T, IPL>& s, const V4<T>& q, 
   }
 #pragma unroll
   for (int k = 0; k < IPL; ++k)
-    interact<T, FM>(s.x[k], s.y[k], s.z[k], q.x, q.y, q.z, q.w, cut2, eps2, s.ax[k], s.ay[k],
-                     s.az[k], s.ph[k]);
+    interact<FM>(s.x[k], s.y[k], s.z[k], q, cut2, eps2, s.ax[k], s.ay[k], s.az[k], s.ph[k]);
 }
 
 

@@ -1,10 +1,14 @@
-// Device helpers shared by the one-sided force kernels (nbody_kernels.hip) and the Hermite
-// kernels of both orders (nbody_hermite.hip, nbody_hermite6.hip): 4-vectors, the reciprocal
-// square root, the fused multiply-adds, the workgroup minimum, the LDS-DMA tile fill and the
-// geometry an evaluate launch must have.
+// Device helpers shared by the one-sided force kernels (nbody_kernels.hip), the Hermite kernels
+// of both orders (nbody_hermite.hip, nbody_hermite6.hip) and the k-nearest-neighbour kernel
+// (nbody_knn.hip): 4-vectors, the reciprocal square root, the fused multiply-adds, the helpers of
+// a pair term written once over its element type (a scalar or a 2-vector: fmav, inv_cut, vget /
+// vset), the workgroup minimum, the LDS-DMA tile fill and the geometry an evaluate launch must
+// have.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "gs_common.h"
 
@@ -36,6 +40,57 @@ __device__ __forceinline__ double fma_(double a, double b, double c) { return __
 // Two fp32 values per lane as one 2-vector (v_pk_* operands).
 using f2 = float __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+
+// The pair terms are written once over their element type V: a scalar T (one i-body) or, fp32
+// with an even number of bodies per lane, f2 (two i-bodies, v_pk_* operations). Each element of
+// a 2-vector sees exactly the scalar arithmetic, so the bits do not depend on the packing.
+
+// The fused multiply-add of V: fma_ (a scalar) or fma2 (a pair).
+template <typename V>
+__device__ __forceinline__ V fmav(V a, V b, V c) {
+  if constexpr (std::is_same<V, f2>::value) return fma2(a, b, c);
+  else return fma_(a, b, c);
+}
+
+// Element e of a V (a scalar is its own element 0).
+template <typename V, typename T>
+__device__ __forceinline__ void vset(V& dst, int e, T v) {
+  if constexpr (std::is_same<V, f2>::value) {
+    if (e == 0) dst.x = v; else dst.y = v;
+  } else {
+    dst = v;
+  }
+}
+template <typename V>
+__device__ __forceinline__ auto vget(const V& src, int e) {
+  if constexpr (std::is_same<V, f2>::value) return e == 0 ? src.x : src.y;
+  else return src;
+}
+
+__device__ __forceinline__ f2 rsqrt_dev(f2 x) {
+  f2 y;
+  y.x = rsqrt_dev(x.x);
+  y.y = rsqrt_dev(x.y);
+  return y;
+}
+
+// 1 / sqrt(r2) where the pair law keeps the pair (r2 >= cut2), else 0.
+__device__ __forceinline__ float inv_cut(float r2, float cut2) {
+  return r2 >= cut2 ? rsqrt_dev(r2) : 0.0f;
+}
+__device__ __forceinline__ f2 inv_cut(f2 r2, float cut2) {
+  f2 inv;
+  inv.x = r2.x >= cut2 ? rsqrt_dev(r2.x) : 0.0f;
+  inv.y = r2.y >= cut2 ? rsqrt_dev(r2.y) : 0.0f;
+  return inv;
+}
+__device__ __forceinline__ double inv_cut(double r2, double cut2) {
+  // Branch-free: the refinement would otherwise be predicated behind exec-mask jumps; it runs
+  // on 1 below the cutoff.
+  const bool ok = r2 >= cut2;
+  const double inv = rsqrt_dev(ok ? r2 : 1.0);
+  return ok ? inv : 0.0;
+}
 
 __device__ __forceinline__ double wave_min(double v) {
   for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
