@@ -409,6 +409,11 @@ def assert_gate(a4, j4, n: int, dtype: str, rows=None, label: str = "", **where)
 
 
 # ---- what a failure corresponds to ------------------------------------------------------------
+def _holds(got_row, want_bound) -> bool:
+    """Whether one returned row is at the gate against (reference, eps x scale) of another row."""
+    return bool((np.abs(got_row - want_bound[0][0]) / want_bound[1][0]).max() <= GATE)
+
+
 def _unit_matrix(starts, markers) -> np.ndarray:
     """(units, K) 0/1: marker k lies in the unit that begins at starts[u]."""
     u = np.searchsorted(starts, markers, side="right") - 1
@@ -419,24 +424,44 @@ def _unit_matrix(starts, markers) -> np.ndarray:
 
 def locate(a4, j4, n: int, dtype: str, rows=None, ipl: int = 0, groups: int = 0, P: int = 0,
            narrow: bool = False, nn: bool = False, worst: int = 4, limit: int = 1024) -> list:
+    """locate_units() on the (a, j, phi) columns of case n under the launch shape ipl x groups."""
+    b, m, ref = probe_case(n, dtype)
+    p, v, mu = seen(b, dtype)
+
+    def columns(r):
+        ra, rj, rphi, sa, sj = (x[r] for x in ref)
+        return (np.concatenate([ra, rj, rphi[:, None]], 1),
+                EPS[dtype] * np.concatenate([sa, sj, np.abs(rphi)[:, None]], 1) + 1e-300)
+
+    def terms(r):
+        ta, tj, tp = pair_terms(p[r], v[r], p[m], v[m], mu[m])
+        return np.concatenate([ta, tj, tp[:, :, None]], 2)
+
+    got = np.concatenate([a4[:, :3], j4[:, :3], a4[:, 3:4]], 1)
+    return locate_units(got, columns, terms, m, geometry(n, dtype, ipl, groups, nn), n, rows, P,
+                        narrow, worst, limit)
+
+
+def locate_units(got, columns, terms, m, g: dict, n: int, rows=None, P: int = 0,
+                 narrow: bool = False, worst: int = 4, limit: int = 1024) -> list:
     """For the rows that miss the gate (the `limit` worst), fit what the residual is: up to two
     units, each missing (-1) or doubled (+1), where a unit is one marker, the markers of one
     tile, of one chunk or (narrow) of one narrow slice, the smallest unit that fits first; where
     no unit fits and P ranks are in use, whether the row holds the reference of the same local
-    row of another rank. Returns the `worst` largest groups as dicts: kind / what / markers /
-    chunk / tile / group (the chunk group under the launch shape ipl x groups) or slice, the
+    row of another rank. got: (rows, C) what the kernel returned; columns(r): (reference,
+    eps x scale) (len(r), C) of the bodies r; terms(r): the (len(r), K, C) marker terms; g: the
+    geometry. Returns the `worst` largest groups as dicts: kind / what / markers /
+    chunk / tile / group (the chunk group under the launch shape of g) or slice, the
     i-blocks and the ranks (or narrow slices) of the failing rows, rows, fitted (how many of
     them the fit brings back inside the gate), ratio."""
-    b, m, ref = probe_case(n, dtype)
-    g = geometry(n, dtype, ipl, groups, nn)
     idx = np.arange(n) if rows is None else np.asarray(rows, dtype=np.int64)
-    r_all = ratios(a4, j4, ref, dtype, rows)
+    want, bound = columns(idx)
+    r_all = np.abs(got - want) / bound
     rmax = np.where(np.isfinite(r_all), r_all, np.inf).max(1)
     bad = np.nonzero(~(rmax <= GATE))[0]
     bad = bad[np.argsort(-rmax[bad], kind="stable")][:limit]
     if not len(bad):
         return []
-    p, v, mu = seen(b, dtype)
     cand = [("marker", np.eye(len(m)), m)]
     if narrow:
         st = np.arange(g["n_slices"]) * g["slice"]
@@ -448,13 +473,11 @@ def locate(a4, j4, n: int, dtype: str, rows=None, ipl: int = 0, groups: int = 0,
         cand.append(("chunk", _unit_matrix(st, m), st))
     kinds = [(k, int(s)) for k, M, starts in cand for s, row in zip(starts, M) if row.any()]
     M = np.concatenate([M[M.any(1)] for _, M, _ in cand])
-    ra, rj, rphi, sa, sj = (x[idx[bad]] for x in ref)
-    ta, tj, tp = pair_terms(p[idx[bad]], v[idx[bad]], p[m], v[m], mu[m])
-    T = np.concatenate([ta, tj, tp[:, :, None]], 2)                       # (b, K, 7)
-    U = np.einsum("uk,bkc->buc", M, T, optimize=True)                     # (b, units, 7)
-    bound = EPS[dtype] * np.concatenate([sa, sj, np.abs(rphi)[:, None]], 1) + 1e-300
-    got = np.concatenate([a4[bad, :3], j4[bad, :3], a4[bad, 3:4]], 1)
-    res = got - np.concatenate([ra, rj, rphi[:, None]], 1)
+    T = terms(idx[bad])                                                   # (b, K, C)
+    C = T.shape[2]
+    U = np.einsum("uk,bkc->buc", M, T, optimize=True)                     # (b, units, C)
+    bound = bound[bad]
+    res = got[bad] - want[bad]
     res = np.where(np.isfinite(res), res, 0.0)
     # one unit: missing (got = ref - U) or doubled (got = ref + U)
     left = np.stack([np.abs((res[:, None, :] + U) / bound[:, None, :]).max(-1),
@@ -470,8 +493,8 @@ def locate(a4, j4, n: int, dtype: str, rows=None, ipl: int = 0, groups: int = 0,
         sl = np.nonzero(~fitted[i0:i0 + 32])[0] + i0
         if not len(sl) or len(big) < 2:
             continue
-        V = U[sl][:, big, None, :] * sg[None, None, :, None]              # (b, nb, 2, 7)
-        V = V.reshape(len(sl), -1, 7)
+        V = U[sl][:, big, None, :] * sg[None, None, :, None]              # (b, nb, 2, C)
+        V = V.reshape(len(sl), -1, C)
         two = np.abs((res[sl][:, None, None, :] + V[:, :, None, :] + V[:, None, :, :])
                      / bound[sl][:, None, None, :]).max(-1)               # (b, 2 nb, 2 nb)
         k = two.reshape(len(sl), -1).argmin(1)
@@ -488,8 +511,7 @@ def locate(a4, j4, n: int, dtype: str, rows=None, ipl: int = 0, groups: int = 0,
             me = next(r for r, (r0, c) in enumerate(ranks) if r0 <= row < r0 + c)
             for r, (r0, c) in enumerate(ranks):
                 src = row - ranks[me][0] + r0
-                if r != me and src < n and ratios(a4[bad[i]][None], j4[bad[i]][None], ref, dtype,
-                                                  [src]).max() <= GATE:
+                if r != me and src < n and _holds(got[bad[i]], columns(np.array([src]))):
                     key, extra = ("rows", me, r), dict(kind="rows of another rank", rank=me,
                                                       holds_rank=r)
                     fitted[i] = True

@@ -1,7 +1,7 @@
 """The gfx950 acceleration+jerk+snap kernel of the 6th-order Hermite scheme and its device-side
 step chain against the NumPy oracle and the native CPU engine: tile and chunk edges, the pair
 law, bitwise launch-shape independence, the step chain, the order of accuracy, the driver,
-checkpoints and the native refusals.
+checkpoints, the native refusals, and one step from a state the test chose (section 7).
 
 Accuracy gates: |err| <= 128 eps sum_j |term_ij| (the project's gate), with the snap's scale from
 oracle.acc_jerk_snap(with_abs=True). The reference is the oracle on the inputs as the kernel sees
@@ -21,6 +21,7 @@ from gravsim.runtime.hermite import HermiteCpuEngine, HermiteHipEngine
 from gravsim.runtime.simulation import Simulation
 
 import hermite6_helpers as h6
+import hermite6_probe_helpers as h6p
 
 pytestmark = pytest.mark.gpu
 
@@ -339,3 +340,47 @@ def test_order_6_then_4_is_the_fresh_order_4_run(hip, dtype):
     assert st_a == st_b and st_a.steps == 3
     for x, y in zip(rows_a, rows_b):
         assert x.tobytes() == y.tobytes()
+
+
+# ---- 7. one step from a supplied state ----------------------------------------------------
+@pytest.mark.parametrize("n", h6p.STEP_SIZES)
+@pytest.mark.parametrize("dtype,ipl", [("fp32", 1), ("fp32", 2), ("fp64", 1)])
+def test_one_step_from_a_supplied_state(hip, n, dtype, ipl):
+    """The evaluate kernel reads acceleration rows the test chose, inside the step chain: the
+    state is (x0, 0, A0, 0, 0, 0) with A0 unrelated to any kernel output and h = 1024 s, so the
+    predicted rows are known to the bit (h6p.supplied_state). After step(1): a1, j1, s1 against
+    oracle.acc_jerk_snap at those rows at 128 eps scale (the gated launch, the HM_STEP reduce and
+    the predict kernel's AP; n_pad holds 1048, 2047 and 2047 ghost rows), v1 and x1 against
+    h6_correct at 10 roundings, the crackle against oracle.hermite6_high at one rounding, and
+    dt_next against oracle.hermite6_dt at 1e-9 (h6p.check_supplied_step). The CPU engine passes
+    the same gates (tests/test_hermite6_probe_cpu.py) and stands at the same time and step."""
+    kw = dict(n=n, dtype=dtype, integrator="hermite", hermite_order=6, dt=h6p.STEP_H,
+              eta=h6p.STEP_ETA)
+    eng = HermiteHipEngine(SimConfig(device="gpu", ipl=ipl, **kw).validate())
+    try:
+        assert eng.native_layout["ipl"] == ipl
+        out = h6p.check_supplied_step(eng, n, dtype, label=f"step n {n} {dtype} ipl {ipl}")
+    finally:
+        eng.close()
+    print(f"step n={n} {dtype} ipl {ipl}: {h6p.fmt(out['worst'])}; v1 {out['v']:.2f} x1 "
+          f"{out['x']:.2f} of {h6p.CORRECT_ROUNDINGS} u sum |terms|; crackle {out['crackle']:.2f} "
+          f"of its bound; dt_next {out['dt_next']:.6g} ({out['dt_rel']:.1e} relative), body "
+          f"{out['row']}")
+    cpu = HermiteCpuEngine(SimConfig(device="cpu", **kw).validate())
+    ref = h6p.check_supplied_step(cpu, n, dtype, label=f"cpu step n {n} {dtype}")
+    g, c = out["status"], ref["status"]
+    assert (g.time, g.steps) == (c.time, c.steps) == (h6p.STEP_H, 1)
+    # (dt_next is gated on each engine's own rows above: in fp32 the two engines' a1, j1, s1
+    # differ by their rounding, and the steps they ask for with them, by about 1e-7)
+    if n == 1000 and ipl == 1:  # a fixed step of the same size: the same rows, the ceiling next
+        fixed = HermiteHipEngine(SimConfig(device="gpu", **dict(kw, eta=0.0)).validate())
+        try:
+            st = h6p.supplied_case(n, dtype)[0]
+            fixed.load(st["bodies"], **st["load"])
+            fixed.step(1)
+            s = fixed.state()
+            for x, y in zip((s.pos, s.vel) + tuple(fixed.carried()), out["rows"]):
+                assert np.array_equal(x, y)
+            assert fixed.status().dt_next == h6p.STEP_H
+        finally:
+            fixed.close()
