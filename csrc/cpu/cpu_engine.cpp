@@ -647,6 +647,14 @@ int gs_cpu_accjerksnap_f32(const float* X4, const float* V4, const float* A4, in
   return accjerk_rows<float, false, true>(X4, V4, n_real, nullptr, i0, i1 - i0, chunk, cut2, eps2,
                                           acc4, jerk4, A4, snap4);
 }
+int gs_cpu_accjerksnap_idx_f64(const double* X4, const double* V4, const double* A4,
+                               int64_t n_real, const int32_t* idx, int64_t n_idx, int32_t chunk,
+                               double cut2, double eps2, double* acc4, double* jerk4,
+                               double* snap4) {
+  if (!list_ok("cpu_accjerksnap_idx", idx, n_idx)) return -1;
+  return accjerk_rows<double, false, true>(X4, V4, n_real, idx, 0, n_idx, chunk, cut2, eps2, acc4,
+                                           jerk4, A4, snap4);
+}
 int gs_cpu_hermite6_step_f64(double* X4, double* V4, double* A4, double* J4, double* S4,
                              double* C4, double* scratch, int64_t n_real, int32_t chunk, double h,
                              double cut2, double eps2, double eta, double* dt_min_out) {

@@ -7,10 +7,13 @@
 // The order is a property of the run (gs_hermite_set_order): order 6 also carries snap and
 // crackle rows, its chain is the same four launches with the kernels of nbody_hermite6.hip, and
 // the one path below asks the order where the two differ (with_args, launch_shape, eval_current,
-// the carried rows). It runs on one rank in fp32 or fp64 with shared steps (refuse6).
+// the carried rows). It runs on one rank in fp32 or fp64; gs_hermite_set_block keeps refusing it,
+// and its block steps (fp64 only) are switched on by gs_hermite_set_block6 (refuse6).
 // Block mode (gs_hermite_set_block): per-body times and levels, an active list and a second
 // control block; a block step is a chain of seven launches, and gs_hermite_step advances whole
-// macro steps of dt against a device-side target time, one status read per 32 chains.
+// macro steps of dt against a device-side target time, one status read per 32 chains. Order 6
+// runs the same chain: order 4's next, control, compact and start kernels, and its own
+// predict-all, narrow, wide and correct kernels (block_chain).
 // Three precisions: fp32 and fp64 throughout, and mixed (GS_MIXED): the state rows, the reduce
 // and the corrector in fp64, the predicted rows (position as double-single hi + lo) and the
 // partial sums of the pair kernels in fp32.
@@ -76,6 +79,7 @@ struct gs_hermite {
   // the snap partials and output
   int32_t order = 4;
   void *S = nullptr, *C = nullptr, *AP = nullptr, *PS = nullptr, *s_out = nullptr;
+  void* NS = nullptr;  // order 6 in block mode: the snap partials of the narrow path
 };
 
 namespace {
@@ -139,6 +143,8 @@ void set_args(const gs_hermite* h, int mode, bool phi, gs::H6Args<T>& a) {
   a.phi = phi ? 1 : 0;
   a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
   a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
+  a.blk = h->blk;
+  a.NS = static_cast<T*>(h->NS);
 }
 
 template <typename A>
@@ -317,13 +323,18 @@ int eval_current(gs_hermite* h, A a) {
 
 // What order 6 does not run with, each stated once: the settings of the engine itself, then
 // what a caller is about to switch on (`asked`). Null: nothing stands in the way.
-enum { R6_NONE, R6_BLOCK, R6_NN, R6_GROUP };
+enum { R6_NONE, R6_BLOCK, R6_BLOCK6, R6_NN, R6_GROUP };
 const char* refuse6(const gs_hermite* h, int asked = R6_NONE) {
   if (multi(h)) return "hermite order 6 runs on one rank (nranks > 1, --gpus, is refused)";
   if (h->cfg.dtype == GS_MIXED)
     return "hermite order 6 has no mixed precision (GS_MIXED, --dtype mixed, is refused)";
-  if (h->block || asked == R6_BLOCK)
-    return "hermite order 6 has no block steps (gs_hermite_set_block, --block-steps)";
+  // (block mode that gs_hermite_set_block switched on is order 4's)
+  if ((h->block && h->order != 6) || asked == R6_BLOCK)
+    return "hermite order 6 has no block steps through gs_hermite_set_block (--block-steps): its "
+           "own are gs_hermite_set_block6 (--block-steps6), in fp64";
+  if (asked == R6_BLOCK6 && h->cfg.dtype != GS_FP64)
+    return "hermite order 6 runs block steps (gs_hermite_set_block6, --block-steps6) in fp64 only: "
+           "fp32 pair arithmetic collapses its step criterion (fp32 with block steps is refused)";
   if (h->nn || asked == R6_NN)
     return "hermite order 6 has no collisions (gs_hermite_set_collisions, --collisions)";
   if (asked == R6_GROUP)
@@ -622,7 +633,10 @@ int32_t default_narrow_max(const gs_hermite* h) {
   // beyond the measured sizes: n_pad / 8 from 262,144 up, n_pad / 16 (fp32), / 32 (fp64) below.
   // Mixed (§16): 8192 at 65,536 and 32,768 at 262,144, n_pad / 8 at both and elsewhere (its wide
   // path pays a third LDS read per j, its narrow path only one more coalesced load).
-  const int64_t div = h->n_pad >= 262144 || is_mixed(h) ? 8 : (h->esz == 4 ? 16 : 32);
+  // Order 6 (fp64; §23): 4096 at 65,536 and 32,768 at 262,144 (profiles/hermite6_block_sweep.json),
+  // n_pad / 16 and n_pad / 8; the same rule between and beyond the two measured sizes.
+  const int64_t div = h->n_pad >= 262144 || is_mixed(h) ? 8
+                      : h->order == 6 ? 16 : (h->esz == 4 ? 16 : 32);
   int64_t d = 1;
   while (2 * d <= h->n_pad / div) d *= 2;
   return (int32_t)d;
@@ -630,9 +644,10 @@ int32_t default_narrow_max(const gs_hermite* h) {
 
 void free_block(gs_hermite* h) {
   for (void* p : {(void*)h->blk.bc, (void*)h->blk.tb, (void*)h->blk.level, (void*)h->blk.list,
-                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ})
+                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ, h->NS})
     if (p) (void)hipFree(p);
   h->blk = gs::HBlock{};
+  h->NS = nullptr;
   (void)size_nni(h, h->nn != 0);  // (no slots: freed)
 }
 
@@ -643,13 +658,15 @@ int set_narrow(gs_hermite* h, int32_t narrow_max) {
   GS_HIP(hipStreamSynchronize(h->stream));
   if (h->blk.NA) GS_HIP(hipFree(h->blk.NA));
   if (h->blk.NJ) GS_HIP(hipFree(h->blk.NJ));
-  h->blk.NA = h->blk.NJ = nullptr;
+  if (h->NS) GS_HIP(hipFree(h->NS));
+  h->blk.NA = h->blk.NJ = h->NS = nullptr;
   h->blk.cap = narrow_max;
   h->narrow_max = narrow_max;
   if (narrow_max > 0) {
     const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->psz;
     GS_HIP(hipMalloc(&h->blk.NA, bytes));
     GS_HIP(hipMalloc(&h->blk.NJ, bytes));
+    if (h->order == 6) GS_HIP(hipMalloc(&h->NS, bytes));  // (the snap partials)
   }
   if (size_nni(h, h->nn != 0)) return -1;
   gs::HermiteBlockCtrl c;
@@ -696,8 +713,29 @@ int block_chain(gs_hermite* h, const gs::HArgs<T, S>& a) {
   return 0;
 }
 
+// Order 6 (fp64): the same seven launches; next, control and compact are order 4's kernels on
+// the block state (they read blk and n_real of an HArgs).
+int block_chain(gs_hermite* h, const gs::H6Args<double>& a) {
+  gs::HArgs<double, double> c{};
+  c.blk = a.blk;
+  c.n_real = a.n_real;
+  c.n_pad = a.n_pad;
+  GS_HIP((gs::launch_block_next<double, double>(c, h->stream)));
+  GS_HIP(gs::launch_block6_predict(a, h->stream));
+  GS_HIP((gs::launch_block_compact<double, double>(c, h->stream)));
+  GS_HIP(gs::launch_block6_narrow(a, h->stream));
+  GS_HIP(gs::launch_block6_wide(a, h->ipl, h->groups, h->stream));
+  GS_HIP(gs::launch_block6_correct(a, h->stream));
+  return 0;
+}
+int block_chain(gs_hermite*, const gs::H6Args<float>&) {
+  gs_set_error("hermite order 6 runs block steps in fp64 only");
+  return -1;
+}
+
 // n macro steps: chains in batches of 32 against the device-side target, one status read each.
-template <typename T, typename S>
+// A: the kernel arguments of the run's precision and order (with_args).
+template <typename A>
 int block_step_t(gs_hermite* h, int32_t nsteps) {
   gs::HermiteBlockCtrl c;
   if (read_bctrl(h, &c)) return -1;
@@ -710,11 +748,11 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
   if (target <= c.t_ticks) return 0;
   c.target = target;
   if (write_bctrl(h, c)) return -1;
-  const gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_STEP, false);
+  const A a = make_args<A>(h, gs::HM_STEP, false);
   while (c.t_ticks < target) {
     const int64_t before = c.t_ticks;
     for (int k = 0; k < 32; ++k)
-      if (block_chain<T, S>(h, a)) return -1;
+      if (block_chain(h, a)) return -1;
     if (read_bctrl(h, &c)) return -1;
     if (c.t_ticks == before) {
       gs_set_error("hermite block steps: no progress (body times out of step)");
@@ -754,6 +792,41 @@ int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t pa
   }
   if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
       ((q || nn) && download_pair(h, h->q_out, h->nn_out, n_idx, q, nn)))
+    return -1;
+  return write_bctrl(h, keep);
+}
+
+// Order 6: one pass at the rows (x, v, carried a) of the current state.
+int derivs_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
+                   double* jerk4, double* snap4, int32_t reps, double* ms) {
+  gs::HermiteBlockCtrl keep;
+  if (read_bctrl(h, &keep)) return -1;
+  gs::HermiteBlockCtrl c = keep;
+  c.n_act = n_idx;
+  c.path = path;
+  c.active = 1;
+  GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
+                        h->stream));
+  if (write_bctrl(h, c)) return -1;
+  gs::H6Args<double> a = make_args<gs::H6Args<double>>(h, gs::HM_OUT, true);
+  a.XP = a.X;
+  a.VP = a.V;
+  a.AP = a.A;
+  EventTimer timer;
+  if (ms && (timer.create() || timer.start(h->stream))) return -1;
+  for (int32_t r = 0; r < reps; ++r) {
+    if (path == gs::HP_NARROW)
+      GS_HIP(gs::launch_block6_narrow(a, h->stream));
+    else
+      GS_HIP(gs::launch_block6_wide(a, h->ipl, h->groups, h->stream));
+    GS_HIP(gs::launch_block6_correct(a, h->stream));
+  }
+  if (ms) {
+    if (timer.stop(h->stream, ms)) return -1;
+    *ms /= reps;
+  }
+  if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
+      download_rows(h, h->s_out, n_idx, snap4, 4))
     return -1;
   return write_bctrl(h, keep);
 }
@@ -1073,9 +1146,8 @@ int gs_hermite_derivs_nn(gs_hermite* h, double* acc4, double* jerk4, double* q, 
 int gs_hermite_step(gs_hermite* h, int32_t nsteps) {
   GS_HIP(hipSetDevice(h->cfg.device));
   if (h->block)
-    return by_dtype(h, [&](auto t, auto s) {
-      return block_step_t<decltype(t), decltype(s)>(h, nsteps);
-    });
+    return with_args(h, gs::HM_STEP, false,
+                     [&](auto a) { return block_step_t<decltype(a)>(h, nsteps); });
   return with_args(h, gs::HM_STEP, false,
                    [&](auto a) { return step_t<decltype(a)>(&h, 1, nsteps); });
 }
@@ -1137,7 +1209,8 @@ int gs_hermite_status(gs_hermite* h, gs_hermite_info* out) {
   return 0;
 }
 
-int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
+// Block mode on or off: gs_hermite_set_block (order 4) and gs_hermite_set_block6 (order 6).
+static int set_block_mode(gs_hermite* h, int32_t on, int32_t max_level, int32_t order) {
   if (!h) { gs_set_error("hermite set_block: null argument"); return -1; }
   GS_HIP(hipSetDevice(h->cfg.device));
   if (!on) {
@@ -1150,7 +1223,15 @@ int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
     gs_set_error("hermite block steps (block_steps) run on one rank");
     return -1;
   }
-  if (h->order == 6) { gs_set_error(refuse6(h, R6_BLOCK)); return -1; }
+  if (order == 6 && h->order != 6) {
+    gs_set_error("hermite set_block6: the order is not 6 (gs_hermite_set_order)");
+    return -1;
+  }
+  if (h->order == 6)
+    if (const char* why = refuse6(h, order == 6 ? R6_BLOCK6 : R6_BLOCK)) {
+      gs_set_error(why);
+      return -1;
+    }
   if (max_level < 0 || max_level > 40) {
     gs_set_error("hermite block steps: max_level must be in 0..40");
     return -1;
@@ -1180,6 +1261,14 @@ int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
   h->narrow_max = 0;
   if (reset_bctrl(h, 0)) return -1;
   return set_narrow(h, -1);
+}
+
+int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
+  return set_block_mode(h, on, max_level, 4);
+}
+
+int gs_hermite_set_block6(gs_hermite* h, int32_t on, int32_t max_level) {
+  return set_block_mode(h, on, max_level, 6);
 }
 
 int gs_hermite_set_block_tuning(gs_hermite* h, int32_t narrow_max) {
@@ -1250,11 +1339,10 @@ int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx
   return time_active_nn(h, idx, n_idx, path, 1, nullptr, acc4, jerk4, q, nn);
 }
 
-static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
-                          int32_t* nn) {
+// The checks of every derivs_active / time_active entry; *path 0 becomes the path narrow_max picks.
+static int active_args_ok(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t* path_io) {
+  int32_t path = *path_io;
   if (!h || !h->block) { gs_set_error("hermite derivs_active: not in block mode"); return -1; }
-  if (reps < 1) reps = 1;
   if (!idx || n_idx < 1 || n_idx > h->n || path < 0 || path > 2) {
     gs_set_error("hermite derivs_active: bad arguments");
     return -1;
@@ -1269,6 +1357,31 @@ static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int3
     gs_set_error("hermite derivs_active: narrow path needs n_idx <= narrow_max");
     return -1;
   }
+  *path_io = path;
+  return 0;
+}
+
+int gs_hermite_derivs_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                              double* acc4, double* jerk4, double* snap4) {
+  return gs_hermite_time_active6(h, idx, n_idx, path, 1, nullptr, acc4, jerk4, snap4);
+}
+
+int gs_hermite_time_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                            int32_t reps, double* ms, double* acc4, double* jerk4,
+                            double* snap4) {
+  if (active_args_ok(h, idx, n_idx, &path)) return -1;
+  if (h->order != 6) { gs_set_error("hermite derivs_active6: the order is not 6"); return -1; }
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return derivs_active6(h, idx, n_idx, path, acc4, jerk4, snap4, reps < 1 ? 1 : reps, ms);
+}
+
+static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
+                          int32_t* nn) {
+  if (active_args_ok(h, idx, n_idx, &path)) return -1;
+  if (h->order == 6)  // (a and j of gs_hermite_time_active6; order 6 has no collisions)
+    return gs_hermite_time_active6(h, idx, n_idx, path, reps, ms, acc4, jerk4, nullptr);
+  if (reps < 1) reps = 1;
   GS_HIP(hipSetDevice(h->cfg.device));
   return by_dtype(h, [&](auto t, auto s) {
     return derivs_active_t<decltype(t), decltype(s)>(h, idx, n_idx, path, acc4, jerk4, reps, ms,
@@ -1344,6 +1457,10 @@ int gs_hermite_set_order(gs_hermite* h, int32_t order) {
   if (order == 6)
     if (const char* why = refuse6(h)) { gs_set_error(why); return -1; }
   const int32_t was = h->order;
+  if (order != was && h->block) {  // (the narrow partials and the chain are the order's)
+    gs_set_error("hermite set_order: switch block steps off first (gs_hermite_set_block6)");
+    return -1;
+  }
   h->order = order;
   if (launch_shape(h)) {
     h->order = was;

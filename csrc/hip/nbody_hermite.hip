@@ -610,14 +610,7 @@ __device__ __forceinline__ int wave_sum_i32(int v) {
   return v;
 }
 
-// Seconds of a span of ticks: dt_max ticks 2^-L in fp64 (the run's dtype takes a cast of it).
-__device__ __forceinline__ double ticks_seconds(double dt_max, int64_t ticks, int L) {
-  return dt_max * ldexp((double)ticks, -L);
-}
-
-__device__ __forceinline__ bool body_due(const HBlock& b, int64_t i, int L, int64_t t_next) {
-  return b.tb[i] + ((int64_t)1 << (L - b.level[i])) == t_next;
-}
+// (ticks_seconds, body_due and the level rule block_new_level: gs_hermite.h, shared with order 6)
 
 // NEXT, stage 1: per-workgroup minimum of tb + step over the real bodies.
 template <typename T, typename S>
@@ -866,19 +859,7 @@ __global__ __launch_bounds__(kBlock) void block_correct_kernel(typename K::Args 
   b.tb[i] = t_next;
   double want;
   const bool rated = aarseth_dt(hd, eta, a0, j0, m, want);
-  int k = b.level[i];
-  if (rated) {
-    const double dtk = ldexp(dt_max, -k);
-    if (want < dtk) {
-      while (k < L && ldexp(dt_max, -k) > want) ++k;
-      if (ldexp(dt_max, -k) > want) atomicAdd(&bc->level_clamped, 1ull);
-    } else if (k > 0 && want >= 2.0 * dtk &&
-               (t_next & (((int64_t)1 << (L - k + 1)) - 1)) == 0) {
-      --k;
-    }
-  }
-  b.level[i] = k;
-  if (k > bc->level_max) atomicMax(&bc->level_max, k);
+  b.level[i] = block_new_level(bc, b.level[i], rated, want, t_next, L, dt_max);
 }
 
 // START: the level of every real body from the carried a, j (the smallest k with
@@ -1064,6 +1045,11 @@ hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s) {
     return hlaunch(block_predict_kernel<decltype(k)>, row_grid(a.n_pad), s, a);
   });
   if (e != hipSuccess) return e;
+  return launch_block_compact<T, S>(a, s);
+}
+
+template <typename T, typename S>
+hipError_t launch_block_compact(const HArgs<T, S>& a, hipStream_t s) {
   return hlaunch(block_compact_kernel<T, S>, row_grid(a.n_pad), s, a);
 }
 
@@ -1114,6 +1100,7 @@ hipError_t launch_block_init(const HArgs<T, S>& a, int64_t t0, hipStream_t s) {
   template hipError_t launch_hermite_stage<T, S>(const HArgs<T, S>&, hipStream_t);               \
   template hipError_t launch_block_next<T, S>(const HArgs<T, S>&, hipStream_t);                  \
   template hipError_t launch_block_predict<T, S>(const HArgs<T, S>&, hipStream_t);               \
+  template hipError_t launch_block_compact<T, S>(const HArgs<T, S>&, hipStream_t);               \
   template hipError_t launch_block_narrow<T, S>(const HArgs<T, S>&, hipStream_t);                \
   template hipError_t launch_block_wide<T, S>(const HArgs<T, S>&, int, int, hipStream_t);        \
   template hipError_t launch_block_correct<T, S>(const HArgs<T, S>&, hipStream_t);               \

@@ -22,6 +22,12 @@
 //     and the number of chunk groups change the grid, never the bits.
 // Step chain (one stream, no host round trip): control (hermite_ctrl_kernel, shared with the
 // 4th-order chain) -> predict -> evaluate -> reduce + correct + next-step minima.
+// Block time steps (fp64; second half of this file): the chain of nbody_hermite.hip, whose
+// next-time minima, control, compaction and start kernels it runs as they are (they read the
+// block state, n_real, A and J only): next + control -> predict-all + mark (block6_predict_kernel)
+// -> compact -> evaluate of the active bodies, narrow (hermite6_narrow_kernel, parallel over j) or
+// wide (the LIST form of hermite6_eval_kernel) by n_act -> reduce + correct + new level
+// (block6_correct_kernel).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -93,7 +99,10 @@ struct H6Lane {
 // EVALUATE: grid (n_pad / (256 IPL), groups). Workgroup (b, g) sweeps the chunks of group g and
 // stores one partial per chunk and i-body: PA[c][i] = (ax, ay, az, sum mu / r),
 // PJ[c][i] = (jx, jy, jz, 0), PS[c][i] = (sx, sy, sz, 0).
-template <typename T, bool PHI, int IPL>
+// LIST (a block step's wide path): lane slot s owns body blk.list[s] (spare slots: a copy of the
+// last entry), the partials are stored per slot and i-blocks beyond n_act exit; the j loop, hence
+// a body's bits, is the same.
+template <typename T, bool PHI, int IPL, bool LIST = false>
 __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int gated) {
   constexpr int TB = Tile<T>::kBodies;
   using Lane = H6Lane<T, IPL>;
@@ -104,6 +113,13 @@ __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int 
   __shared__ __attribute__((aligned(16))) V4<T> ta[2][TB];
   if (gated && !a.ctrl->active) return;  // the run has reached t_end: a no-op step
   const int64_t ib = (int64_t)blockIdx.x * (kBlock * IPL);
+  int64_t n_act = 0;
+  if constexpr (LIST) {
+    const HermiteBlockCtrl* bc = a.blk.bc;
+    if (!bc->active || bc->path != HP_WIDE) return;
+    n_act = bc->n_act;
+    if (ib >= n_act) return;
+  }
   const int per = (a.n_chunks + (int)gridDim.y - 1) / (int)gridDim.y;
   const int c0 = (int)blockIdx.y * per;
   const int c1 = min(c0 + per, a.n_chunks);
@@ -119,7 +135,8 @@ __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int 
   Lane ln;
 #pragma unroll
   for (int k = 0; k < IPL; ++k) {
-    const int64_t row = ib + threadIdx.x + k * kBlock;
+    int64_t row = ib + threadIdx.x + k * kBlock;
+    if constexpr (LIST) row = a.blk.list[row < n_act ? row : n_act - 1];
     const V4<T> x = XP[row], v = VP[row], p = AP[row];
     H6Body<V>& b = ln.b[k / E];
     vset(b.x, k % E, x.x); vset(b.y, k % E, x.y); vset(b.z, k % E, x.z);
@@ -279,6 +296,186 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// Block time steps (fp64): body i stands at tb_i ticks and steps by 2^(L - level_i) ticks.
+
+// PREDICT-ALL + MARK: every real body from its own tb to t_next (x to h^5, v to h^4, a to h^3);
+// ghost rows zero; counts the due bodies of the workgroup for the compaction
+// (block_compact_kernel, nbody_hermite.hip).
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block6_predict_kernel(H6Args<T> a) {
+  __shared__ int cnt[kBlock / 64];
+  const HBlock& b = a.blk;
+  if (!b.bc->active) return;
+  const int L = b.bc->L;
+  const int64_t t_next = b.bc->t_ticks;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad: a multiple of 256)
+  V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp, ap = xp;
+  bool due = false;
+  if (i < a.n_real) {
+    due = body_due(b, i, L, t_next);
+    const H6Taylor<T> t = h6_taylor((T)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L));
+    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
+    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
+    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
+    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
+    const V4<T> sn = reinterpret_cast<const V4<T>*>(a.S)[i];
+    const V4<T> cr = reinterpret_cast<const V4<T>*>(a.C)[i];
+    T px, pv, pa;
+    h6_predict(t, x.x, v.x, ac.x, jk.x, sn.x, cr.x, px, pv, pa);
+    xp.x = px; vp.x = pv; ap.x = pa;
+    h6_predict(t, x.y, v.y, ac.y, jk.y, sn.y, cr.y, px, pv, pa);
+    xp.y = px; vp.y = pv; ap.y = pa;
+    h6_predict(t, x.z, v.z, ac.z, jk.z, sn.z, cr.z, px, pv, pa);
+    xp.z = px; vp.z = pv; ap.z = pa;
+    xp.w = x.w;
+  }
+  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
+  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
+  reinterpret_cast<V4<T>*>(a.AP)[i] = ap;
+  const int c = __popcll(__ballot(due));
+  if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) b.wgcount[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+// NARROW EVALUATE (n_act <= narrow_max): parallel over j, the geometry of hermite_narrow_kernel.
+// Grid (n_slices, passes): workgroup (s, y) takes the j rows of slice s and the groups y,
+// y + passes, ... of kNarrowGroup6 active bodies. The group's predicted rows are wave-uniform;
+// the lanes stride over the slice with coalesced 32-byte loads of (XP, VP, AP), each summing its
+// rows from zero in j order; the lanes are folded by a fixed tree (shuffle-down 32..1 in the
+// wave, then the four waves in order through LDS) and one partial (a, sum mu / r), j, s per
+// (slice, slot) is stored. Slice length and tree depend on n_pad only, so a body's bits depend
+// on neither the group size, its slot nor the other active bodies.
+template <typename T, bool PHI>
+__global__ __launch_bounds__(kBlock) void hermite6_narrow_kernel(H6Args<T> a) {
+  constexpr int G = kNarrowGroup6;
+  __shared__ T red[kBlock / 64][G][10];
+  const HBlock& b = a.blk;
+  if (!b.bc->active || b.bc->path != HP_NARROW) return;
+  const int n_act = min(b.bc->n_act, b.cap);
+  const int ngroups = (n_act + G - 1) / G;
+  const int64_t j0 = (int64_t)blockIdx.x * b.slice;
+  const int64_t j1 = min(j0 + (int64_t)b.slice, a.n_pad);
+  const V4<T>* XP = reinterpret_cast<const V4<T>*>(a.XP);
+  const V4<T>* VP = reinterpret_cast<const V4<T>*>(a.VP);
+  const V4<T>* AP = reinterpret_cast<const V4<T>*>(a.AP);
+  V4<T>* NA = reinterpret_cast<V4<T>*>(b.NA);
+  V4<T>* NJ = reinterpret_cast<V4<T>*>(b.NJ);
+  V4<T>* NS = reinterpret_cast<V4<T>*>(a.NS);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int g = blockIdx.y; g < ngroups; g += (int)gridDim.y) {
+    H6Body<T> st[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {  // (spare slots of the last group: a copy)
+      const int64_t row = b.list[min(g * G + k, n_act - 1)];
+      const V4<T> x = XP[row], v = VP[row], p = AP[row];
+      st[k].x = x.x; st[k].y = x.y; st[k].z = x.z;
+      st[k].u = v.x; st[k].v = v.y; st[k].w = v.z;
+      st[k].bx = p.x; st[k].by = p.y; st[k].bz = p.z;
+      h6reset(st[k]);
+    }
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += kBlock) {
+      const V4<T> xj = XP[j], vj = VP[j], aj = AP[j];
+#pragma unroll
+      for (int k = 0; k < G; ++k) h6interact<PHI>(st[k], xj, vj, aj, a.cut2, a.eps2);
+    }
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+      T v[10] = {st[k].ax, st[k].ay, st[k].az, st[k].ph, st[k].jx,
+                 st[k].jy, st[k].jz, st[k].sx, st[k].sy, st[k].sz};
+#pragma unroll
+      for (int c = 0; c < 10; ++c) {
+        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_down(v[c], off, 64);
+        if (lane == 0) red[wave][k][c] = v[c];
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < G && g * G + (int)threadIdx.x < n_act) {
+      const int k = threadIdx.x;
+      T v[10];
+#pragma unroll
+      for (int c = 0; c < 10; ++c)
+        v[c] = ((red[0][k][c] + red[1][k][c]) + red[2][k][c]) + red[3][k][c];
+      const V4<T> oa = {v[0], v[1], v[2], v[3]}, oj = {v[4], v[5], v[6], T(0)},
+                  os = {v[7], v[8], v[9], T(0)};
+      const int64_t o = (int64_t)blockIdx.x * b.cap + (g * G + k);
+      NA[o] = oa;
+      NJ[o] = oj;
+      NS[o] = os;
+    }
+    __syncthreads();
+  }
+}
+
+// REDUCE + CORRECT + NEW LEVEL, one thread per slot of the active list: the slice partials in
+// slice order (narrow) or the chunk partials in chunk order (wide), then the corrector over the
+// body's own h, c1 and the higher derivatives, the step the body wants (h6_dt) and the level rule
+// of order 4 (block_new_level). HM_OUT: the sums go to a_out / j_out / s_out [slot] and nothing
+// else is touched.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void block6_correct_kernel(H6Args<T> a) {
+  const HBlock& b = a.blk;
+  HermiteBlockCtrl* bc = b.bc;
+  if (!bc->active) return;
+  const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (s >= bc->n_act) return;
+  const bool narrow = bc->path == HP_NARROW;
+  const V4<T>* PA = reinterpret_cast<const V4<T>*>(narrow ? b.NA : (void*)a.PA);
+  const V4<T>* PJ = reinterpret_cast<const V4<T>*>(narrow ? b.NJ : (void*)a.PJ);
+  const V4<T>* PS = reinterpret_cast<const V4<T>*>(narrow ? (void*)a.NS : (void*)a.PS);
+  const int parts = narrow ? b.n_slices : a.n_chunks;
+  const int64_t stride = narrow ? (int64_t)b.cap : a.n_pad;
+  T m[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ph = 0;  // a1, j1, s1
+#pragma unroll 4
+  for (int c = 0; c < parts; ++c) {
+    const int64_t o = (int64_t)c * stride + s;
+    const V4<T> pa = PA[o], pj = PJ[o], ps = PS[o];
+    m[0][0] += pa.x; m[0][1] += pa.y; m[0][2] += pa.z; ph += pa.w;
+    m[1][0] += pj.x; m[1][1] += pj.y; m[1][2] += pj.z;
+    m[2][0] += ps.x; m[2][1] += ps.y; m[2][2] += ps.z;
+  }
+  V4<T> oa = {m[0][0], m[0][1], m[0][2], T(0)}, oj = {m[1][0], m[1][1], m[1][2], T(0)},
+        os = {m[2][0], m[2][1], m[2][2], T(0)};
+  if (a.mode == HM_OUT) {
+    oa.w = -ph;
+    reinterpret_cast<V4<T>*>(a.a_out)[s] = oa;
+    reinterpret_cast<V4<T>*>(a.j_out)[s] = oj;
+    reinterpret_cast<V4<T>*>(a.s_out)[s] = os;
+    return;
+  }
+  const int64_t i = b.list[s];
+  const int L = bc->L;
+  const int64_t t_next = bc->t_ticks;
+  const double dt_max = bc->dt_max;
+  const double hd = ticks_seconds(dt_max, t_next - b.tb[i], L);
+  const T h = (T)hd;
+  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
+  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
+  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
+  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
+  V4<T>* S = reinterpret_cast<V4<T>*>(a.S);
+  V4<T>* C = reinterpret_cast<V4<T>*>(a.C);
+  const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i], s0 = S[i];
+  const T xs[3] = {x.x, x.y, x.z}, vs[3] = {v.x, v.y, v.z};
+  const T as[3] = {a0.x, a0.y, a0.z}, js[3] = {j0.x, j0.y, j0.z}, ss[3] = {s0.x, s0.y, s0.z};
+  T x1[3], v1[3];
+  double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    h6_correct(h, xs[d], vs[d], as[d], js[d], ss[d], m[0][d], m[1][d], m[2][d], x1[d], v1[d]);
+    a1[d] = m[0][d]; j1[d] = m[1][d]; s1[d] = m[2][d];
+    h6_high(hd, as[d], js[d], ss[d], a1[d], j1[d], s1[d], c1[d], p1[d], a5[d]);
+  }
+  const V4<T> ox = {x1[0], x1[1], x1[2], x.w}, ov = {v1[0], v1[1], v1[2], T(0)};
+  const V4<T> oc = {(T)c1[0], (T)c1[1], (T)c1[2], T(0)};
+  X[i] = ox; V[i] = ov; A[i] = oa; J[i] = oj; S[i] = os; C[i] = oc;
+  b.tb[i] = t_next;
+  double want;
+  const bool rated = h6_dt(bc->eta, a1, j1, s1, c1, p1, a5, want);
+  b.level[i] = block_new_level(bc, b.level[i], rated, want, t_next, L, dt_max);
+}
+
+// ---------------------------------------------------------------------------------------
 // Host launchers: validate, compute the grid, dispatch.
 
 // The forms that are built: 1 or 2 i-bodies per lane in fp32, 1 in fp64.
@@ -324,6 +521,57 @@ hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s) {
   if (!args6_ok(a) || !a.ctrl || !a.wgmin) return hipErrorInvalidValue;
   hipLaunchKernelGGL(hermite6_reduce_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
                      0, s, a);
+  return hipGetLastError();
+}
+
+// ---- block steps (fp64) ---------------------------------------------------------------------
+static bool block6_ok(const H6Args<double>& a) {
+  const HBlock& b = a.blk;
+  return args6_ok(a) && b.bc && b.tb && b.level && b.list && b.wgcount && b.wgnext;
+}
+
+hipError_t launch_block6_predict(const H6Args<double>& a, hipStream_t s) {
+  if (!block6_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(block6_predict_kernel<double>, dim3((unsigned)(a.n_pad / kBlock)),
+                     dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_block6_narrow(const H6Args<double>& a, hipStream_t s) {
+  const HBlock& b = a.blk;
+  if (!block6_ok(a)) return hipErrorInvalidValue;
+  if (b.cap < 1) return hipSuccess;  // (narrow_max 0: every step is wide)
+  if (b.slice < kBlock || b.slice % kBlock || (int64_t)b.n_slices * b.slice < a.n_pad || !b.NA ||
+      !b.NJ || !a.NS || b.cap > a.n_pad)
+    return hipErrorInvalidValue;
+  const int groups = (b.cap + kNarrowGroup6 - 1) / kNarrowGroup6;
+  const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
+  if (a.phi)
+    hipLaunchKernelGGL((hermite6_narrow_kernel<double, true>), grid, dim3(kBlock), 0, s, a);
+  else
+    hipLaunchKernelGGL((hermite6_narrow_kernel<double, false>), grid, dim3(kBlock), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_block6_wide(const H6Args<double>& a, int ipl, int groups, hipStream_t s) {
+  if (!hermite6_ipl_ok(1, ipl) || !block6_ok(a) || !a.XP || !a.VP || !a.AP || !a.PA || !a.PJ ||
+      !a.PS)
+    return hipErrorInvalidValue;
+  const int g = groups < 1 ? 1 : groups > a.n_chunks ? a.n_chunks : groups;
+  const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)g);
+  if (a.phi)
+    hipLaunchKernelGGL((hermite6_eval_kernel<double, true, 1, true>), grid, dim3(kBlock), 0, s, a,
+                       0);
+  else
+    hipLaunchKernelGGL((hermite6_eval_kernel<double, false, 1, true>), grid, dim3(kBlock), 0, s, a,
+                       0);
+  return hipGetLastError();
+}
+
+hipError_t launch_block6_correct(const H6Args<double>& a, hipStream_t s) {
+  if (!block6_ok(a)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(block6_correct_kernel<double>, dim3((unsigned)(a.n_pad / kBlock)),
+                     dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

@@ -241,6 +241,12 @@ int gs_cpu_accjerksnap_f64(const double* X4, const double* V4, const double* A4,
 int gs_cpu_accjerksnap_f32(const float* X4, const float* V4, const float* A4, int64_t n_real,
                            int64_t i0, int64_t i1, int32_t chunk, float cut2, float eps2,
                            float* acc4, float* jerk4, float* snap4);
+// The same for listed bodies (an order-6 block step's active set): row k of the outputs is
+// body idx[k]. fp64 only: order 6 runs its block steps in fp64.
+int gs_cpu_accjerksnap_idx_f64(const double* X4, const double* V4, const double* A4,
+                               int64_t n_real, const int32_t* idx, int64_t n_idx, int32_t chunk,
+                               double cut2, double eps2, double* acc4, double* jerk4,
+                               double* snap4);
 // One 6th-order step of size h on the n_real bodies, in place: predict (x, v, a), evaluate,
 // correct; A4, J4, S4, C4 carry a, j, snap and crackle from step to step (scratch: 6 arrays of
 // n_real * 4: the predicted x, v, a rows, then a1, j1, s1). *dt_min_out (if given and eta > 0)
@@ -464,7 +470,8 @@ int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx
 //   dt_i = eta ((|a||s| + |j|^2) / (|c||a^(5)| + |a^(4)|^2))^(1/6),
 // eta linear: useful values are 0.2 to 0.5), fp32 or fp64, one rank. gs_hermite_set_order(h, 6)
 // refuses GS_MIXED, nranks > 1, block steps and collisions, and once the order is 6
-// gs_hermite_set_block, gs_hermite_set_collisions and the gs_hermite_group_* calls refuse. Call
+// gs_hermite_set_block, gs_hermite_set_collisions and the gs_hermite_group_* calls refuse.
+// Block steps of order 6 are an explicit choice, gs_hermite_set_block6 below. Call
 // it before the state is set (like gs_hermite_set_block); order 4 frees the extra arrays again.
 // cfg's ipl: 0 auto, 1, or 2 for fp32 (gs_hermite6_ipl_ok). A run starts with c = 0 and two
 // evaluate passes: with ap = 0 for a and j, then with ap = a for s.
@@ -484,6 +491,19 @@ int gs_hermite_get_carried6(gs_hermite* h, double* snap, double* crackle);
 // (ax, ay, az, phi), (jx, jy, jz, 0) and (sx, sy, sz, 0) of the current (x, v), the snap at the
 // acceleration of that state, through the step's own kernel (any pointer may be NULL).
 int gs_hermite_derivs6(gs_hermite* h, double* acc4, double* jerk4, double* snap4);
+// Block steps of an order-6 engine, fp64 only (in fp32 pair arithmetic, also with fp64 state and
+// sums, the order-6 step criterion collapses: docs/DESIGN.md section 21): gs_hermite_set_block for
+// order 6, with its arguments and conditions (one rank, eta > 0, t_end a multiple of dt); off (on
+// = 0) before the order changes again. The block state, tuning and status calls are order 4's.
+int gs_hermite_set_block6(gs_hermite* h, int32_t on, int32_t max_level);
+// Order 6 in block mode: gs_hermite_derivs_active / gs_hermite_time_active with the snap. One
+// pass at the rows (x, v, carried a) of the current state, so the snap is taken at the carried
+// acceleration; row k belongs to idx[k], path as for order 4.
+int gs_hermite_derivs_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                              double* acc4, double* jerk4, double* snap4);
+int gs_hermite_time_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                            int32_t reps, double* ms, double* acc4, double* jerk4,
+                            double* snap4);
 
 // ---------------------------------------------------------------- k nearest neighbours
 // (nbody_knn.hip; the Casertano & Hut local density and the cluster read-outs rest on it.)

@@ -59,6 +59,41 @@ struct HBlock {
 };
 
 constexpr int kNarrowGroup = 4;  // active bodies a narrow workgroup carries per pass
+// ... and of order 6 (nbody_hermite6.hip), whose bodies hold 10 fp64 sums and 9 fp64 row values
+// each: the most that leaves the kernel without scratch (docs/DESIGN.md section 23).
+constexpr int kNarrowGroup6 = 2;
+
+#ifdef __HIPCC__
+// The arithmetic every block-step kernel of both orders shares.
+// Seconds of a span of ticks: dt_max ticks 2^-L in fp64 (the run's dtype takes a cast of it).
+__device__ __forceinline__ double ticks_seconds(double dt_max, int64_t ticks, int L) {
+  return dt_max * ldexp((double)ticks, -L);
+}
+
+__device__ __forceinline__ bool body_due(const HBlock& b, int64_t i, int L, int64_t t_next) {
+  return b.tb[i] + ((int64_t)1 << (L - b.level[i])) == t_next;
+}
+
+// The level of an active body after its step to t_next from level k, where its criterion gave
+// `want` (rated): any number of halvings (capped at L, a clamp is counted), at most one doubling
+// and only where t_next allows the doubled step. Records the deepest level.
+__device__ __forceinline__ int block_new_level(HermiteBlockCtrl* bc, int k, bool rated,
+                                               double want, int64_t t_next, int L,
+                                               double dt_max) {
+  if (rated) {
+    const double dtk = ldexp(dt_max, -k);
+    if (want < dtk) {
+      while (k < L && ldexp(dt_max, -k) > want) ++k;
+      if (ldexp(dt_max, -k) > want) atomicAdd(&bc->level_clamped, 1ull);
+    } else if (k > 0 && want >= 2.0 * dtk &&
+               (t_next & (((int64_t)1 << (L - k + 1)) - 1)) == 0) {
+      --k;
+    }
+  }
+  if (k > bc->level_max) atomicMax(&bc->level_max, k);
+  return k;
+}
+#endif
 
 // What the reduce kernel does with the summed derivatives.
 enum { HM_STEP = 0,   // corrector: x, v, a, j <- corrected; per-workgroup min of dt_i
@@ -133,6 +168,10 @@ template <typename T, typename S>
 hipError_t launch_block_next(const HArgs<T, S>& a, hipStream_t s);
 template <typename T, typename S>
 hipError_t launch_block_predict(const HArgs<T, S>& a, hipStream_t s);
+// The compaction alone (launch_block_predict ends with it): it reads blk and n_real only, so the
+// order-6 chain runs it after its own predict-all + mark.
+template <typename T, typename S>
+hipError_t launch_block_compact(const HArgs<T, S>& a, hipStream_t s);
 template <typename T, typename S>
 hipError_t launch_block_narrow(const HArgs<T, S>& a, hipStream_t s);
 template <typename T, typename S>
@@ -170,6 +209,10 @@ struct H6Args {
   int32_t mode;
   int32_t phi;
   T cut2, eps2;
+  // Block steps (fp64; all null otherwise; last: the fields above keep their offsets). The
+  // narrow partials are blk.NA, blk.NJ and NS, [n_slices][cap] rows of 4 each.
+  HBlock blk;
+  T* NS;
 };
 
 // ipl values the order-6 evaluate kernel is compiled for (fp32: 1, 2; fp64: 1).
@@ -183,5 +226,14 @@ hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool ga
                                 hipStream_t s);
 template <typename T>
 hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s);
+// Order-6 block-step chain (fp64 only). The next-time minima, the control, the compaction and
+// the start are order 4's kernels (launch_block_next, _compact, _init on an HArgs that carries
+// blk, n_real, n_pad, A and J); these are the four that differ, enqueued in order 4's order:
+// predict-all + mark, [compact,] narrow evaluate, wide (gathered) evaluate, reduce + correct +
+// new level (mode HM_STEP or HM_OUT).
+hipError_t launch_block6_predict(const H6Args<double>& a, hipStream_t s);
+hipError_t launch_block6_narrow(const H6Args<double>& a, hipStream_t s);
+hipError_t launch_block6_wide(const H6Args<double>& a, int ipl, int groups, hipStream_t s);
+hipError_t launch_block6_correct(const H6Args<double>& a, hipStream_t s);
 
 }  // namespace gs

@@ -51,8 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="hermite: 4 (Makino & Aarseth 1992) or 6 (Nitadori & Makino 2008: one "
                         "acceleration+jerk+snap pass per step). Order 6 takes --eta linearly in "
                         "its criterion: useful values are 0.2 to 0.5, not the 0.02 of order 4. "
-                        "It runs one shared step in fp32 or fp64 on one rank (not with "
-                        "--block-steps, --dtype mixed, --collisions or --gpus > 1). Adaptive "
+                        "It runs on one rank in fp32 or fp64 (not with --dtype mixed, "
+                        "--collisions or --gpus > 1), with one shared step or, in fp64 only, "
+                        "with --block-steps6 (--block-steps is order 4's and is refused). Adaptive "
                         "runs of systems with a wide range of timescales want --dtype fp64: "
                         "with fp32 rows the criterion's 5th derivative is rounding noise once "
                         "the shared step is far below a body's own timescale, and the step "
@@ -62,7 +63,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--block-steps", dest="block_steps", action="store_true",
                    default=d.block_steps,
                    help="hermite: individual block time steps dt 2^-k per body (needs --eta > 0; "
-                        "--steps then counts macro steps of --dt)")
+                        "--steps then counts macro steps of --dt; order 4)")
+    p.add_argument("--block-steps6", dest="block_steps6", action="store_true",
+                   default=d.block_steps6,
+                   help="hermite --hermite-order 6: block time steps under the order-6 predictor, "
+                        "corrector and criterion (--dtype fp64 only, --eta > 0, --max-level; "
+                        "--steps counts macro steps of --dt)")
     p.add_argument("--collisions", choices=["off", "detect", "merge"], default=d.collisions,
                    help="hermite: off | detect: every body's nearest neighbour by "
                         "q = r^2 - (R_i + R_j)^2 from the force kernel, closest approaches and "
@@ -164,6 +170,7 @@ def config_from_args(a: argparse.Namespace) -> SimConfig:
                      seed=a.seed, G=a.G, cutoff=a.cutoff, softening=a.softening,
                      cutoff_mode=a.cutoff_mode, integrator=a.integrator, eta=a.eta,
                      t_end=a.t_end, block_steps=a.block_steps, max_level=a.max_level,
+                     block_steps6=a.block_steps6,
                      collisions=a.collisions, body_density=a.body_density,
                      hermite_order=a.hermite_order, kernel=a.kernel,
                      mode=a.mode, ipl=a.ipl, chunk=a.chunk, graph=a.graph, graph_comm=a.graph_comm,

@@ -44,6 +44,9 @@ class SimConfig:
     block_steps: bool = False     # hermite: individual block time steps dt 2^-k per body (needs
                                   # eta > 0); `steps` then counts macro steps of dt
     max_level: int = 24           # hermite block steps: deepest level k (0..40)
+    block_steps6: bool = False    # hermite order 6: block time steps under the order-6 predictor,
+                                  # corrector and criterion (fp64 only; block_steps itself stays
+                                  # order 4's and keeps refusing order 6)
     collisions: str = "off"       # hermite: off | detect (nearest neighbours, closest approaches
                                   # and overlaps recorded and reported) | merge (overlapping
                                   # bodies become one at the next synchronised state)
@@ -133,7 +136,7 @@ class SimConfig:
         if self.dtype == "mixed" and self.integrator != "hermite":
             raise ValueError("dtype mixed (fp64 state, double-single fp32 pair arithmetic) "
                              "belongs to integrator hermite")
-        if self.integrator != "hermite" and self.block_steps:
+        if self.integrator != "hermite" and self.block_mode:
             raise ValueError("block_steps belongs to integrator hermite")
         if self.collisions not in COLLISIONS:
             raise ValueError(f"collisions must be one of {COLLISIONS}")
@@ -142,7 +145,7 @@ class SimConfig:
             raise ValueError("collisions and body_density belong to integrator hermite")
         if self.body_density is not None and not self.body_density > 0:
             raise ValueError("body_density must be > 0")
-        if self.block_steps:
+        if self.block_mode:
             if not self.eta > 0:
                 raise ValueError("block steps need eta > 0")
             if not 0 <= self.max_level <= 40:
@@ -156,7 +159,12 @@ class SimConfig:
             if self.integrator != "hermite":
                 raise ValueError("hermite_order belongs to integrator hermite")
             if self.block_steps:
-                raise ValueError("hermite order 6 has no block steps (--block-steps): a follow-up")
+                raise ValueError("hermite order 6 has no block steps under --block-steps: its own "
+                                 "are --block-steps6 (block_steps6), with --dtype fp64")
+            if self.block_steps6 and self.dtype == "fp32":
+                raise ValueError("hermite order 6 runs block steps (--block-steps6) in fp64 only "
+                                 "(--dtype fp64): fp32 pair arithmetic collapses its step "
+                                 "criterion")
             if self.dtype == "mixed":
                 raise ValueError("hermite order 6 has no mixed precision (--dtype mixed): fp32 or "
                                  "fp64")
@@ -166,6 +174,9 @@ class SimConfig:
                 raise ValueError("hermite order 6 runs on one rank: not with --gpus > 1")
             if self.ipl == 4 or (self.ipl == 2 and self.dtype == "fp64"):
                 raise ValueError("hermite order 6: ipl must be 0, 1 (or 2 for fp32)")
+        if self.block_steps6 and self.hermite_order != 6:
+            raise ValueError("block_steps6 (--block-steps6) belongs to hermite_order 6; order 4 "
+                             "takes --block-steps")
         if self.integrator == "hermite":
             if not self.eta >= 0:
                 raise ValueError("eta must be >= 0")
@@ -206,6 +217,11 @@ class SimConfig:
         if self.cutoff < 0 or self.softening < 0:
             raise ValueError("cutoff and softening must be >= 0")
         return self
+
+    @property
+    def block_mode(self) -> bool:
+        """Block time steps are on: block_steps (order 4) or block_steps6 (order 6)."""
+        return bool(self.block_steps or self.block_steps6)
 
     def replace(self, **kw) -> "SimConfig":
         return dataclasses.replace(self, **kw)

@@ -155,6 +155,9 @@ def cpu_lib():
             _sig(lib, f"gs_cpu_accjerksnap_{t}", c_int32, [P, P, P, L, L, L, I, T, T, P, P, P])
             _sig(lib, f"gs_cpu_hermite6_step_{t}", c_int32,
                  [P, P, P, P, P, P, P, L, I, c_double, T, T, c_double, _PD])
+        # (order 6 runs its block steps in fp64 only; optional: A/B runs load older builds)
+        _sig(lib, "gs_cpu_accjerksnap_idx_f64", c_int32,
+             [_PD, _PD, _PD, L, PI32, L, I, c_double, c_double, _PD, _PD, _PD], optional=True)
         _sig(lib, "gs_cpu_accel_abs_f64", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
                                                     c_double, _PD])
         _sig(lib, "gs_cpu_accel_abs_ld", c_int32, [_PD, c_int64, c_int64, c_int64, c_double,
@@ -267,6 +270,12 @@ def hip_lib():
                                                      c_double, c_double, c_double])
         _sig(lib, "gs_hermite_get_carried6", c_int32, [S, _PD, _PD])
         _sig(lib, "gs_hermite_derivs6", c_int32, [S, _PD, _PD, _PD])
+        # (optional: A/B runs load the builds of earlier trees, which have none of them)
+        _sig(lib, "gs_hermite_set_block6", c_int32, [S, c_int32, c_int32], optional=True)
+        _sig(lib, "gs_hermite_derivs_active6", c_int32, [S, PI, c_int32, c_int32, _PD, _PD, _PD],
+             optional=True)
+        _sig(lib, "gs_hermite_time_active6", c_int32, [S, PI, c_int32, c_int32, c_int32, _PD,
+                                                       _PD, _PD, _PD], optional=True)
         _sig(lib, "gs_hip_knn", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,
                                           c_int32, _PD, PI32])
         _sig(lib, "gs_hip_knn_time", c_int32, [_PD, c_int64, c_int32, c_int32, c_int32, c_int32,

@@ -842,3 +842,124 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
     if near is not None and record is not None:
         near.export(record)
     return x, v, lev.copy(), log, clamped
+
+
+# ---- 6th-order Hermite with individual block time steps --------------------------------------
+def acc_jerk_snap_rows(pos, vel, acc_in, mass, idx, G: float = G_SI, cutoff: float = 1e-10,
+                       softening: float = 0.0):
+    """acc_jerk_snap() of the bodies `idx` only, against all bodies: (len(idx), 3) each (the
+    same terms in the same column order, so the rows are those of the full call bit for bit)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    vel = np.asarray(vel, dtype=np.float64)
+    ain = np.asarray(acc_in, dtype=np.float64)
+    mu = G * np.asarray(mass, dtype=np.float64)
+    idx = np.asarray(idx, dtype=np.int64)
+    acc, jerk, snap = (np.zeros((len(idx), 3)) for _ in range(3))
+    for b0 in range(0, len(idx), 256):
+        rows = idx[b0:b0 + 256]
+        d = pos[None, :, :] - pos[rows, None, :]
+        w = vel[None, :, :] - vel[rows, None, :]
+        q = ain[None, :, :] - ain[rows, None, :]
+        r2 = (d * d).sum(-1) + softening * softening
+        ok = r2 >= cutoff * cutoff
+        inv = np.zeros_like(r2)
+        inv[ok] = 1.0 / np.sqrt(r2[ok])
+        inv2 = inv * inv
+        s = (mu[None, :] * inv * inv2)[:, :, None]
+        al = ((d * w).sum(-1) * inv2)[:, :, None]
+        be = (((w * w).sum(-1) + (d * q).sum(-1)) * inv2)[:, :, None] + al * al
+        A = s * d
+        Jt = s * w - 3.0 * al * A
+        acc[b0:b0 + 256] = A.sum(1)
+        jerk[b0:b0 + 256] = Jt.sum(1)
+        snap[b0:b0 + 256] = (s * q - 6.0 * al * Jt - 3.0 * be * A).sum(1)
+    return acc, jerk, snap
+
+
+def hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, h, eta):
+    """hermite6_dt()'s criterion per body, h (m,) each body's own step: (dt_want, valid) with
+    valid False where the ratio is zero or not finite."""
+    h = np.asarray(h, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        c1, p1, a5 = hermite6_high(a0, j0, s0, a1, j1, s1, h)
+        nrm = lambda y: np.sqrt((y * y).sum(1))  # noqa: E731
+        ratio = (nrm(a1) * nrm(s1) + nrm(j1) ** 2) / (nrm(c1) * nrm(a5) + nrm(p1) ** 2)
+        dt = eta * ratio ** (1.0 / 6.0)
+    return dt, (ratio > 0) & np.isfinite(dt)
+
+
+def simulate_hermite6_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI, cutoff=1e-10,
+                            softening=0.0, check=None, levels=None, body_times=None, stats=None):
+    """6th-order Hermite (simulate_hermite6) with the individual block time steps of
+    simulate_hermite_block: body i carries x, v, a, j, s, c, a time in ticks of dt 2^-max_level
+    and a level k (step dt 2^-k). A run starts with hermite6_start (c = 0) and the levels of
+    block_first_levels, the first-step rule of the shared order-6 run. A block step predicts
+    every body from its own time over its own h (x to h^5, v to h^4, a to h^3), evaluates a1, j1,
+    s1 of the due bodies against all predicted rows, corrects them over their own h, forms c1 and
+    the step each wants (hermite6_dt_bodies) and applies the level rule of order 4
+    (block_new_levels). t_end, check, levels, body_times, stats and the return value are those of
+    simulate_hermite_block; there are no sources and no collisions."""
+    if not eta > 0:
+        raise ValueError("block steps need eta > 0")
+    L = int(max_level)
+    if not 0 <= L <= 40:
+        raise ValueError("max_level must be in 0..40")
+    macro = int(round(t_end / dt))
+    if macro * dt != t_end:
+        raise ValueError("t_end must be a whole multiple of dt")
+    x = np.array(pos, dtype=np.float64, copy=True)
+    v = np.array(vel, dtype=np.float64, copy=True)
+    n = x.shape[0]
+    mass = np.asarray(mass, dtype=np.float64)
+    a, j, s = hermite6_start(x, v, mass, G, cutoff, softening)
+    c = np.zeros_like(a)
+    tb = (np.zeros(n, dtype=np.int64) if body_times is None else
+          np.array(body_times, dtype=np.int64))
+    lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
+           np.array(levels, dtype=np.int32))
+    if lev.shape != (n,) or tb.shape != (n,) or (lev < 0).any() or (lev > L).any() or \
+            (tb < 0).any() or (tb % (np.int64(1) << (L - lev).astype(np.int64))).any():
+        raise ValueError("block state: level out of 0..max_level, or a body time that is no "
+                         "multiple of its step")
+    lean = float("inf")
+    if stats is not None and levels is None:
+        an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            first = 0.5 * eta * an / jn
+        lean = level_lean(first, (jn > 0) & np.isfinite(first), dt)
+    level_max, active = int(lev.max()) if n else 0, []
+    end = macro << L
+    log, clamped = [], 0
+    while tb.min() < end:
+        stp = np.int64(1) << (L - lev).astype(np.int64)
+        t_next = int((tb + stp).min())
+        act = np.nonzero(tb + stp == t_next)[0]
+        h = dt * np.ldexp((t_next - tb).astype(np.float64), -L)
+        hc = h[:, None]
+        h2, h3, h4, h5 = (hc * hc) / 2, (hc * hc * hc) / 6, (hc * hc * hc * hc) / 24, \
+            (hc * hc * hc * hc * hc) / 120
+        xp = x + (v * hc + (a * h2 + (j * h3 + (s * h4 + c * h5))))
+        vp = v + (a * hc + (j * h2 + (s * h3 + c * h4)))
+        ap = a + (j * hc + (s * h2 + c * h3))
+        a1, j1, s1 = acc_jerk_snap_rows(xp, vp, ap, mass, act, G, cutoff, softening)
+        ha = hc[act]
+        hh, h10, h120 = ha / 2, (ha * ha) / 10, (ha * ha * ha) / 120
+        a0, j0, s0, v0 = a[act], j[act], s[act], v[act]
+        v1 = v0 + ((a0 + a1) * hh + ((j0 - j1) * h10 + (s0 + s1) * h120))
+        x[act] = x[act] + ((v0 + v1) * hh + ((a0 - a1) * h10 + (j0 + j1) * h120))
+        want, valid = hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, h[act], eta)
+        c[act] = hermite6_high(a0, j0, s0, a1, j1, s1, h[act])[0]
+        v[act], a[act], j[act], s[act] = v1, a1, j1, s1
+        tb[act] = t_next
+        lev[act], hit = block_new_levels(lev[act], want, valid, t_next, dt, L)
+        clamped += int(hit.sum())
+        log.append((t_next, int(len(act))))
+        if stats is not None:
+            lean = min(lean, level_lean(want, valid, dt))
+            level_max = max(level_max, int(lev[act].max()))
+            active.append(act)
+        if check is not None:
+            check(tb, lev)
+    if stats is not None:
+        stats.update(active=active, lean=lean, level_max=level_max)
+    return x, v, lev.copy(), log, clamped

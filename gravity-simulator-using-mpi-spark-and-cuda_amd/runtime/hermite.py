@@ -30,7 +30,9 @@ crackle c, the predictor runs to h^5 in x and also predicts a, the one evaluatio
 and s1 at (xp, vp, ap), and the corrector is v1 = v + (a + a1) h/2 - (j1 - j) h^2/10 +
 (s + s1) h^3/120, x1 likewise from v, a, j (ops/oracle.py simulate_hermite6). eta enters its step
 criterion linearly (0.2 to 0.5). load() then also takes snap and crackle, carried() returns
-(acc, jerk, snap, crackle) and derivs() (a4, j4, s4). One shared step, fp32 or fp64, one rank.
+(acc, jerk, snap, crackle) and derivs() (a4, j4, s4). fp32 or fp64, one rank; one shared step, or
+(fp64 only, cfg.block_steps6) block mode: the block step below with the order-6 predictor, evaluation, corrector
+and criterion (ops/oracle.py simulate_hermite6_block).
 
 Block mode (cfg.block_steps; Makino 1991): body i steps by dt 2^-k_i, time is an integer count
 of ticks of dt 2^-max_level, and a block step predicts every body to the earliest due time,
@@ -125,10 +127,11 @@ class HermiteHipEngine:
             _native.check(self.lib, self.lib.gs_hermite_set_order(self._h, 6), "set_order")
             _native.check(self.lib, self.lib.gs_hermite_layout(self._h, ctypes.byref(L)), "layout")
             self.native_layout = L.as_dict()
-        self.block = bool(cfg.block_steps)
-        if self.block:
-            _native.check(self.lib, self.lib.gs_hermite_set_block(self._h, 1, int(cfg.max_level)),
-                          "set_block")
+        self.block = cfg.block_mode
+        if self.block:  # (order 6: its own entry; gs_hermite_set_block refuses it)
+            set_block = self.lib.gs_hermite_set_block6 if cfg.block_steps6 else \
+                self.lib.gs_hermite_set_block
+            _native.check(self.lib, set_block(self._h, 1, int(cfg.max_level)), "set_block")
         self.collisions = cfg.collisions != "off"
         if self.collisions:
             _native.check(self.lib, self.lib.gs_hermite_set_collisions(
@@ -326,7 +329,15 @@ class HermiteHipEngine:
     def derivs(self, active=None, path: Optional[str] = None) -> tuple[np.ndarray, np.ndarray]:
         """(n, 4) (ax, ay, az, phi) and (jx, jy, jz, 0) of the current (x, v), through the
         step's own kernel. Block mode, active = body indices: their rows only, through the block
-        path's evaluate and reduce (path "narrow", "wide" or None: by narrow_max)."""
+        path's evaluate and reduce (path "narrow", "wide" or None: by narrow_max). Order 6:
+        (a4, j4, s4), for active bodies in one pass at the rows (x, v, carried a)."""
+        if active is not None and self.order == 6:
+            idx = np.ascontiguousarray(active, dtype=np.int32)
+            a4, j4, s4 = (np.zeros((len(idx), 4)) for _ in range(3))
+            _native.check(self.lib, self.lib.gs_hermite_derivs_active6(
+                self._h, _i32ptr(idx), len(idx), PATH_IDS[path], _native.dptr(a4),
+                _native.dptr(j4), _native.dptr(s4)), "derivs_active6")
+            return a4, j4, s4
         if active is not None:
             idx = np.ascontiguousarray(active, dtype=np.int32)
             a4, j4 = np.zeros((len(idx), 4)), np.zeros((len(idx), 4))
@@ -350,6 +361,11 @@ class HermiteHipEngine:
         events around `reps` back-to-back launches)."""
         idx = np.ascontiguousarray(active, dtype=np.int32)
         ms = ctypes.c_double(0.0)
+        if self.order == 6:
+            _native.check(self.lib, self.lib.gs_hermite_time_active6(
+                self._h, _i32ptr(idx), len(idx), PATH_IDS[path], int(reps), ctypes.byref(ms),
+                None, None, None), "time_active6")
+            return ms.value
         _native.check(self.lib, self.lib.gs_hermite_time_active(
             self._h, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), len(idx), PATH_IDS[path],
             int(reps), ctypes.byref(ms), None, None), "time_active")
@@ -514,10 +530,11 @@ class HermiteCpuEngine:
         if six:
             self.S, self.C = self._rows[2:]
             self._ajs = _native.cpu_entry(self.lib, "accjerksnap", cfg.dtype)[0]
+            self._ajs_idx = self.lib.gs_cpu_accjerksnap_idx_f64  # (block steps: fp64 only)
         self._accjerk, self._accjerk_idx, self._first_dt, self._nn, self._nn_idx = (
             _native.cpu_entry(self.lib, stem, cfg.dtype)[0]
             for stem in ("accjerk", "accjerk_idx", "hermite_first_dt", "nn", "nn_idx"))
-        self.block = bool(cfg.block_steps)
+        self.block = cfg.block_mode
         self.L = int(cfg.max_level)
         self.tb = np.zeros(n, dtype=np.int64)       # body times [ticks of dt 2^-L]
         self.lev = np.zeros(n, dtype=np.int32)
@@ -692,6 +709,45 @@ class HermiteCpuEngine:
         self.body_steps += len(act)
         self.block_log.append((t_next, len(act)))
 
+    def _block_step6(self) -> None:
+        """One block step of order 6 (the rules of oracle.simulate_hermite6_block; fp64)."""
+        from ..ops import oracle
+
+        cfg, L, n = self.cfg, self.L, self.cfg.n
+        stp = np.int64(1) << (L - self.lev).astype(np.int64)
+        t_next = int((self.tb + stp).min())
+        act = np.nonzero(self.tb + stp == t_next)[0]
+        hd = cfg.dt * np.ldexp((t_next - self.tb).astype(np.float64), -L)
+        h = hd[:, None]
+        h2, h3, h4, h5 = (h * h) / 2, (h * h * h) / 6, (h * h * h * h) / 24, \
+            (h * h * h * h * h) / 120
+        x, v, a, j, s, c = (y[:, :3] for y in (self.X, self.V, self.A, self.J, self.S, self.C))
+        XP, VP, AP = self.X.copy(), np.zeros_like(self.V), np.zeros_like(self.V)
+        XP[:, :3] = x + (v * h + (a * h2 + (j * h3 + (s * h4 + c * h5))))
+        VP[:, :3] = v + (a * h + (j * h2 + (s * h3 + c * h4)))
+        AP[:, :3] = a + (j * h + (s * h2 + c * h3))
+        idx = np.ascontiguousarray(act, dtype=np.int32)
+        a4, j4, s4 = (np.zeros((len(idx), 4)) for _ in range(3))
+        rc = self._ajs_idx(self._ptr(XP), self._ptr(VP), self._ptr(AP), n, _i32ptr(idx), len(idx),
+                           self.layout.chunk, self._cut2, self._eps2, self._ptr(a4),
+                           self._ptr(j4), self._ptr(s4))
+        _native.check(self.lib, rc, "cpu accjerksnap_idx")
+        a1, j1, s1 = a4[:, :3], j4[:, :3], s4[:, :3]
+        ha = h[act]
+        hh, h10, h120 = ha / 2, (ha * ha) / 10, (ha * ha * ha) / 120
+        a0, j0, s0, v0 = a[act], j[act], s[act], v[act]
+        v1 = v0 + ((a0 + a1) * hh + ((j0 - j1) * h10 + (s0 + s1) * h120))
+        self.X[act, :3] = x[act] + ((v0 + v1) * hh + ((a0 - a1) * h10 + (j0 + j1) * h120))
+        want, valid = oracle.hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, hd[act], cfg.eta)
+        self.C[act, :3] = oracle.hermite6_high(a0, j0, s0, a1, j1, s1, hd[act])[0]
+        self.V[act, :3], self.A[act, :3], self.J[act, :3], self.S[act, :3] = v1, a1, j1, s1
+        self.tb[act] = t_next
+        self.lev[act], hit = oracle.block_new_levels(self.lev[act], want, valid, t_next, cfg.dt, L)
+        self.level_clamped += int(hit.sum())
+        self.level_max = max(self.level_max, int(self.lev.max()))
+        self.body_steps += len(act)
+        self.block_log.append((t_next, len(act)))
+
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
              dt_next: Optional[float] = None, dt_min: Optional[float] = None,
              levels=None, body_times=None, snap=None, crackle=None) -> None:
@@ -733,7 +789,7 @@ class HermiteCpuEngine:
                     return
                 macro = int(self.tb.min()) >> self.L
                 while int(self.tb.min()) < (macro + 1) << self.L:
-                    self._block_step()
+                    self._block_step6() if self.order == 6 else self._block_step()
                 self.t = cfg.dt * (macro + 1)
                 self.dt_last = cfg.dt
                 self.k += 1

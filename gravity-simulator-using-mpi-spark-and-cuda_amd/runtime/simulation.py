@@ -196,20 +196,15 @@ class Simulation:
                 self.engine.load(c.bodies, c.extra["acc"], c.extra["jerk"],
                                  t=float(c.meta.get("time", 0.0)), dt_next=c.meta.get("dt_next"),
                                  dt_min=c.meta.get("dt_min"), snap=c.extra["snap"],
-                                 crackle=c.extra["crackle"])
+                                 crackle=c.extra["crackle"], **self._resumed_levels(c))
             elif self.hermite and same_order and cfg.hermite_order == 4 and \
                     c.meta.get("integrator") == "hermite" and \
                     "acc" in c.extra and "jerk" in c.extra:
                 # the carried a, j (evaluated at the last predicted state) and the step size
                 # the criterion chose: the run continues bit for bit
-                kw = {}
-                if cfg.block_steps and c.meta.get("block_steps") and "level" in c.extra and \
-                        int(c.meta.get("max_level", -1)) == cfg.max_level:
-                    kw["levels"] = c.extra["level"][:, int(c.meta.get("level_column", 0))]
-                # (a shared-step checkpoint resumed with block steps starts the levels afresh)
                 self.engine.load(c.bodies, c.extra["acc"], c.extra["jerk"],
                                  t=float(c.meta.get("time", 0.0)), dt_next=c.meta.get("dt_next"),
-                                 dt_min=c.meta.get("dt_min"), **kw)
+                                 dt_min=c.meta.get("dt_min"), **self._resumed_levels(c))
             elif self.hermite:
                 self.engine.load(c.bodies, t=float(c.meta.get("time", 0.0)))  # a, j afresh
             else:
@@ -234,6 +229,15 @@ class Simulation:
         elif cfg.integrator in ("kd", "hermite") and self.staggered:
             self._half_kick(+1.0)
             self.staggered = False
+
+    def _resumed_levels(self, c) -> dict:
+        """load()'s levels of a block-step run resumed from a block-step checkpoint of the same
+        max_level (a shared-step checkpoint resumed with block steps starts the levels afresh)."""
+        cfg = self.cfg
+        if cfg.block_mode and c.meta.get("block_steps") and "level" in c.extra and \
+                int(c.meta.get("max_level", -1)) == cfg.max_level:
+            return {"levels": c.extra["level"][:, int(c.meta.get("level_column", 0))]}
+        return {}
 
     def _engine_cfg(self) -> SimConfig:
         """The engine's configuration: cfg, but for the bodies a resumed merge run has left.
@@ -424,7 +428,7 @@ class Simulation:
                 col[:, 0], col[:, 1] = b.radii(), self.ids
                 extra["collide"] = col
                 meta.update(collide_columns=["radius", "id"], mergers=self.mergers)
-            if cfg.block_steps:  # (a synchronised state: every body time is st.time)
+            if cfg.block_mode:  # (a synchronised state: every body time is st.time)
                 lev = np.zeros((b.n, 3))
                 lev[:, 0] = self.engine.levels()
                 extra["level"] = lev
@@ -463,7 +467,7 @@ class Simulation:
         if merging and st0.overlaps:  # (bodies that overlap as the run starts: merged at once)
             self._merge(st0)
         polled = 0
-        poll = 1 if cfg.block_steps else 32  # (a macro step waits for its block steps anyway)
+        poll = 1 if cfg.block_mode else 32  # (a macro step waits for its block steps anyway)
         comm.barrier(self.dist)
         t0 = time.perf_counter()
         s = 0
@@ -551,7 +555,7 @@ class Simulation:
             steps = self._steps_gone - steps_gone0 + st.steps - st0.steps
             herm = dict(time_reached=st.time, steps_taken=steps, hermite_order=cfg.hermite_order,
                         dt_min=st.dt_min if np.isfinite(st.dt_min) else None)
-            if cfg.block_steps:
+            if cfg.block_mode:
                 body = gone["body_steps"] + st.body_steps - st0.body_steps
                 herm.update(block_steps=gone["block_steps"] + st.block_steps - st0.block_steps,
                             body_steps=body,
