@@ -19,6 +19,9 @@ steps under three narrow_max; the shared step on 2 and 3 virtual ranks (n = 3000
 Order 6 (fp32, fp64): derivs() (a4, j4, s4) at the same n and, at 5000, every built bodies-per-lane
 x chunk-group (1, 3, 7, 20) shape; 3 steps fixed and 3 adaptive (eta 0.25) with state(), the four
 carried rows and (time, dt_next); a resume from the four carried rows, then 2 more steps.
+Order 6 block steps (fp64, eta 0.25): derivs() (a4, j4, s4) of the three active sets on both
+evaluate paths; two block macro steps at n = 200, 2049 under three narrow_max, with the four
+carried rows.
 """
 from __future__ import annotations
 
@@ -201,6 +204,34 @@ def cases() -> dict:
             out[f"resume6/{dtype}"] = stepped6(e, 2)
         finally:
             e.close()
+
+    # order 6, block steps (fp64 only): the cases of active/ and block/ above
+    blk6 = dict(hermite_order=6, block_steps6=True, eta=0.25, dt=3600.0, max_level=6)
+    n = 2049
+    sets = {"one": [0], "four": [5, 6, 7, 2048], "third": list(range(0, n, 3))}
+
+    def active6(e):
+        e.set_block_tuning(n)  # (any active set may take the narrow path)
+        d = []
+        for idx in sets.values():
+            idx = np.asarray(idx, dtype=np.int32)
+            for path in ("narrow", "wide"):
+                d.extend(e.derivs(idx, path))
+        return digest(*d)
+
+    run("active6/fp64", engine(n, "fp64", **blk6), bodies(n), active6)
+    for n in (200, 2049):
+        for tag, cut in (("default", None), ("wide", 0), ("narrow", n)):
+            def macro6(e, cut=cut):
+                if cut is not None:
+                    e.set_block_tuning(cut)
+                e.step(2)
+                e.sync()
+                s, st = e.state(), e.status()
+                return digest(s.pos, s.vel, *e.carried(), e.body_times(), e.levels(),
+                              np.array([st.block_steps, st.body_steps, st.level_max]))
+
+            run(f"block6/fp64/n{n}/{tag}", engine(n, "fp64", **blk6), bodies(n), macro6)
     return out
 
 

@@ -11,9 +11,10 @@
 // and its block steps (fp64 only) are switched on by gs_hermite_set_block6 (refuse6).
 // Block mode (gs_hermite_set_block): per-body times and levels, an active list and a second
 // control block; a block step is a chain of seven launches, and gs_hermite_step advances whole
-// macro steps of dt against a device-side target time, one status read per 32 chains. Order 6
-// runs the same chain: order 4's next, control, compact and start kernels, and its own
-// predict-all, narrow, wide and correct kernels (block_chain).
+// macro steps of dt against a device-side target time, one status read per 32 chains. Both orders
+// take the one path: block_chain and derivs_active call gs::launch_block_* on the run's kernel
+// arguments, and the overloads for H6Args run order 4's next, control and compact kernels on
+// base_view(a) and order 6's own predict-all, narrow, wide and correct kernels.
 // Three precisions: fp32 and fp64 throughout, and mixed (GS_MIXED): the state rows, the reduce
 // and the corrector in fp64, the predicted rows (position as double-single hi + lo) and the
 // partial sums of the pair kernels in fp32.
@@ -103,22 +104,30 @@ int nwg(const gs_hermite* h) { return (int)(h->n_pad / gs::kForceBlock); }
 bool multi(const gs_hermite* h) { return h->cfg.nranks > 1; }
 constexpr int64_t kUnit = 1024;  // rows per ownership unit (gs_hermite_partition)
 
-// The kernel arguments of a launch: order 4 (T the pair type, S the state type) and order 6.
-template <typename T, typename S>
-void set_args(const gs_hermite* h, int mode, bool phi, gs::HArgs<T, S>& a) {
+// The kernel arguments of a launch. What both structs hold: P the type of the predicted rows, the
+// partials and the pair law, S of the state rows and the outputs.
+template <typename P, typename S, typename A>
+void set_shared(const gs_hermite* h, int mode, bool phi, A& a) {
   a.X = static_cast<S*>(h->X); a.V = static_cast<S*>(h->V);
   a.A = static_cast<S*>(h->A); a.J = static_cast<S*>(h->J);
-  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.XL = static_cast<T*>(h->XL);
-  a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ);
+  a.XP = static_cast<P*>(h->XP); a.VP = static_cast<P*>(h->VP);
+  a.PA = static_cast<P*>(h->PA); a.PJ = static_cast<P*>(h->PJ);
   a.a_out = static_cast<S*>(h->a_out); a.j_out = static_cast<S*>(h->j_out);
   a.ctrl = h->ctrl;
   a.wgmin = h->wgmin;
   a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
   a.mode = mode;
   a.phi = phi ? 1 : 0;
-  a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
-  a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
+  a.cut2 = (P)(h->cfg.cutoff * h->cfg.cutoff);
+  a.eps2 = (P)(h->cfg.softening * h->cfg.softening);
   a.blk = h->blk;
+}
+
+// Order 4 (T the pair type, S the state type) and order 6.
+template <typename T, typename S>
+void set_args(const gs_hermite* h, int mode, bool phi, gs::HArgs<T, S>& a) {
+  set_shared<T, S>(h, mode, phi, a);
+  a.XL = static_cast<T*>(h->XL);
   a.nn = h->nn ? 1 : 0;
   a.R = static_cast<S*>(h->R);
   a.PN = h->PN; a.NNI = h->NNI;
@@ -129,21 +138,10 @@ void set_args(const gs_hermite* h, int mode, bool phi, gs::HArgs<T, S>& a) {
 
 template <typename T>
 void set_args(const gs_hermite* h, int mode, bool phi, gs::H6Args<T>& a) {
-  a.X = static_cast<T*>(h->X); a.V = static_cast<T*>(h->V);
-  a.A = static_cast<T*>(h->A); a.J = static_cast<T*>(h->J);
+  set_shared<T, T>(h, mode, phi, a);
   a.S = static_cast<T*>(h->S); a.C = static_cast<T*>(h->C);
-  a.XP = static_cast<T*>(h->XP); a.VP = static_cast<T*>(h->VP); a.AP = static_cast<T*>(h->AP);
-  a.PA = static_cast<T*>(h->PA); a.PJ = static_cast<T*>(h->PJ); a.PS = static_cast<T*>(h->PS);
-  a.a_out = static_cast<T*>(h->a_out); a.j_out = static_cast<T*>(h->j_out);
+  a.AP = static_cast<T*>(h->AP); a.PS = static_cast<T*>(h->PS);
   a.s_out = static_cast<T*>(h->s_out);
-  a.ctrl = h->ctrl;
-  a.wgmin = h->wgmin;
-  a.n_real = h->n; a.n_pad = h->n_pad; a.chunk = h->chunk; a.n_chunks = h->n_chunks;
-  a.mode = mode;
-  a.phi = phi ? 1 : 0;
-  a.cut2 = (T)(h->cfg.cutoff * h->cfg.cutoff);
-  a.eps2 = (T)(h->cfg.softening * h->cfg.softening);
-  a.blk = h->blk;
   a.NS = static_cast<T*>(h->NS);
 }
 
@@ -166,6 +164,12 @@ int with_args(const gs_hermite* h, int mode, bool phi, F f) {
   });
 }
 
+// The kernel arguments of order 6; and of order 6 in fp32, which has no block steps (refuse6
+// R6_BLOCK6 keeps them from being switched on, so what asks this never runs).
+template <typename A> struct is_six : std::false_type {};
+template <typename T> struct is_six<gs::H6Args<T>> : std::true_type {};
+template <typename A> constexpr bool kNoBlock = std::is_same<A, gs::H6Args<float>>::value;
+
 // The four launches of a shared step, by the type of the kernel arguments.
 template <typename T, typename S>
 hipError_t launch_ctrl(const gs::HArgs<T, S>& a, hipStream_t s) {
@@ -185,11 +189,7 @@ hipError_t launch_reduce(const gs::HArgs<T, S>& a, hipStream_t s) {
 }
 template <typename T>
 hipError_t launch_ctrl(const gs::H6Args<T>& a, hipStream_t s) {
-  gs::HArgs<T, T> c{};  // (the control kernel, shared with order 4, reads these three)
-  c.ctrl = a.ctrl;
-  c.wgmin = a.wgmin;
-  c.n_pad = a.n_pad;
-  return gs::launch_hermite_ctrl<T, T>(c, s);
+  return gs::launch_hermite_ctrl<T, T>(gs::base_view(a), s);  // (order 4's control kernel)
 }
 template <typename T>
 hipError_t launch_predict(const gs::H6Args<T>& a, hipStream_t s) {
@@ -304,8 +304,7 @@ int point_at_current(gs_hermite*, gs::H6Args<T>& a) {
 template <typename A>
 int eval_current(gs_hermite* h, A a) {
   if (point_at_current(h, a)) return -1;
-  if constexpr (std::is_same<A, gs::H6Args<float>>::value ||
-                std::is_same<A, gs::H6Args<double>>::value) {
+  if constexpr (is_six<A>::value) {
     // Order 6 takes two passes: this one with ap = 0 gives a (and j), the one below with ap = a
     // gives s (and phi where asked).
     A first = a;
@@ -703,34 +702,21 @@ int block_start(gs_hermite* h, int64_t macro) {
   });
 }
 
-template <typename T, typename S>
-int block_chain(gs_hermite* h, const gs::HArgs<T, S>& a) {
-  GS_HIP((gs::launch_block_next<T, S>(a, h->stream)));
-  GS_HIP((gs::launch_block_predict<T, S>(a, h->stream)));
-  GS_HIP((gs::launch_block_narrow<T, S>(a, h->stream)));
-  GS_HIP((gs::launch_block_wide<T, S>(a, h->ipl, h->groups, h->stream)));
-  GS_HIP((gs::launch_block_correct<T, S>(a, h->stream)));
-  return 0;
-}
-
-// Order 6 (fp64): the same seven launches; next, control and compact are order 4's kernels on
-// the block state (they read blk and n_real of an HArgs).
-int block_chain(gs_hermite* h, const gs::H6Args<double>& a) {
-  gs::HArgs<double, double> c{};
-  c.blk = a.blk;
-  c.n_real = a.n_real;
-  c.n_pad = a.n_pad;
-  GS_HIP((gs::launch_block_next<double, double>(c, h->stream)));
-  GS_HIP(gs::launch_block6_predict(a, h->stream));
-  GS_HIP((gs::launch_block_compact<double, double>(c, h->stream)));
-  GS_HIP(gs::launch_block6_narrow(a, h->stream));
-  GS_HIP(gs::launch_block6_wide(a, h->ipl, h->groups, h->stream));
-  GS_HIP(gs::launch_block6_correct(a, h->stream));
-  return 0;
-}
-int block_chain(gs_hermite*, const gs::H6Args<float>&) {
-  gs_set_error("hermite order 6 runs block steps in fp64 only");
-  return -1;
+// One block step of either order: next + control, predict-all + mark + compact, narrow, wide,
+// correct (the overloads of gs_hermite.h).
+template <typename A>
+int block_chain(gs_hermite* h, const A& a) {
+  if constexpr (kNoBlock<A>) {
+    gs_set_error(refuse6(h, R6_BLOCK6));
+    return -1;
+  } else {
+    GS_HIP(gs::launch_block_next(a, h->stream));
+    GS_HIP(gs::launch_block_predict(a, h->stream));
+    GS_HIP(gs::launch_block_narrow(a, h->stream));
+    GS_HIP(gs::launch_block_wide(a, h->ipl, h->groups, h->stream));
+    GS_HIP(gs::launch_block_correct(a, h->stream));
+    return 0;
+  }
 }
 
 // n macro steps: chains in batches of 32 against the device-side target, one status read each.
@@ -762,73 +748,47 @@ int block_step_t(gs_hermite* h, int32_t nsteps) {
   return 0;
 }
 
-template <typename T, typename S>
-int derivs_active_t(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
-                    double* jerk4, int32_t reps = 1, double* ms = nullptr, double* q = nullptr,
-                    int32_t* nn = nullptr) {
-  gs::HermiteBlockCtrl keep;
-  if (read_bctrl(h, &keep)) return -1;
-  gs::HermiteBlockCtrl c = keep;
-  c.n_act = n_idx;
-  c.path = path;
-  c.active = 1;
-  GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
-                        h->stream));
-  if (write_bctrl(h, c)) return -1;
-  gs::HArgs<T, S> a = make_args<gs::HArgs<T, S>>(h, gs::HM_OUT, true);
-  if (point_at_current(h, a)) return -1;
-  EventTimer timer;
-  if (ms && (timer.create() || timer.start(h->stream))) return -1;
-  for (int32_t r = 0; r < reps; ++r) {
-    if (path == gs::HP_NARROW)
-      GS_HIP((gs::launch_block_narrow<T, S>(a, h->stream)));
-    else
-      GS_HIP((gs::launch_block_wide<T, S>(a, h->ipl, h->groups, h->stream)));
-    GS_HIP((gs::launch_block_correct<T, S>(a, h->stream)));
-  }
-  if (ms) {
-    if (timer.stop(h->stream, ms)) return -1;
-    *ms /= reps;
-  }
-  if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
-      ((q || nn) && download_pair(h, h->q_out, h->nn_out, n_idx, q, nn)))
+// Derivatives of the listed bodies at the current state through one block path's evaluate and
+// correct (a: HM_OUT with the potential), `reps` times between two events where ms is asked. The
+// block control is put back as it was. Order 6: one pass at the rows (x, v, carried a), and the
+// snap where asked.
+template <typename A>
+int derivs_active(gs_hermite* h, A a, const int32_t* idx, int32_t n_idx, int32_t path, int32_t reps,
+                  double* ms, double* acc4, double* jerk4, double* snap4, double* q, int32_t* nn) {
+  if constexpr (kNoBlock<A>) {
+    gs_set_error(refuse6(h, R6_BLOCK6));
     return -1;
-  return write_bctrl(h, keep);
-}
-
-// Order 6: one pass at the rows (x, v, carried a) of the current state.
-int derivs_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path, double* acc4,
-                   double* jerk4, double* snap4, int32_t reps, double* ms) {
-  gs::HermiteBlockCtrl keep;
-  if (read_bctrl(h, &keep)) return -1;
-  gs::HermiteBlockCtrl c = keep;
-  c.n_act = n_idx;
-  c.path = path;
-  c.active = 1;
-  GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t), hipMemcpyHostToDevice,
-                        h->stream));
-  if (write_bctrl(h, c)) return -1;
-  gs::H6Args<double> a = make_args<gs::H6Args<double>>(h, gs::HM_OUT, true);
-  a.XP = a.X;
-  a.VP = a.V;
-  a.AP = a.A;
-  EventTimer timer;
-  if (ms && (timer.create() || timer.start(h->stream))) return -1;
-  for (int32_t r = 0; r < reps; ++r) {
-    if (path == gs::HP_NARROW)
-      GS_HIP(gs::launch_block6_narrow(a, h->stream));
-    else
-      GS_HIP(gs::launch_block6_wide(a, h->ipl, h->groups, h->stream));
-    GS_HIP(gs::launch_block6_correct(a, h->stream));
+  } else {
+    gs::HermiteBlockCtrl keep;
+    if (read_bctrl(h, &keep)) return -1;
+    gs::HermiteBlockCtrl c = keep;
+    c.n_act = n_idx;
+    c.path = path;
+    c.active = 1;
+    GS_HIP(hipMemcpyAsync(h->blk.list, idx, (size_t)n_idx * sizeof(int32_t),
+                          hipMemcpyHostToDevice, h->stream));
+    if (write_bctrl(h, c)) return -1;
+    if (point_at_current(h, a)) return -1;
+    if constexpr (is_six<A>::value) a.AP = a.A;
+    EventTimer timer;
+    if (ms && (timer.create() || timer.start(h->stream))) return -1;
+    for (int32_t r = 0; r < reps; ++r) {
+      if (path == gs::HP_NARROW)
+        GS_HIP(gs::launch_block_narrow(a, h->stream));
+      else
+        GS_HIP(gs::launch_block_wide(a, h->ipl, h->groups, h->stream));
+      GS_HIP(gs::launch_block_correct(a, h->stream));
+    }
+    if (ms) {
+      if (timer.stop(h->stream, ms)) return -1;
+      *ms /= reps;
+    }
+    if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
+        (h->order == 6 && download_rows(h, h->s_out, n_idx, snap4, 4)) ||
+        ((q || nn) && download_pair(h, h->q_out, h->nn_out, n_idx, q, nn)))
+      return -1;
+    return write_bctrl(h, keep);
   }
-  if (ms) {
-    if (timer.stop(h->stream, ms)) return -1;
-    *ms /= reps;
-  }
-  if (download_rows(h, h->a_out, n_idx, acc4, 4) || download_rows(h, h->j_out, n_idx, jerk4, 4) ||
-      download_rows(h, h->s_out, n_idx, snap4, 4))
-    return -1;
-  return write_bctrl(h, keep);
 }
 
 // The arrays order 6 adds to the run's (snap and crackle rows, the predicted acceleration, the
@@ -982,10 +942,6 @@ int set_state(gs_hermite* h, const double* pos, const double* vel, const double*
 }  // namespace
 
 extern "C" {
-
-static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
-                          int32_t* nn);
 
 int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   if (!cfg || !out) { gs_set_error("hermite: null argument"); return -1; }
@@ -1320,25 +1276,6 @@ int gs_hermite_set_block_state(gs_hermite* h, const int64_t* tb, const int32_t* 
   return write_bctrl(h, c);  // (waits for the copies: lv, tv are on this frame)
 }
 
-int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                             double* acc4, double* jerk4) {
-  return gs_hermite_time_active(h, idx, n_idx, path, 1, nullptr, acc4, jerk4);
-}
-
-int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                           int32_t reps, double* ms, double* acc4, double* jerk4) {
-  return time_active_nn(h, idx, n_idx, path, reps, ms, acc4, jerk4, nullptr, nullptr);
-}
-
-int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                                double* acc4, double* jerk4, double* q, int32_t* nn) {
-  if (h && (q || nn) && !h->nn) {
-    gs_set_error("hermite derivs_active_nn: collisions are off");
-    return -1;
-  }
-  return time_active_nn(h, idx, n_idx, path, 1, nullptr, acc4, jerk4, q, nn);
-}
-
 // The checks of every derivs_active / time_active entry; *path 0 becomes the path narrow_max picks.
 static int active_args_ok(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t* path_io) {
   int32_t path = *path_io;
@@ -1361,32 +1298,49 @@ static int active_args_ok(gs_hermite* h, const int32_t* idx, int32_t n_idx, int3
   return 0;
 }
 
+// The one way in of the entries below. six: an entry of order 6 (the engine's order must be 6);
+// the others take an engine of either order (of order 6: its a and j).
+static int active_entry(gs_hermite* h, bool six, const int32_t* idx, int32_t n_idx, int32_t path,
+                        int32_t reps, double* ms, double* acc4, double* jerk4, double* snap4,
+                        double* q, int32_t* nn) {
+  if (active_args_ok(h, idx, n_idx, &path)) return -1;
+  if (six && h->order != 6) { gs_set_error("hermite derivs_active6: the order is not 6"); return -1; }
+  if (reps < 1) reps = 1;
+  GS_HIP(hipSetDevice(h->cfg.device));
+  return with_args(h, gs::HM_OUT, true, [&](auto a) {
+    return derivs_active(h, a, idx, n_idx, path, reps, ms, acc4, jerk4, snap4, q, nn);
+  });
+}
+
+int gs_hermite_derivs_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                             double* acc4, double* jerk4) {
+  return active_entry(h, false, idx, n_idx, path, 1, nullptr, acc4, jerk4, nullptr, nullptr,
+                      nullptr);
+}
+
+int gs_hermite_time_active(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                           int32_t reps, double* ms, double* acc4, double* jerk4) {
+  return active_entry(h, false, idx, n_idx, path, reps, ms, acc4, jerk4, nullptr, nullptr, nullptr);
+}
+
+int gs_hermite_derivs_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
+                                double* acc4, double* jerk4, double* q, int32_t* nn) {
+  if (h && (q || nn) && !h->nn) {
+    gs_set_error("hermite derivs_active_nn: collisions are off");
+    return -1;
+  }
+  return active_entry(h, false, idx, n_idx, path, 1, nullptr, acc4, jerk4, nullptr, q, nn);
+}
+
 int gs_hermite_derivs_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                               double* acc4, double* jerk4, double* snap4) {
-  return gs_hermite_time_active6(h, idx, n_idx, path, 1, nullptr, acc4, jerk4, snap4);
+  return active_entry(h, true, idx, n_idx, path, 1, nullptr, acc4, jerk4, snap4, nullptr, nullptr);
 }
 
 int gs_hermite_time_active6(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
                             int32_t reps, double* ms, double* acc4, double* jerk4,
                             double* snap4) {
-  if (active_args_ok(h, idx, n_idx, &path)) return -1;
-  if (h->order != 6) { gs_set_error("hermite derivs_active6: the order is not 6"); return -1; }
-  GS_HIP(hipSetDevice(h->cfg.device));
-  return derivs_active6(h, idx, n_idx, path, acc4, jerk4, snap4, reps < 1 ? 1 : reps, ms);
-}
-
-static int time_active_nn(gs_hermite* h, const int32_t* idx, int32_t n_idx, int32_t path,
-                          int32_t reps, double* ms, double* acc4, double* jerk4, double* q,
-                          int32_t* nn) {
-  if (active_args_ok(h, idx, n_idx, &path)) return -1;
-  if (h->order == 6)  // (a and j of gs_hermite_time_active6; order 6 has no collisions)
-    return gs_hermite_time_active6(h, idx, n_idx, path, reps, ms, acc4, jerk4, nullptr);
-  if (reps < 1) reps = 1;
-  GS_HIP(hipSetDevice(h->cfg.device));
-  return by_dtype(h, [&](auto t, auto s) {
-    return derivs_active_t<decltype(t), decltype(s)>(h, idx, n_idx, path, acc4, jerk4, reps, ms,
-                                                      q, nn);
-  });
+  return active_entry(h, true, idx, n_idx, path, reps, ms, acc4, jerk4, snap4, nullptr, nullptr);
 }
 
 int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {

@@ -887,14 +887,7 @@ __global__ __launch_bounds__(kBlock) void block_init_kernel(HArgs<T, S> a, int64
 // ---------------------------------------------------------------------------------------
 // Host launchers: validate, compute the grid, dispatch.
 
-template <typename... P, typename... A>
-static hipError_t hlaunch(void (*kernel)(P...), dim3 grid, hipStream_t s, const A&... args) {
-  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, args...);
-  return hipGetLastError();
-}
-
-// Workgroups of one thread per row.
-static dim3 row_grid(int64_t rows) { return dim3((unsigned)(rows / kBlock)); }
+// (hlaunch, row_grid and clamp_groups: gs_hermite.h, shared with nbody_hermite6.hip)
 
 // A rank's slice of a multi-rank run.
 template <typename T, typename S>
@@ -974,10 +967,6 @@ template <typename T, typename S>
 static bool slice_ok(const HArgs<T, S>& a, int64_t unit) {
   return a.row0 >= 0 && a.n_loc >= 1 && a.row0 + a.n_loc <= a.n_pad && a.n_loc % unit == 0 &&
          a.row0 % kBlock == 0 && !(is_slice(a) && a.blk.bc);
-}
-
-static int clamp_groups(int groups, int n_chunks) {
-  return groups < 1 ? 1 : groups > n_chunks ? n_chunks : groups;
 }
 
 template <typename T, typename S>

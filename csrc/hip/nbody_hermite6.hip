@@ -22,12 +22,14 @@
 //     and the number of chunk groups change the grid, never the bits.
 // Step chain (one stream, no host round trip): control (hermite_ctrl_kernel, shared with the
 // 4th-order chain) -> predict -> evaluate -> reduce + correct + next-step minima.
-// Block time steps (fp64; second half of this file): the chain of nbody_hermite.hip, whose
-// next-time minima, control, compaction and start kernels it runs as they are (they read the
-// block state, n_real, A and J only): next + control -> predict-all + mark (block6_predict_kernel)
-// -> compact -> evaluate of the active bodies, narrow (hermite6_narrow_kernel, parallel over j) or
-// wide (the LIST form of hermite6_eval_kernel) by n_act -> reduce + correct + new level
-// (block6_correct_kernel).
+// Block time steps (fp64): the chain of nbody_hermite.hip, whose next-time minima, control,
+// compaction and start kernels it runs as they are (they read the block state, n_real, A and J
+// only): next + control -> predict-all + mark (block6_predict_kernel) -> compact -> evaluate of the
+// active bodies, narrow (hermite6_narrow_kernel, parallel over j) or wide (the LIST form of
+// hermite6_eval_kernel) by n_act -> reduce + correct + new level (block6_correct_kernel). The
+// predictor, the fold of the partials, the HM_OUT store and the corrector of a body are device
+// functions that the shared step's kernels and the block step's both call (h6predict_row, h6fold,
+// h6out, h6correct_row); the launchers are the H6Args overloads of order 4's (gs_hermite.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -188,6 +190,102 @@ __global__ __launch_bounds__(kBlock) void hermite6_eval_kernel(H6Args<T> a, int 
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// What the shared step's kernels and the block step's share, per body.
+
+template <typename T>
+__device__ __forceinline__ V4<T>* rows4(T* p) { return reinterpret_cast<V4<T>*>(p); }
+
+// The predicted rows of body i over h (x to h^5, v to h^4, a to h^3; xp.w = mu).
+template <typename T>
+__device__ __forceinline__ void h6predict_row(const H6Args<T>& a, int64_t i, T h, V4<T>& xp,
+                                              V4<T>& vp, V4<T>& ap) {
+  const H6Taylor<T> t = h6_taylor(h);
+  const V4<T> x = rows4(a.X)[i], v = rows4(a.V)[i], ac = rows4(a.A)[i], jk = rows4(a.J)[i],
+              sn = rows4(a.S)[i], cr = rows4(a.C)[i];
+  T px, pv, pa;
+  h6_predict(t, x.x, v.x, ac.x, jk.x, sn.x, cr.x, px, pv, pa);
+  xp.x = px; vp.x = pv; ap.x = pa;
+  h6_predict(t, x.y, v.y, ac.y, jk.y, sn.y, cr.y, px, pv, pa);
+  xp.y = px; vp.y = pv; ap.y = pa;
+  h6_predict(t, x.z, v.z, ac.z, jk.z, sn.z, cr.z, px, pv, pa);
+  xp.z = px; vp.z = pv; ap.z = pa;
+  xp.w = x.w;
+}
+
+// ... and their store (ghost rows: zero).
+template <typename T>
+__device__ __forceinline__ void h6predicted(const H6Args<T>& a, int64_t i, const V4<T>& xp,
+                                            const V4<T>& vp, const V4<T>& ap) {
+  rows4(a.XP)[i] = xp; rows4(a.VP)[i] = vp; rows4(a.AP)[i] = ap;
+}
+
+// m = (a1, j1, s1) and ph of one row: its `parts` partials, `stride` rows apart, added from zero
+// in order. UNROLL4: the block step's loop (a schedule hint, the sums are the same).
+template <bool UNROLL4, typename T>
+__device__ __forceinline__ void h6fold(const void* pa_, const void* pj_, const void* ps_, int parts,
+                                       int64_t stride, int64_t row, T (&m)[3][3], T& ph) {
+  const V4<T>* PA = reinterpret_cast<const V4<T>*>(pa_);
+  const V4<T>* PJ = reinterpret_cast<const V4<T>*>(pj_);
+  const V4<T>* PS = reinterpret_cast<const V4<T>*>(ps_);
+  auto add = [&](int c) {
+    const int64_t o = (int64_t)c * stride + row;
+    const V4<T> pa = PA[o], pj = PJ[o], ps = PS[o];
+    m[0][0] += pa.x; m[0][1] += pa.y; m[0][2] += pa.z; ph += pa.w;
+    m[1][0] += pj.x; m[1][1] += pj.y; m[1][2] += pj.z;
+    m[2][0] += ps.x; m[2][1] += ps.y; m[2][2] += ps.z;
+  };
+  if constexpr (UNROLL4) {
+#pragma unroll 4
+    for (int c = 0; c < parts; ++c) add(c);
+  } else {
+    for (int c = 0; c < parts; ++c) add(c);
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ V4<T> h6row(const T (&v)[3]) {
+  return V4<T>{v[0], v[1], v[2], T(0)};
+}
+
+// HM_OUT: (a, -sum mu / r), j, s of the sums m to row (or slot) `row` of the outputs.
+template <typename T>
+__device__ __forceinline__ void h6out(const H6Args<T>& a, int64_t row, const T (&m)[3][3], T ph) {
+  V4<T> oa = h6row(m[0]);
+  oa.w = -ph;
+  rows4(a.a_out)[row] = oa; rows4(a.j_out)[row] = h6row(m[1]); rows4(a.s_out)[row] = h6row(m[2]);
+}
+
+// What h6_dt reads: the new a, j, s and the higher derivatives at the end of the step.
+struct H6Rates {
+  double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
+};
+
+// The corrector of body i over hd with the sums m = (a1, j1, s1), the crackle c1 and the higher
+// derivatives; stores x, v, a, j, s, c.
+template <typename T>
+__device__ __forceinline__ H6Rates h6correct_row(const H6Args<T>& a, int64_t i, double hd,
+                                                 const T (&m)[3][3]) {
+  V4<T>*X = rows4(a.X), *V = rows4(a.V), *A = rows4(a.A), *J = rows4(a.J), *S = rows4(a.S);
+  const T h = (T)hd;
+  const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i], s0 = S[i];
+  const T xs[3] = {x.x, x.y, x.z}, vs[3] = {v.x, v.y, v.z};
+  const T as[3] = {a0.x, a0.y, a0.z}, js[3] = {j0.x, j0.y, j0.z}, ss[3] = {s0.x, s0.y, s0.z};
+  T x1[3], v1[3];
+  H6Rates r;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    h6_correct(h, xs[d], vs[d], as[d], js[d], ss[d], m[0][d], m[1][d], m[2][d], x1[d], v1[d]);
+    r.a1[d] = m[0][d]; r.j1[d] = m[1][d]; r.s1[d] = m[2][d];
+    h6_high(hd, as[d], js[d], ss[d], r.a1[d], r.j1[d], r.s1[d], r.c1[d], r.p1[d], r.a5[d]);
+  }
+  const V4<T> ox = {x1[0], x1[1], x1[2], x.w}, ov = {v1[0], v1[1], v1[2], T(0)};
+  const V4<T> oc = {(T)r.c1[0], (T)r.c1[1], (T)r.c1[2], T(0)};
+  X[i] = ox; V[i] = ov; A[i] = h6row(m[0]); J[i] = h6row(m[1]); S[i] = h6row(m[2]);
+  rows4(a.C)[i] = oc;
+  return r;
+}
+
 // PREDICT over the step's h (ghost rows stay zero).
 template <typename T>
 __global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(H6Args<T> a) {
@@ -195,26 +293,8 @@ __global__ __launch_bounds__(kBlock) void hermite6_predict_kernel(H6Args<T> a) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= a.n_pad) return;
   V4<T> xp = {T(0), T(0), T(0), T(0)}, vp = xp, ap = xp;
-  if (i < a.n_real) {
-    const H6Taylor<T> t = h6_taylor((T)a.ctrl->h);
-    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
-    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
-    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
-    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
-    const V4<T> sn = reinterpret_cast<const V4<T>*>(a.S)[i];
-    const V4<T> cr = reinterpret_cast<const V4<T>*>(a.C)[i];
-    T px, pv, pa;
-    h6_predict(t, x.x, v.x, ac.x, jk.x, sn.x, cr.x, px, pv, pa);
-    xp.x = px; vp.x = pv; ap.x = pa;
-    h6_predict(t, x.y, v.y, ac.y, jk.y, sn.y, cr.y, px, pv, pa);
-    xp.y = px; vp.y = pv; ap.y = pa;
-    h6_predict(t, x.z, v.z, ac.z, jk.z, sn.z, cr.z, px, pv, pa);
-    xp.z = px; vp.z = pv; ap.z = pa;
-    xp.w = x.w;
-  }
-  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
-  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
-  reinterpret_cast<V4<T>*>(a.AP)[i] = ap;
+  if (i < a.n_real) h6predict_row(a, i, (T)a.ctrl->h, xp, vp, ap);
+  h6predicted(a, i, xp, vp, ap);
 }
 
 // REDUCE (+ CORRECT): one thread per body adds its chunk partials in chunk order, then HM_STEP
@@ -227,33 +307,12 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
   __shared__ double red[kBlock / 64];
   if (a.mode == HM_STEP && !a.ctrl->active) return;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;  // (n_pad: a multiple of 256)
-  const V4<T>* PA = reinterpret_cast<const V4<T>*>(a.PA);
-  const V4<T>* PJ = reinterpret_cast<const V4<T>*>(a.PJ);
-  const V4<T>* PS = reinterpret_cast<const V4<T>*>(a.PS);
   T m[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ph = 0;  // a1, j1, s1
-  for (int c = 0; c < a.n_chunks; ++c) {
-    const int64_t o = (int64_t)c * a.n_pad + i;
-    const V4<T> pa = PA[o], pj = PJ[o], ps = PS[o];
-    m[0][0] += pa.x; m[0][1] += pa.y; m[0][2] += pa.z; ph += pa.w;
-    m[1][0] += pj.x; m[1][1] += pj.y; m[1][2] += pj.z;
-    m[2][0] += ps.x; m[2][1] += ps.y; m[2][2] += ps.z;
-  }
+  h6fold<false>(a.PA, a.PJ, a.PS, a.n_chunks, a.n_pad, i, m, ph);
+  if (a.mode == HM_OUT) return h6out(a, i, m, ph);
   const V4<T> z = {T(0), T(0), T(0), T(0)};
-  V4<T> oa = {m[0][0], m[0][1], m[0][2], T(0)}, oj = {m[1][0], m[1][1], m[1][2], T(0)},
-        os = {m[2][0], m[2][1], m[2][2], T(0)};
-  if (a.mode == HM_OUT) {
-    oa.w = -ph;
-    reinterpret_cast<V4<T>*>(a.a_out)[i] = oa;
-    reinterpret_cast<V4<T>*>(a.j_out)[i] = oj;
-    reinterpret_cast<V4<T>*>(a.s_out)[i] = os;
-    return;
-  }
-  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
-  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
-  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
-  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
-  V4<T>* S = reinterpret_cast<V4<T>*>(a.S);
-  V4<T>* C = reinterpret_cast<V4<T>*>(a.C);
+  V4<T>*X = rows4(a.X), *V = rows4(a.V), *A = rows4(a.A), *J = rows4(a.J), *S = rows4(a.S),
+        *C = rows4(a.C);
   const double eta = a.ctrl->eta;
   double dti = INFINITY;
   if (i >= a.n_real) {
@@ -263,33 +322,16 @@ __global__ __launch_bounds__(kBlock) void hermite6_reduce_kernel(H6Args<T> a) {
       V[i] = z;
     }
   } else if (a.mode == HM_INIT) {
-    A[i] = oa; J[i] = oj; S[i] = os; C[i] = z;
+    A[i] = h6row(m[0]); J[i] = h6row(m[1]); S[i] = h6row(m[2]); C[i] = z;
     if (eta > 0.0) {
       const double ad[3] = {m[0][0], m[0][1], m[0][2]}, jd[3] = {m[1][0], m[1][1], m[1][2]};
       double d;
       if (hermite_first_dt(eta, ad, jd, d)) dti = d;
     }
   } else {
-    const double hd = a.ctrl->h;
-    const T h = (T)hd;
-    const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i], s0 = S[i];
-    const T xs[3] = {x.x, x.y, x.z}, vs[3] = {v.x, v.y, v.z};
-    const T as[3] = {a0.x, a0.y, a0.z}, js[3] = {j0.x, j0.y, j0.z}, ss[3] = {s0.x, s0.y, s0.z};
-    T x1[3], v1[3];
-    double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      h6_correct(h, xs[d], vs[d], as[d], js[d], ss[d], m[0][d], m[1][d], m[2][d], x1[d], v1[d]);
-      a1[d] = m[0][d]; j1[d] = m[1][d]; s1[d] = m[2][d];
-      h6_high(hd, as[d], js[d], ss[d], a1[d], j1[d], s1[d], c1[d], p1[d], a5[d]);
-    }
-    const V4<T> ox = {x1[0], x1[1], x1[2], x.w}, ov = {v1[0], v1[1], v1[2], T(0)};
-    const V4<T> oc = {(T)c1[0], (T)c1[1], (T)c1[2], T(0)};
-    X[i] = ox; V[i] = ov; A[i] = oa; J[i] = oj; S[i] = os; C[i] = oc;
-    if (eta > 0.0) {
-      double d;
-      if (h6_dt(eta, a1, j1, s1, c1, p1, a5, d)) dti = d;
-    }
+    const H6Rates r = h6correct_row(a, i, a.ctrl->h, m);
+    double d;
+    if (eta > 0.0 && h6_dt(eta, r.a1, r.j1, r.s1, r.c1, r.p1, r.a5, d)) dti = d;
   }
   dti = block_min(dti, red);
   if (threadIdx.x == 0) a.wgmin[blockIdx.x] = dti;
@@ -313,25 +355,9 @@ __global__ __launch_bounds__(kBlock) void block6_predict_kernel(H6Args<T> a) {
   bool due = false;
   if (i < a.n_real) {
     due = body_due(b, i, L, t_next);
-    const H6Taylor<T> t = h6_taylor((T)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L));
-    const V4<T> x = reinterpret_cast<const V4<T>*>(a.X)[i];
-    const V4<T> v = reinterpret_cast<const V4<T>*>(a.V)[i];
-    const V4<T> ac = reinterpret_cast<const V4<T>*>(a.A)[i];
-    const V4<T> jk = reinterpret_cast<const V4<T>*>(a.J)[i];
-    const V4<T> sn = reinterpret_cast<const V4<T>*>(a.S)[i];
-    const V4<T> cr = reinterpret_cast<const V4<T>*>(a.C)[i];
-    T px, pv, pa;
-    h6_predict(t, x.x, v.x, ac.x, jk.x, sn.x, cr.x, px, pv, pa);
-    xp.x = px; vp.x = pv; ap.x = pa;
-    h6_predict(t, x.y, v.y, ac.y, jk.y, sn.y, cr.y, px, pv, pa);
-    xp.y = px; vp.y = pv; ap.y = pa;
-    h6_predict(t, x.z, v.z, ac.z, jk.z, sn.z, cr.z, px, pv, pa);
-    xp.z = px; vp.z = pv; ap.z = pa;
-    xp.w = x.w;
+    h6predict_row(a, i, (T)ticks_seconds(b.bc->dt_max, t_next - b.tb[i], L), xp, vp, ap);
   }
-  reinterpret_cast<V4<T>*>(a.XP)[i] = xp;
-  reinterpret_cast<V4<T>*>(a.VP)[i] = vp;
-  reinterpret_cast<V4<T>*>(a.AP)[i] = ap;
+  h6predicted(a, i, xp, vp, ap);
   const int c = __popcll(__ballot(due));
   if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = c;
   __syncthreads();
@@ -420,58 +446,19 @@ __global__ __launch_bounds__(kBlock) void block6_correct_kernel(H6Args<T> a) {
   const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (s >= bc->n_act) return;
   const bool narrow = bc->path == HP_NARROW;
-  const V4<T>* PA = reinterpret_cast<const V4<T>*>(narrow ? b.NA : (void*)a.PA);
-  const V4<T>* PJ = reinterpret_cast<const V4<T>*>(narrow ? b.NJ : (void*)a.PJ);
-  const V4<T>* PS = reinterpret_cast<const V4<T>*>(narrow ? (void*)a.NS : (void*)a.PS);
-  const int parts = narrow ? b.n_slices : a.n_chunks;
-  const int64_t stride = narrow ? (int64_t)b.cap : a.n_pad;
   T m[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, ph = 0;  // a1, j1, s1
-#pragma unroll 4
-  for (int c = 0; c < parts; ++c) {
-    const int64_t o = (int64_t)c * stride + s;
-    const V4<T> pa = PA[o], pj = PJ[o], ps = PS[o];
-    m[0][0] += pa.x; m[0][1] += pa.y; m[0][2] += pa.z; ph += pa.w;
-    m[1][0] += pj.x; m[1][1] += pj.y; m[1][2] += pj.z;
-    m[2][0] += ps.x; m[2][1] += ps.y; m[2][2] += ps.z;
-  }
-  V4<T> oa = {m[0][0], m[0][1], m[0][2], T(0)}, oj = {m[1][0], m[1][1], m[1][2], T(0)},
-        os = {m[2][0], m[2][1], m[2][2], T(0)};
-  if (a.mode == HM_OUT) {
-    oa.w = -ph;
-    reinterpret_cast<V4<T>*>(a.a_out)[s] = oa;
-    reinterpret_cast<V4<T>*>(a.j_out)[s] = oj;
-    reinterpret_cast<V4<T>*>(a.s_out)[s] = os;
-    return;
-  }
+  h6fold<true>(narrow ? b.NA : (void*)a.PA, narrow ? b.NJ : (void*)a.PJ,
+               narrow ? (void*)a.NS : (void*)a.PS, narrow ? b.n_slices : a.n_chunks,
+               narrow ? (int64_t)b.cap : a.n_pad, s, m, ph);
+  if (a.mode == HM_OUT) return h6out(a, s, m, ph);
   const int64_t i = b.list[s];
   const int L = bc->L;
   const int64_t t_next = bc->t_ticks;
   const double dt_max = bc->dt_max;
-  const double hd = ticks_seconds(dt_max, t_next - b.tb[i], L);
-  const T h = (T)hd;
-  V4<T>* X = reinterpret_cast<V4<T>*>(a.X);
-  V4<T>* V = reinterpret_cast<V4<T>*>(a.V);
-  V4<T>* A = reinterpret_cast<V4<T>*>(a.A);
-  V4<T>* J = reinterpret_cast<V4<T>*>(a.J);
-  V4<T>* S = reinterpret_cast<V4<T>*>(a.S);
-  V4<T>* C = reinterpret_cast<V4<T>*>(a.C);
-  const V4<T> x = X[i], v = V[i], a0 = A[i], j0 = J[i], s0 = S[i];
-  const T xs[3] = {x.x, x.y, x.z}, vs[3] = {v.x, v.y, v.z};
-  const T as[3] = {a0.x, a0.y, a0.z}, js[3] = {j0.x, j0.y, j0.z}, ss[3] = {s0.x, s0.y, s0.z};
-  T x1[3], v1[3];
-  double a1[3], j1[3], s1[3], c1[3], p1[3], a5[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    h6_correct(h, xs[d], vs[d], as[d], js[d], ss[d], m[0][d], m[1][d], m[2][d], x1[d], v1[d]);
-    a1[d] = m[0][d]; j1[d] = m[1][d]; s1[d] = m[2][d];
-    h6_high(hd, as[d], js[d], ss[d], a1[d], j1[d], s1[d], c1[d], p1[d], a5[d]);
-  }
-  const V4<T> ox = {x1[0], x1[1], x1[2], x.w}, ov = {v1[0], v1[1], v1[2], T(0)};
-  const V4<T> oc = {(T)c1[0], (T)c1[1], (T)c1[2], T(0)};
-  X[i] = ox; V[i] = ov; A[i] = oa; J[i] = oj; S[i] = os; C[i] = oc;
+  const H6Rates r = h6correct_row(a, i, ticks_seconds(dt_max, t_next - b.tb[i], L), m);
   b.tb[i] = t_next;
   double want;
-  const bool rated = h6_dt(bc->eta, a1, j1, s1, c1, p1, a5, want);
+  const bool rated = h6_dt(bc->eta, r.a1, r.j1, r.s1, r.c1, r.p1, r.a5, want);
   b.level[i] = block_new_level(bc, b.level[i], rated, want, t_next, L, dt_max);
 }
 
@@ -487,57 +474,69 @@ static bool args6_ok(const H6Args<T>& a, int ipl = 1) {
          a.n_real <= a.n_pad;
 }
 
-template <typename T, bool PHI, int IPL>
+// What every evaluate launch needs (the shared step's and the block step's wide path), and its
+// grid.
+template <typename T>
+static bool eval6_ok(const H6Args<T>& a, int ipl) {
+  return hermite6_ipl_ok(sizeof(T) == 8, ipl) && args6_ok(a, ipl) && a.XP && a.VP && a.AP &&
+         a.PA && a.PJ && a.PS;
+}
+
+template <typename T>
+static dim3 eval6_grid(const H6Args<T>& a, int ipl, int groups) {
+  return dim3((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)clamp_groups(groups, a.n_chunks));
+}
+
+template <typename T, int IPL>
 static hipError_t eval6_go(const H6Args<T>& a, dim3 grid, bool gated, hipStream_t s) {
-  hipLaunchKernelGGL((hermite6_eval_kernel<T, PHI, IPL>), grid, dim3(kBlock), 0, s, a, (int)gated);
-  return hipGetLastError();
+  return a.phi ? hlaunch(hermite6_eval_kernel<T, true, IPL>, grid, s, a, (int)gated)
+               : hlaunch(hermite6_eval_kernel<T, false, IPL>, grid, s, a, (int)gated);
 }
 
 template <typename T>
 hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool gated,
                                 hipStream_t s) {
-  if (!hermite6_ipl_ok(sizeof(T) == 8, ipl) || !args6_ok(a, ipl) || (gated && !a.ctrl) || !a.XP ||
-      !a.VP || !a.AP || !a.PA || !a.PJ || !a.PS)
-    return hipErrorInvalidValue;
-  const int g = groups < 1 ? 1 : groups > a.n_chunks ? a.n_chunks : groups;
-  const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)g);
+  if (!eval6_ok(a, ipl) || (gated && !a.ctrl)) return hipErrorInvalidValue;
   if constexpr (sizeof(T) == 4) {
-    if (ipl == 2)
-      return a.phi ? eval6_go<T, true, 2>(a, grid, gated, s) : eval6_go<T, false, 2>(a, grid, gated, s);
+    if (ipl == 2) return eval6_go<T, 2>(a, eval6_grid(a, ipl, groups), gated, s);
   }
-  return a.phi ? eval6_go<T, true, 1>(a, grid, gated, s) : eval6_go<T, false, 1>(a, grid, gated, s);
+  return eval6_go<T, 1>(a, eval6_grid(a, ipl, groups), gated, s);
 }
 
 template <typename T>
 hipError_t launch_hermite6_predict(const H6Args<T>& a, hipStream_t s) {
   if (!args6_ok(a) || !a.ctrl) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hermite6_predict_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
-                     0, s, a);
-  return hipGetLastError();
+  return hlaunch(hermite6_predict_kernel<T>, row_grid(a.n_pad), s, a);
 }
 
 template <typename T>
 hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s) {
   if (!args6_ok(a) || !a.ctrl || !a.wgmin) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(hermite6_reduce_kernel<T>, dim3((unsigned)(a.n_pad / kBlock)), dim3(kBlock),
-                     0, s, a);
-  return hipGetLastError();
+  return hlaunch(hermite6_reduce_kernel<T>, row_grid(a.n_pad), s, a);
 }
 
-// ---- block steps (fp64) ---------------------------------------------------------------------
-static bool block6_ok(const H6Args<double>& a) {
+// ---- block steps (fp64): the H6Args overloads of order 4's launchers ------------------------
+template <typename T>
+static bool block6_ok(const H6Args<T>& a) {
   const HBlock& b = a.blk;
   return args6_ok(a) && b.bc && b.tb && b.level && b.list && b.wgcount && b.wgnext;
 }
 
-hipError_t launch_block6_predict(const H6Args<double>& a, hipStream_t s) {
-  if (!block6_ok(a)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(block6_predict_kernel<double>, dim3((unsigned)(a.n_pad / kBlock)),
-                     dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+template <typename T>
+hipError_t launch_block_next(const H6Args<T>& a, hipStream_t s) {
+  return launch_block_next<T, T>(base_view(a), s);
 }
 
-hipError_t launch_block6_narrow(const H6Args<double>& a, hipStream_t s) {
+template <typename T>
+hipError_t launch_block_predict(const H6Args<T>& a, hipStream_t s) {
+  if (!block6_ok(a)) return hipErrorInvalidValue;
+  const hipError_t e = hlaunch(block6_predict_kernel<T>, row_grid(a.n_pad), s, a);
+  if (e != hipSuccess) return e;
+  return launch_block_compact<T, T>(base_view(a), s);
+}
+
+template <typename T>
+hipError_t launch_block_narrow(const H6Args<T>& a, hipStream_t s) {
   const HBlock& b = a.blk;
   if (!block6_ok(a)) return hipErrorInvalidValue;
   if (b.cap < 1) return hipSuccess;  // (narrow_max 0: every step is wide)
@@ -546,34 +545,29 @@ hipError_t launch_block6_narrow(const H6Args<double>& a, hipStream_t s) {
     return hipErrorInvalidValue;
   const int groups = (b.cap + kNarrowGroup6 - 1) / kNarrowGroup6;
   const dim3 grid((unsigned)b.n_slices, (unsigned)(groups < 16 ? groups : 16));
-  if (a.phi)
-    hipLaunchKernelGGL((hermite6_narrow_kernel<double, true>), grid, dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((hermite6_narrow_kernel<double, false>), grid, dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  return a.phi ? hlaunch(hermite6_narrow_kernel<T, true>, grid, s, a)
+               : hlaunch(hermite6_narrow_kernel<T, false>, grid, s, a);
 }
 
-hipError_t launch_block6_wide(const H6Args<double>& a, int ipl, int groups, hipStream_t s) {
-  if (!hermite6_ipl_ok(1, ipl) || !block6_ok(a) || !a.XP || !a.VP || !a.AP || !a.PA || !a.PJ ||
-      !a.PS)
-    return hipErrorInvalidValue;
-  const int g = groups < 1 ? 1 : groups > a.n_chunks ? a.n_chunks : groups;
-  const dim3 grid((unsigned)(a.n_pad / (kBlock * ipl)), (unsigned)g);
-  if (a.phi)
-    hipLaunchKernelGGL((hermite6_eval_kernel<double, true, 1, true>), grid, dim3(kBlock), 0, s, a,
-                       0);
-  else
-    hipLaunchKernelGGL((hermite6_eval_kernel<double, false, 1, true>), grid, dim3(kBlock), 0, s, a,
-                       0);
-  return hipGetLastError();
+template <typename T>
+hipError_t launch_block_wide(const H6Args<T>& a, int ipl, int groups, hipStream_t s) {
+  if (!eval6_ok(a, ipl) || !block6_ok(a)) return hipErrorInvalidValue;
+  const dim3 grid = eval6_grid(a, ipl, groups);
+  return a.phi ? hlaunch(hermite6_eval_kernel<T, true, 1, true>, grid, s, a, 0)
+               : hlaunch(hermite6_eval_kernel<T, false, 1, true>, grid, s, a, 0);
 }
 
-hipError_t launch_block6_correct(const H6Args<double>& a, hipStream_t s) {
+template <typename T>
+hipError_t launch_block_correct(const H6Args<T>& a, hipStream_t s) {
   if (!block6_ok(a)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(block6_correct_kernel<double>, dim3((unsigned)(a.n_pad / kBlock)),
-                     dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  return hlaunch(block6_correct_kernel<T>, row_grid(a.n_pad), s, a);
 }
+
+template hipError_t launch_block_next<double>(const H6Args<double>&, hipStream_t);
+template hipError_t launch_block_predict<double>(const H6Args<double>&, hipStream_t);
+template hipError_t launch_block_narrow<double>(const H6Args<double>&, hipStream_t);
+template hipError_t launch_block_wide<double>(const H6Args<double>&, int, int, hipStream_t);
+template hipError_t launch_block_correct<double>(const H6Args<double>&, hipStream_t);
 
 #define GS_HERMITE6_INSTANTIATE(T)                                                          \
   template hipError_t launch_hermite6_predict<T>(const H6Args<T>&, hipStream_t);             \

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gs_common.h"
+
 namespace gs {
 
 // Device control block of a Hermite run: the step chain reads and advances it on the device,
@@ -226,14 +228,49 @@ hipError_t launch_hermite6_eval(const H6Args<T>& a, int ipl, int groups, bool ga
                                 hipStream_t s);
 template <typename T>
 hipError_t launch_hermite6_reduce(const H6Args<T>& a, hipStream_t s);
-// Order-6 block-step chain (fp64 only). The next-time minima, the control, the compaction and
-// the start are order 4's kernels (launch_block_next, _compact, _init on an HArgs that carries
-// blk, n_real, n_pad, A and J); these are the four that differ, enqueued in order 4's order:
-// predict-all + mark, [compact,] narrow evaluate, wide (gathered) evaluate, reduce + correct +
-// new level (mode HM_STEP or HM_OUT).
-hipError_t launch_block6_predict(const H6Args<double>& a, hipStream_t s);
-hipError_t launch_block6_narrow(const H6Args<double>& a, hipStream_t s);
-hipError_t launch_block6_wide(const H6Args<double>& a, int ipl, int groups, hipStream_t s);
-hipError_t launch_block6_correct(const H6Args<double>& a, hipStream_t s);
+// Order-6 block-step chain (fp64 only): the overloads of launch_block_next, _predict (predict-all
+// + mark, then the compaction), _narrow, _wide and _correct (mode HM_STEP or HM_OUT) for H6Args,
+// enqueued as order 4's are. The next-time minima, the control, the compaction and the start are
+// order 4's kernels on base_view(a); the predict-all, the narrow and the wide evaluate and the
+// correct kernel are the order's own.
+template <typename T>
+hipError_t launch_block_next(const H6Args<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_predict(const H6Args<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_narrow(const H6Args<T>& a, hipStream_t s);
+template <typename T>
+hipError_t launch_block_wide(const H6Args<T>& a, int ipl, int groups, hipStream_t s);
+template <typename T>
+hipError_t launch_block_correct(const H6Args<T>& a, hipStream_t s);
+
+// What order 4's kernels read of an order-6 run: the control (ctrl, wgmin, n_pad) and the block
+// state (blk, n_real, n_pad).
+template <typename T>
+HArgs<T, T> base_view(const H6Args<T>& a) {
+  HArgs<T, T> c{};
+  c.ctrl = a.ctrl;
+  c.wgmin = a.wgmin;
+  c.blk = a.blk;
+  c.n_real = a.n_real;
+  c.n_pad = a.n_pad;
+  return c;
+}
+
+#ifdef __HIPCC__
+// Launch helpers of both kernel files: workgroups of kForceBlock threads.
+template <typename... P, typename... A>
+hipError_t hlaunch(void (*kernel)(P...), dim3 grid, hipStream_t s, const A&... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kForceBlock), 0, s, args...);
+  return hipGetLastError();
+}
+
+// Workgroups of one thread per row.
+inline dim3 row_grid(int64_t rows) { return dim3((unsigned)(rows / kForceBlock)); }
+
+inline int clamp_groups(int groups, int n_chunks) {
+  return groups < 1 ? 1 : groups > n_chunks ? n_chunks : groups;
+}
+#endif
 
 }  // namespace gs

@@ -746,6 +746,64 @@ def level_lean(dt_want, valid, dt):
     return float(np.abs(e - np.rint(e)).min()) if e.size else float("inf")
 
 
+def _simulate_block(pos, vel, start, advance, dt, t_end, eta, max_level, check, levels,
+                    body_times, stats):
+    """The block schedule of both orders: the checks, the block state, the due set, the level
+    rule, the log and the stats. The order's own part is two callables: start(x, v) evaluates
+    the state and returns the carried rows, a and j first; advance(x, v, rows, act, h) takes the
+    due bodies `act` over the steps h (n,) from every body's own time (predict, evaluate their
+    rows, correct, write the state) and returns (dt_want, valid) of each."""
+    if not eta > 0:
+        raise ValueError("block steps need eta > 0")
+    L = int(max_level)
+    if not 0 <= L <= 40:
+        raise ValueError("max_level must be in 0..40")
+    macro = int(round(t_end / dt))
+    if macro * dt != t_end:
+        raise ValueError("t_end must be a whole multiple of dt")
+    x = np.array(pos, dtype=np.float64, copy=True)
+    v = np.array(vel, dtype=np.float64, copy=True)
+    n = x.shape[0]
+    rows = start(x, v)
+    a, j = rows[:2]
+    tb = (np.zeros(n, dtype=np.int64) if body_times is None else
+          np.array(body_times, dtype=np.int64))
+    lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
+           np.array(levels, dtype=np.int32))
+    if lev.shape != (n,) or tb.shape != (n,) or (lev < 0).any() or (lev > L).any() or \
+            (tb < 0).any() or (tb % (np.int64(1) << (L - lev).astype(np.int64))).any():
+        raise ValueError("block state: level out of 0..max_level, or a body time that is no "
+                         "multiple of its step")
+    lean = float("inf")
+    if stats is not None and levels is None:
+        an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            first = 0.5 * eta * an / jn
+        lean = level_lean(first, (jn > 0) & np.isfinite(first), dt)
+    level_max, active = int(lev.max()) if n else 0, []
+    end = macro << L
+    log, clamped = [], 0
+    while tb.min() < end:
+        stp = np.int64(1) << (L - lev).astype(np.int64)
+        t_next = int((tb + stp).min())
+        act = np.nonzero(tb + stp == t_next)[0]
+        h = dt * np.ldexp((t_next - tb).astype(np.float64), -L)
+        want, valid = advance(x, v, rows, act, h)
+        tb[act] = t_next
+        lev[act], hit = block_new_levels(lev[act], want, valid, t_next, dt, L)
+        clamped += int(hit.sum())
+        log.append((t_next, int(len(act))))
+        if stats is not None:
+            lean = min(lean, level_lean(want, valid, dt))
+            level_max = max(level_max, int(lev[act].max()))
+            active.append(act)
+        if check is not None:
+            check(tb, lev)
+    if stats is not None:
+        stats.update(active=active, lean=lean, level_max=level_max)
+    return x, v, lev.copy(), log, clamped
+
+
 def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI, cutoff=1e-10,
                            softening=0.0, check=None, sources=None, levels=None,
                            body_times=None, stats=None, radius=None, collisions="off",
@@ -771,47 +829,20 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
         raise ValueError("collisions must be off, detect or merge")
     if collisions != "off" and sources is not None:
         raise ValueError("collisions need every body's predicted state (no sources)")
-    if not eta > 0:
-        raise ValueError("block steps need eta > 0")
-    L = int(max_level)
-    if not 0 <= L <= 40:
-        raise ValueError("max_level must be in 0..40")
-    macro = int(round(t_end / dt))
-    if macro * dt != t_end:
-        raise ValueError("t_end must be a whole multiple of dt")
-    x = np.array(pos, dtype=np.float64, copy=True)
-    v = np.array(vel, dtype=np.float64, copy=True)
-    n = x.shape[0]
     mass = np.asarray(mass, dtype=np.float64)
     src = None if sources is None else np.unique(_source_columns(mass, sources))
-    a, j = acc_jerk(x, v, mass, G, cutoff, softening, sources=src)
-    near = None if collisions == "off" else _Closest(n, radius, cutoff, softening)
-    if near is not None:
-        near.see(x)
-    tb = (np.zeros(n, dtype=np.int64) if body_times is None else
-          np.array(body_times, dtype=np.int64))
-    lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
-           np.array(levels, dtype=np.int32))
-    if lev.shape != (n,) or tb.shape != (n,) or (lev < 0).any() or (lev > L).any() or \
-            (tb < 0).any() or (tb % (np.int64(1) << (L - lev).astype(np.int64))).any():
-        raise ValueError("block state: level out of 0..max_level, or a body time that is no "
-                         "multiple of its step")
-    lean = float("inf")
-    if stats is not None and levels is None:
-        an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            first = 0.5 * eta * an / jn
-        lean = level_lean(first, (jn > 0) & np.isfinite(first), dt)
-    level_max, active = int(lev.max()) if n else 0, []
-    end = macro << L
-    log, clamped = [], 0
-    while tb.min() < end:
-        stp = np.int64(1) << (L - lev).astype(np.int64)
-        t_next = int((tb + stp).min())
-        act = np.nonzero(tb + stp == t_next)[0]
+    near = None if collisions == "off" else _Closest(len(mass), radius, cutoff, softening)
+
+    def start(x, v):
+        if near is not None:
+            near.see(x)
+        return acc_jerk(x, v, mass, G, cutoff, softening, sources=src)
+
+    def advance(x, v, rows, act, h):
+        a, j = rows
         # the bodies whose predicted state is read: all, or the due ones and the sources
-        need = np.arange(n) if src is None else np.union1d(act, src)
-        h = dt * np.ldexp((t_next - tb[need]).astype(np.float64), -L)
+        need = np.arange(len(x)) if src is None else np.union1d(act, src)
+        h = h[need]
         hc = h[:, None]
         xn, vn, an_, jn_ = x[need], v[need], a[need], j[need]
         xp = xn + (vn * hc + (an_ * (hc * hc / 2) + jn_ * (hc * hc * hc / 6)))
@@ -826,22 +857,13 @@ def simulate_hermite_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI,
         v1 = v0 + ((a0 + a1) * (ha / 2) + (j0 - j1) * (ha * ha / 12))
         x[act] = x[act] + ((v0 + v1) * (ha / 2) + (a0 - a1) * (ha * ha / 12))
         v[act], a[act], j[act] = v1, a1, j1
-        want, valid = hermite_dt_bodies(a0, j0, a1, j1, h[at], eta)
-        tb[act] = t_next
-        lev[act], hit = block_new_levels(lev[act], want, valid, t_next, dt, L)
-        clamped += int(hit.sum())
-        log.append((t_next, int(len(act))))
-        if stats is not None:
-            lean = min(lean, level_lean(want, valid, dt))
-            level_max = max(level_max, int(lev[act].max()))
-            active.append(act)
-        if check is not None:
-            check(tb, lev)
-    if stats is not None:
-        stats.update(active=active, lean=lean, level_max=level_max)
+        return hermite_dt_bodies(a0, j0, a1, j1, h[at], eta)
+
+    out = _simulate_block(pos, vel, start, advance, dt, t_end, eta, max_level, check, levels,
+                          body_times, stats)
     if near is not None and record is not None:
         near.export(record)
-    return x, v, lev.copy(), log, clamped
+    return out
 
 
 # ---- 6th-order Hermite with individual block time steps --------------------------------------
@@ -899,42 +921,14 @@ def simulate_hermite6_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI
     the step each wants (hermite6_dt_bodies) and applies the level rule of order 4
     (block_new_levels). t_end, check, levels, body_times, stats and the return value are those of
     simulate_hermite_block; there are no sources and no collisions."""
-    if not eta > 0:
-        raise ValueError("block steps need eta > 0")
-    L = int(max_level)
-    if not 0 <= L <= 40:
-        raise ValueError("max_level must be in 0..40")
-    macro = int(round(t_end / dt))
-    if macro * dt != t_end:
-        raise ValueError("t_end must be a whole multiple of dt")
-    x = np.array(pos, dtype=np.float64, copy=True)
-    v = np.array(vel, dtype=np.float64, copy=True)
-    n = x.shape[0]
     mass = np.asarray(mass, dtype=np.float64)
-    a, j, s = hermite6_start(x, v, mass, G, cutoff, softening)
-    c = np.zeros_like(a)
-    tb = (np.zeros(n, dtype=np.int64) if body_times is None else
-          np.array(body_times, dtype=np.int64))
-    lev = (block_first_levels(a, j, dt, eta, L) if levels is None else
-           np.array(levels, dtype=np.int32))
-    if lev.shape != (n,) or tb.shape != (n,) or (lev < 0).any() or (lev > L).any() or \
-            (tb < 0).any() or (tb % (np.int64(1) << (L - lev).astype(np.int64))).any():
-        raise ValueError("block state: level out of 0..max_level, or a body time that is no "
-                         "multiple of its step")
-    lean = float("inf")
-    if stats is not None and levels is None:
-        an, jn = np.sqrt((a * a).sum(1)), np.sqrt((j * j).sum(1))
-        with np.errstate(divide="ignore", invalid="ignore"):
-            first = 0.5 * eta * an / jn
-        lean = level_lean(first, (jn > 0) & np.isfinite(first), dt)
-    level_max, active = int(lev.max()) if n else 0, []
-    end = macro << L
-    log, clamped = [], 0
-    while tb.min() < end:
-        stp = np.int64(1) << (L - lev).astype(np.int64)
-        t_next = int((tb + stp).min())
-        act = np.nonzero(tb + stp == t_next)[0]
-        h = dt * np.ldexp((t_next - tb).astype(np.float64), -L)
+
+    def start(x, v):
+        a, j, s = hermite6_start(x, v, mass, G, cutoff, softening)
+        return a, j, s, np.zeros_like(a)
+
+    def advance(x, v, rows, act, h):
+        a, j, s, c = rows
         hc = h[:, None]
         h2, h3, h4, h5 = (hc * hc) / 2, (hc * hc * hc) / 6, (hc * hc * hc * hc) / 24, \
             (hc * hc * hc * hc * hc) / 120
@@ -950,16 +944,7 @@ def simulate_hermite6_block(pos, vel, mass, dt, t_end, eta, max_level=24, G=G_SI
         want, valid = hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, h[act], eta)
         c[act] = hermite6_high(a0, j0, s0, a1, j1, s1, h[act])[0]
         v[act], a[act], j[act], s[act] = v1, a1, j1, s1
-        tb[act] = t_next
-        lev[act], hit = block_new_levels(lev[act], want, valid, t_next, dt, L)
-        clamped += int(hit.sum())
-        log.append((t_next, int(len(act))))
-        if stats is not None:
-            lean = min(lean, level_lean(want, valid, dt))
-            level_max = max(level_max, int(lev[act].max()))
-            active.append(act)
-        if check is not None:
-            check(tb, lev)
-    if stats is not None:
-        stats.update(active=active, lean=lean, level_max=level_max)
-    return x, v, lev.copy(), log, clamped
+        return want, valid
+
+    return _simulate_block(pos, vel, start, advance, dt, t_end, eta, max_level, check, levels,
+                           body_times, stats)

@@ -675,14 +675,29 @@ class HermiteCpuEngine:
         self.level_max = int(self.lev.max())
 
     def _block_step(self) -> None:
-        """One block step (the rules of oracle.simulate_hermite_block, in the run's dtype)."""
+        """One block step: the schedule and the level rule of oracle._simulate_block around the
+        order's own predict, evaluate and correct in the run's dtype (_advance4, _advance6)."""
         from ..ops import oracle
 
-        cfg, T, L = self.cfg, self.np_dtype, self.L
+        cfg, L = self.cfg, self.L
         stp = np.int64(1) << (L - self.lev).astype(np.int64)
         t_next = int((self.tb + stp).min())
         act = np.nonzero(self.tb + stp == t_next)[0]
         hd = cfg.dt * np.ldexp((t_next - self.tb).astype(np.float64), -L)
+        want, valid = (self._advance6 if self.order == 6 else self._advance4)(act, hd)
+        self.tb[act] = t_next
+        self.lev[act], hit = oracle.block_new_levels(self.lev[act], want, valid, t_next, cfg.dt, L)
+        self.level_clamped += int(hit.sum())
+        self.level_max = max(self.level_max, int(self.lev.max()))
+        self.body_steps += len(act)
+        self.block_log.append((t_next, len(act)))
+
+    def _advance4(self, act, hd):
+        """Order 4: the bodies `act` over the steps hd (n,) from every body's own time; the step
+        each wants (the rules of oracle.simulate_hermite_block)."""
+        from ..ops import oracle
+
+        T = self.np_dtype
         h = hd.astype(T)[:, None]
         x, v, a, j = self.X[:, :3], self.V[:, :3], self.A[:, :3], self.J[:, :3]
         XP, VP = self.X.copy(), np.zeros_like(self.V)
@@ -697,27 +712,15 @@ class HermiteCpuEngine:
         v1 = v0 + ((a0 + a1) * (ha / T(2)) + (j0 - j1) * ((ha * ha) / T(12)))
         self.X[act, :3] = x[act] + ((v0 + v1) * (ha / T(2)) + (a0 - a1) * ((ha * ha) / T(12)))
         self.V[act, :3], self.A[act, :3], self.J[act, :3] = v1, a1, j1
-        want, valid = oracle.hermite_dt_bodies(a0.astype(np.float64), j0.astype(np.float64),
-                                               a1.astype(np.float64), j1.astype(np.float64),
-                                               hd[act], cfg.eta)
-        self.tb[act] = t_next
-        for m, i in enumerate(act):
-            self.lev[i], c = oracle.block_new_level(int(self.lev[i]), want[m], bool(valid[m]),
-                                                    t_next, cfg.dt, L)
-            self.level_clamped += c
-        self.level_max = max(self.level_max, int(self.lev.max()))
-        self.body_steps += len(act)
-        self.block_log.append((t_next, len(act)))
+        return oracle.hermite_dt_bodies(a0.astype(np.float64), j0.astype(np.float64),
+                                        a1.astype(np.float64), j1.astype(np.float64),
+                                        hd[act], self.cfg.eta)
 
-    def _block_step6(self) -> None:
-        """One block step of order 6 (the rules of oracle.simulate_hermite6_block; fp64)."""
+    def _advance6(self, act, hd):
+        """Order 6 (fp64), as _advance4 (the rules of oracle.simulate_hermite6_block)."""
         from ..ops import oracle
 
-        cfg, L, n = self.cfg, self.L, self.cfg.n
-        stp = np.int64(1) << (L - self.lev).astype(np.int64)
-        t_next = int((self.tb + stp).min())
-        act = np.nonzero(self.tb + stp == t_next)[0]
-        hd = cfg.dt * np.ldexp((t_next - self.tb).astype(np.float64), -L)
+        n = self.cfg.n
         h = hd[:, None]
         h2, h3, h4, h5 = (h * h) / 2, (h * h * h) / 6, (h * h * h * h) / 24, \
             (h * h * h * h * h) / 120
@@ -738,15 +741,10 @@ class HermiteCpuEngine:
         a0, j0, s0, v0 = a[act], j[act], s[act], v[act]
         v1 = v0 + ((a0 + a1) * hh + ((j0 - j1) * h10 + (s0 + s1) * h120))
         self.X[act, :3] = x[act] + ((v0 + v1) * hh + ((a0 - a1) * h10 + (j0 + j1) * h120))
-        want, valid = oracle.hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, hd[act], cfg.eta)
+        want, valid = oracle.hermite6_dt_bodies(a0, j0, s0, a1, j1, s1, hd[act], self.cfg.eta)
         self.C[act, :3] = oracle.hermite6_high(a0, j0, s0, a1, j1, s1, hd[act])[0]
         self.V[act, :3], self.A[act, :3], self.J[act, :3], self.S[act, :3] = v1, a1, j1, s1
-        self.tb[act] = t_next
-        self.lev[act], hit = oracle.block_new_levels(self.lev[act], want, valid, t_next, cfg.dt, L)
-        self.level_clamped += int(hit.sum())
-        self.level_max = max(self.level_max, int(self.lev.max()))
-        self.body_steps += len(act)
-        self.block_log.append((t_next, len(act)))
+        return want, valid
 
     def load(self, b: BodySet, acc=None, jerk=None, t: float = 0.0,
              dt_next: Optional[float] = None, dt_min: Optional[float] = None,
@@ -789,7 +787,7 @@ class HermiteCpuEngine:
                     return
                 macro = int(self.tb.min()) >> self.L
                 while int(self.tb.min()) < (macro + 1) << self.L:
-                    self._block_step6() if self.order == 6 else self._block_step()
+                    self._block_step()
                 self.t = cfg.dt * (macro + 1)
                 self.dt_last = cfg.dt
                 self.k += 1
