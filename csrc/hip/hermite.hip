@@ -43,6 +43,9 @@ struct gs_hermite {
   size_t esz = 4;  // bytes per element of the state rows (x, v, a, j, the outputs)
   size_t psz = 4;  // ... of the predicted rows and the partial sums (mixed: 4 against esz 8)
   hipStream_t stream = nullptr;
+  // Device buffers are owned in groups (gs_devmem.h; docs/DESIGN.md §24): each is complete or
+  // empty, and a pointer is null exactly while its group does not hold it.
+  gs::rt::DevMem base;  // while the engine lives: the buffers from here to `nonfinite`
   void *X = nullptr, *V = nullptr, *A = nullptr, *J = nullptr, *XP = nullptr, *VP = nullptr;
   void* XL = nullptr;  // mixed: lo rows of the predicted position
   void *PA = nullptr, *PJ = nullptr, *a_out = nullptr, *j_out = nullptr;
@@ -57,11 +60,18 @@ struct gs_hermite {
   bool block = false;
   int32_t max_level = 24, narrow_max = 0;
   gs::HBlock blk{};
+  gs::rt::DevMem blockg;  // while `block`: blk.bc, tb, level, list, wgcount, wgnext
+  // while `block` with blk.cap > 0 slots, the partials of the narrow path (size_narrow): blk.NA,
+  // blk.NJ, the snap's NS for order 6, the neighbour's NNI where collisions are on
+  gs::rt::DevMem narrow;
+  void* NS = nullptr;
+  int32_t* NNI = nullptr;
   int64_t macro0 = 0;  // macro steps of dt the run stood at when its state was set
   // collisions (gs_hermite_set_collisions): 0 off, 1 record, 2 record and stop the shared step
   int32_t nn = 0;
+  gs::rt::DevMem coll;  // while `nn`: the eight below
   void* R = nullptr;  // radii, state precision
-  int32_t *PN = nullptr, *NNI = nullptr, *nn_i = nullptr, *ca_i = nullptr, *nn_out = nullptr;
+  int32_t *PN = nullptr, *nn_i = nullptr, *ca_i = nullptr, *nn_out = nullptr;
   double *nn_q = nullptr, *ca_q = nullptr, *q_out = nullptr;
   // ranks: the rows this one owns, and every rank's (in units of 1024 rows)
   int64_t row0 = 0, n_loc = 0;
@@ -80,7 +90,7 @@ struct gs_hermite {
   // the snap partials and output
   int32_t order = 4;
   void *S = nullptr, *C = nullptr, *AP = nullptr, *PS = nullptr, *s_out = nullptr;
-  void* NS = nullptr;  // order 6 in block mode: the snap partials of the narrow path
+  gs::rt::DevMem six;  // while `order` is 6: the five above
 };
 
 namespace {
@@ -580,26 +590,14 @@ int clear_records(gs_hermite* h, bool latest) {
   return 0;
 }
 
-// The neighbour partials of the narrow path, the one place that frees and allocates them: they
-// exist exactly while block mode has narrow slots and collisions (`nn`) are on.
-int size_nni(gs_hermite* h, bool nn) {
-  if (h->NNI) GS_HIP(hipFree(h->NNI));
-  h->NNI = nullptr;
-  if (h->block && h->blk.cap > 0 && nn)
-    GS_HIP(hipMalloc((void**)&h->NNI,
-                     (size_t)h->blk.n_slices * (size_t)h->blk.cap * sizeof(int32_t)));
-  return 0;
-}
+using gs::rt::DevMem;
 
-void free_nn(gs_hermite* h) {
-  for (void* p : {h->R, (void*)h->PN, (void*)h->nn_i, (void*)h->ca_i, (void*)h->nn_out,
-                  (void*)h->nn_q, (void*)h->ca_q, (void*)h->q_out})
-    if (p) (void)hipFree(p);
-  h->R = nullptr;
-  h->PN = h->nn_i = h->ca_i = h->nn_out = nullptr;
-  h->nn_q = h->ca_q = h->q_out = nullptr;
-  h->nn = 0;
-  (void)size_nni(h, false);
+// A buffer of group g with every byte set to `fill`, on the engine's stream.
+template <typename T>
+int dev_buf(gs_hermite* h, DevMem& g, T** slot, size_t bytes, const char* tag, int fill = 0) {
+  if (g.alloc(slot, bytes, tag)) return -1;
+  GS_HIP(hipMemsetAsync(*slot, fill, bytes, h->stream));
+  return 0;
 }
 
 int set_wgmin(gs_hermite* h, double first) {
@@ -641,37 +639,45 @@ int32_t default_narrow_max(const gs_hermite* h) {
   return (int32_t)d;
 }
 
-void free_block(gs_hermite* h) {
-  for (void* p : {(void*)h->blk.bc, (void*)h->blk.tb, (void*)h->blk.level, (void*)h->blk.list,
-                  (void*)h->blk.wgcount, (void*)h->blk.wgnext, h->blk.NA, h->blk.NJ, h->NS})
-    if (p) (void)hipFree(p);
-  h->blk = gs::HBlock{};
-  h->NS = nullptr;
-  (void)size_nni(h, h->nn != 0);  // (no slots: freed)
+// The control block's narrow_max follows the host's.
+int push_narrow_max(gs_hermite* h) {
+  gs::HermiteBlockCtrl c;
+  if (read_bctrl(h, &c)) return -1;
+  c.narrow_max = h->narrow_max;
+  return write_bctrl(h, c);
 }
 
-// (Re)allocate the narrow partial buffer for narrow_max slots.
+// The partials of the narrow path for `cap` slots (0 outside block mode), the one place that
+// sizes them: acceleration and jerk, the snap for order 6, the neighbour where collisions (`nn`)
+// are on. A resize that fails leaves no slots, on the host and in the control block: every step
+// then takes the wide path.
+int size_narrow(gs_hermite* h, int32_t cap, bool nn) {
+  const size_t slots = (size_t)h->blk.n_slices * (size_t)cap, bytes = slots * 4 * h->psz;
+  const int rc = h->narrow.rebuild([&](DevMem& g) {
+    return cap > 0 && (g.alloc(&h->blk.NA, bytes, "NA") || g.alloc(&h->blk.NJ, bytes, "NJ") ||
+                       (h->order == 6 && g.alloc(&h->NS, bytes, "NS")) ||
+                       (nn && g.alloc(&h->NNI, slots * sizeof(int32_t), "NNI")));
+  });
+  h->blk.cap = h->narrow_max = rc ? 0 : cap;
+  if (rc && h->blk.bc) (void)push_narrow_max(h);  // (it sets no error unless it fails itself)
+  return rc;
+}
+
+// Block mode off: the narrow slots and the block arrays go.
+void drop_block(gs_hermite* h) {
+  (void)size_narrow(h, 0, false);
+  h->blockg.release();
+  h->blk = gs::HBlock{};
+  h->block = false;
+}
+
+// Narrow partials for narrow_max slots (< 0: the default), and the control block told.
 int set_narrow(gs_hermite* h, int32_t narrow_max) {
   if (narrow_max < 0) narrow_max = default_narrow_max(h);
   if (narrow_max > h->n_pad) narrow_max = (int32_t)h->n_pad;
   GS_HIP(hipStreamSynchronize(h->stream));
-  if (h->blk.NA) GS_HIP(hipFree(h->blk.NA));
-  if (h->blk.NJ) GS_HIP(hipFree(h->blk.NJ));
-  if (h->NS) GS_HIP(hipFree(h->NS));
-  h->blk.NA = h->blk.NJ = h->NS = nullptr;
-  h->blk.cap = narrow_max;
-  h->narrow_max = narrow_max;
-  if (narrow_max > 0) {
-    const size_t bytes = (size_t)h->blk.n_slices * (size_t)narrow_max * 4 * h->psz;
-    GS_HIP(hipMalloc(&h->blk.NA, bytes));
-    GS_HIP(hipMalloc(&h->blk.NJ, bytes));
-    if (h->order == 6) GS_HIP(hipMalloc(&h->NS, bytes));  // (the snap partials)
-  }
-  if (size_nni(h, h->nn != 0)) return -1;
-  gs::HermiteBlockCtrl c;
-  if (read_bctrl(h, &c)) return -1;
-  c.narrow_max = narrow_max;
-  return write_bctrl(h, c);
+  if (size_narrow(h, narrow_max, h->nn != 0)) return -1;
+  return push_narrow_max(h);
 }
 
 // Control block of a block run that stands at `macro` whole steps of dt, counters zero.
@@ -792,18 +798,15 @@ int derivs_active(gs_hermite* h, A a, const int32_t* idx, int32_t n_idx, int32_t
 }
 
 // The arrays order 6 adds to the run's (snap and crackle rows, the predicted acceleration, the
-// snap output, the snap partials), the one place that frees and allocates them: they exist
-// exactly while the order is 6 (`on`).
-int size_order6(gs_hermite* h, bool on) {
-  for (void** p : {&h->S, &h->C, &h->AP, &h->s_out, &h->PS}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    if (!on) continue;
-    const bool rows = p != &h->PS;  // (the partials: a row per chunk, written before they are read)
-    GS_HIP(hipMalloc(p, rows_bytes(h) * (rows ? 1 : (size_t)h->n_chunks)));
-    if (rows) GS_HIP(hipMemsetAsync(*p, 0, rows_bytes(h), h->stream));
-  }
-  if (on) GS_HIP(hipStreamSynchronize(h->stream));
+// snap output, the snap partials), zeroed but for the partials (a row per chunk, written before
+// they are read): they exist exactly while the order is 6.
+int fill_order6(gs_hermite* h, DevMem& g) {
+  const size_t rb = rows_bytes(h);
+  if (dev_buf(h, g, &h->S, rb, "S") || dev_buf(h, g, &h->C, rb, "C") ||
+      dev_buf(h, g, &h->AP, rb, "AP") || dev_buf(h, g, &h->s_out, rb, "s_out") ||
+      g.alloc(&h->PS, rb * (size_t)h->n_chunks, "PS"))
+    return -1;
+  GS_HIP(hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -990,22 +993,20 @@ int gs_hermite_create(const gs_config* cfg, gs_hermite** out) {
   GS_HIP(hipSetDevice(cfg->device));
   GS_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   GS_HIP(hipEventCreateWithFlags(&h->ev, hipEventDisableTiming));
-  const size_t rb = rows_bytes(h), pb = (size_t)h->n_loc * 4 * h->psz;  // (partials: own rows)
-  for (void** p : {&h->X, &h->V, &h->A, &h->J, &h->a_out, &h->j_out}) {
-    GS_HIP(hipMalloc(p, rb));
-    GS_HIP(hipMemsetAsync(*p, 0, rb, h->stream));
-  }
-  for (void** p : {&h->XP, &h->VP, &h->XL}) {
-    if (p == &h->XL && !is_mixed(h)) continue;
-    GS_HIP(hipMalloc(p, pair_rows_bytes(h)));
-    GS_HIP(hipMemsetAsync(*p, 0, pair_rows_bytes(h), h->stream));
-  }
-  GS_HIP(hipMalloc(&h->PA, pb * (size_t)h->n_chunks));
-  GS_HIP(hipMalloc(&h->PJ, pb * (size_t)h->n_chunks));
-  GS_HIP(hipMalloc((void**)&h->ctrl, sizeof(gs::HermiteCtrl)));
-  GS_HIP(hipMalloc((void**)&h->wgmin, (size_t)nwg(h) * sizeof(double)));
-  GS_HIP(hipMalloc((void**)&h->mass_dev, (size_t)h->n_pad * sizeof(double)));
-  GS_HIP(hipMalloc((void**)&h->nonfinite, sizeof(unsigned long long)));
+  const size_t rb = rows_bytes(h), prb = pair_rows_bytes(h);
+  const size_t pb = (size_t)h->n_loc * 4 * h->psz * (size_t)h->n_chunks;  // (partials: own rows)
+  DevMem& g = h->base;
+  if (dev_buf(h, g, &h->X, rb, "X") || dev_buf(h, g, &h->V, rb, "V") ||
+      dev_buf(h, g, &h->A, rb, "A") || dev_buf(h, g, &h->J, rb, "J") ||
+      dev_buf(h, g, &h->a_out, rb, "a_out") || dev_buf(h, g, &h->j_out, rb, "j_out") ||
+      dev_buf(h, g, &h->XP, prb, "XP") || dev_buf(h, g, &h->VP, prb, "VP") ||
+      (is_mixed(h) && dev_buf(h, g, &h->XL, prb, "XL")) ||
+      g.alloc(&h->PA, pb, "PA") || g.alloc(&h->PJ, pb, "PJ") ||
+      g.alloc(&h->ctrl, sizeof(gs::HermiteCtrl), "ctrl") ||
+      g.alloc(&h->wgmin, (size_t)nwg(h) * sizeof(double), "wgmin") ||
+      g.alloc(&h->mass_dev, (size_t)h->n_pad * sizeof(double), "mass") ||
+      g.alloc(&h->nonfinite, sizeof(unsigned long long), "nonfinite"))
+    return -1;
   GS_HIP(hipStreamSynchronize(h->stream));
   h->mass_host.assign((size_t)h->n, 0.0);
   if (set_wgmin(h, std::numeric_limits<double>::infinity()) ||
@@ -1022,14 +1023,9 @@ int gs_hermite_destroy(gs_hermite* h) {
   if (ncclComm_t c = h->comm_live.exchange(nullptr)) (void)ncclCommDestroy(c);
   for (hipEvent_t e : h->ring) (void)hipEventDestroy(e);
   if (h->ev) (void)hipEventDestroy(h->ev);
-  for (void* p : {h->X, h->V, h->A, h->J, h->XP, h->VP, h->XL, h->a_out, h->j_out, h->PA, h->PJ,
-                  (void*)h->ctrl, (void*)h->wgmin, (void*)h->mass_dev, (void*)h->nonfinite})
-    if (p) (void)hipFree(p);
-  free_block(h);
-  free_nn(h);
-  (void)size_order6(h, false);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t stream = h->stream;
+  delete h;  // (the five groups free their buffers)
+  if (stream) (void)hipStreamDestroy(stream);
   return 0;
 }
 
@@ -1171,8 +1167,7 @@ static int set_block_mode(gs_hermite* h, int32_t on, int32_t max_level, int32_t 
   GS_HIP(hipSetDevice(h->cfg.device));
   if (!on) {
     GS_HIP(hipStreamSynchronize(h->stream));
-    free_block(h);
-    h->block = false;
+    drop_block(h);
     return 0;
   }
   if (multi(h)) {
@@ -1198,25 +1193,27 @@ static int set_block_mode(gs_hermite* h, int32_t on, int32_t max_level, int32_t 
     return -1;
   }
   GS_HIP(hipStreamSynchronize(h->stream));
-  free_block(h);
+  drop_block(h);
   h->max_level = max_level;
   const size_t np = (size_t)h->n_pad, wg = (size_t)nwg(h);
-  GS_HIP(hipMalloc((void**)&h->blk.bc, sizeof(gs::HermiteBlockCtrl)));
-  GS_HIP(hipMalloc((void**)&h->blk.tb, np * sizeof(int64_t)));
-  GS_HIP(hipMalloc((void**)&h->blk.level, np * sizeof(int32_t)));
-  GS_HIP(hipMalloc((void**)&h->blk.list, np * sizeof(int32_t)));
-  GS_HIP(hipMalloc((void**)&h->blk.wgcount, wg * sizeof(int32_t)));
-  GS_HIP(hipMalloc((void**)&h->blk.wgnext, wg * sizeof(int64_t)));
-  GS_HIP(hipMemsetAsync(h->blk.tb, 0, np * sizeof(int64_t), h->stream));
-  GS_HIP(hipMemsetAsync(h->blk.level, 0, np * sizeof(int32_t), h->stream));
-  GS_HIP(hipMemsetAsync(h->blk.list, 0, np * sizeof(int32_t), h->stream));
-  GS_HIP(hipMemsetAsync(h->blk.wgcount, 0, wg * sizeof(int32_t), h->stream));
-  h->blk.slice = gs::hermite_narrow_slice(h->n_pad);
-  h->blk.n_slices = (int32_t)((h->n_pad + h->blk.slice - 1) / h->blk.slice);
+  gs::HBlock& b = h->blk;
+  const int built = h->blockg.rebuild([&](DevMem& g) {
+    return g.alloc(&b.bc, sizeof(gs::HermiteBlockCtrl), "block ctrl") ||
+           dev_buf(h, g, &b.tb, np * sizeof(int64_t), "block tb") ||
+           dev_buf(h, g, &b.level, np * sizeof(int32_t), "block level") ||
+           dev_buf(h, g, &b.list, np * sizeof(int32_t), "block list") ||
+           dev_buf(h, g, &b.wgcount, wg * sizeof(int32_t), "block wgcount") ||
+           g.alloc(&b.wgnext, wg * sizeof(int64_t), "block wgnext");
+  });
+  b.slice = gs::hermite_narrow_slice(h->n_pad);
+  b.n_slices = (int32_t)((h->n_pad + b.slice - 1) / b.slice);
+  // (block mode is on once its arrays and the narrow slots stand; else it stays off, with neither)
+  if (built || reset_bctrl(h, 0) || set_narrow(h, -1)) {
+    drop_block(h);
+    return -1;
+  }
   h->block = true;
-  h->narrow_max = 0;
-  if (reset_bctrl(h, 0)) return -1;
-  return set_narrow(h, -1);
+  return 0;
 }
 
 int gs_hermite_set_block(gs_hermite* h, int32_t on, int32_t max_level) {
@@ -1348,9 +1345,11 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
   GS_HIP(hipSetDevice(h->cfg.device));
   GS_HIP(hipStreamSynchronize(h->stream));
   if (!on) {
-    free_nn(h);
-    if (launch_shape(h)) return -1;
-    return update_ctrl(h, 0);
+    h->coll.release();
+    h->nn = 0;
+    const int narrow = size_narrow(h, h->blk.cap, false);  // (without the neighbour partials)
+    if (launch_shape(h) || update_ctrl(h, 0)) return -1;
+    return narrow;
   }
   if (multi(h)) {
     gs_set_error("hermite collisions run on one rank");
@@ -1362,19 +1361,21 @@ int gs_hermite_set_collisions(gs_hermite* h, int32_t on) {
     return -1;
   }
   if (!h->nn) {
-    const size_t np = (size_t)h->n_pad;
-    GS_HIP(hipMalloc(&h->R, np * h->esz));
-    GS_HIP(hipMemsetAsync(h->R, 0, np * h->esz, h->stream));
-    GS_HIP(hipMalloc((void**)&h->PN, np * (size_t)h->n_chunks * sizeof(int32_t)));
-    for (int32_t** p : {&h->nn_i, &h->ca_i, &h->nn_out}) {
-      GS_HIP(hipMalloc((void**)p, np * sizeof(int32_t)));
-      GS_HIP(hipMemsetAsync(*p, 0xff, np * sizeof(int32_t), h->stream));
+    const size_t np = (size_t)h->n_pad, ib = np * sizeof(int32_t), qb = np * sizeof(double);
+    const int built = h->coll.rebuild([&](DevMem& g) {
+      return dev_buf(h, g, &h->R, np * h->esz, "R") ||
+             g.alloc(&h->PN, ib * (size_t)h->n_chunks, "PN") ||  // (the indices: -1, all bits set)
+             dev_buf(h, g, &h->nn_i, ib, "nn_i", 0xff) ||
+             dev_buf(h, g, &h->ca_i, ib, "ca_i", 0xff) ||
+             dev_buf(h, g, &h->nn_out, ib, "nn_out", 0xff) ||
+             dev_buf(h, g, &h->nn_q, qb, "nn_q") || dev_buf(h, g, &h->ca_q, qb, "ca_q") ||
+             dev_buf(h, g, &h->q_out, qb, "q_out");
+    });
+    // (collisions are on once their arrays and the narrow path's neighbour partials stand)
+    if (built || size_narrow(h, h->blk.cap, true)) {
+      h->coll.release();
+      return -1;
     }
-    for (double** p : {&h->nn_q, &h->ca_q, &h->q_out}) {
-      GS_HIP(hipMalloc((void**)p, np * sizeof(double)));
-      GS_HIP(hipMemsetAsync(*p, 0, np * sizeof(double), h->stream));
-    }
-    if (size_nni(h, true)) return -1;
   }
   h->nn = on;
   if (launch_shape(h)) return -1;
@@ -1415,12 +1416,18 @@ int gs_hermite_set_order(gs_hermite* h, int32_t order) {
     gs_set_error("hermite set_order: switch block steps off first (gs_hermite_set_block6)");
     return -1;
   }
+  // (the order and its launch shape change once order 6's arrays stand; a switch that fails
+  // leaves the order, the shape and the arrays of before)
+  if (order == 6 && was != 6 && h->six.rebuild([&](DevMem& g) { return fill_order6(h, g); }))
+    return -1;
   h->order = order;
   if (launch_shape(h)) {
     h->order = was;
+    if (was != 6) h->six.release();
     return -1;
   }
-  return order == was ? 0 : size_order6(h, order == 6);
+  if (order != 6) h->six.release();
+  return 0;
 }
 
 int32_t gs_hermite_get_order(gs_hermite* h) { return h ? h->order : 0; }

@@ -30,13 +30,12 @@
 
 #include "gravsim.h"
 #include "gs_common.h"
+#include "gs_stepper.h"
 #include "gs_tile.h"
 
 #ifndef GS_KNN_EARLY
 #define GS_KNN_EARLY 1
 #endif
-
-void gs_set_error(const char* msg);
 
 namespace gs {
 
@@ -262,13 +261,13 @@ static void knn_launch(const KnnArgs& a, int32_t dtype, int32_t ipl, hipStream_t
 // What one call owns on the device; freed on every way out.
 struct KnnScratch {
   void *X = nullptr, *XL = nullptr, *LR = nullptr, *LI = nullptr, *R = nullptr, *I = nullptr;
+  rt::DevMem mem;  // (the six above)
   hipStream_t s = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   int prev = -1;
   ~KnnScratch() {
     if (s) (void)hipStreamSynchronize(s);
-    for (void* p : {X, XL, LR, LI, R, I})
-      if (p) (void)hipFree(p);
+    mem.release();
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (s) (void)hipStreamDestroy(s);
@@ -342,12 +341,13 @@ static int knn_run(const double* pos, int64_t n, int32_t dtype, int32_t k, int32
   GS_KNN_HIP(hipEventCreate(&d.e0));
   GS_KNN_HIP(hipEventCreate(&d.e1));
   const size_t rows = (size_t)a.n_pad * 4 * esz, lists = (size_t)a.groups * kKnnMax * a.n_pad;
-  GS_KNN_HIP(hipMalloc(&d.X, rows));
-  if (dtype == GS_MIXED) GS_KNN_HIP(hipMalloc(&d.XL, rows));
-  GS_KNN_HIP(hipMalloc(&d.LR, lists * esz));
-  GS_KNN_HIP(hipMalloc(&d.LI, lists * sizeof(int32_t)));
-  GS_KNN_HIP(hipMalloc(&d.R, (size_t)n * k * sizeof(double)));
-  GS_KNN_HIP(hipMalloc(&d.I, (size_t)n * k * sizeof(int32_t)));
+  if (d.mem.alloc(&d.X, rows, "knn X") ||
+      (dtype == GS_MIXED && d.mem.alloc(&d.XL, rows, "knn XL")) ||
+      d.mem.alloc(&d.LR, lists * esz, "knn LR") ||
+      d.mem.alloc(&d.LI, lists * sizeof(int32_t), "knn LI") ||
+      d.mem.alloc(&d.R, (size_t)n * k * sizeof(double), "knn R") ||
+      d.mem.alloc(&d.I, (size_t)n * k * sizeof(int32_t), "knn I"))
+    return -1;
   if (dtype == GS_FP64) {
     knn_rows<double>(pos, n, a.n_pad, false, Hd, Ld);
     GS_KNN_HIP(hipMemcpyAsync(d.X, Hd.data(), rows, hipMemcpyHostToDevice, d.s));

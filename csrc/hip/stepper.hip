@@ -242,21 +242,21 @@ int ensure_sym(gs_stepper* s) {
   if (band < rb) band = rb;
   if (band > rows) band = rows;
   s->sym_band = (int32_t)band;
-  if (dev_alloc(s, &s->sym_Pi, band * s->sym_S_n * 3 * gs::kSymC * e, "sym_Pi")) return -1;
-  if (dev_alloc(s, &s->sym_Pj, band * s->sym_H * 3 * gs::kSymC * e, "sym_Pj")) return -1;
-  if (dev_alloc(s, &s->sym_Pd, band * s->sym_D * 3 * gs::kSymC * e, "sym_Pd")) return -1;
+  if (s->mem.alloc(&s->sym_Pi, band * s->sym_S_n * 3 * gs::kSymC * e, "sym_Pi")) return -1;
+  if (s->mem.alloc(&s->sym_Pj, band * s->sym_H * 3 * gs::kSymC * e, "sym_Pj")) return -1;
+  if (s->mem.alloc(&s->sym_Pd, band * s->sym_D * 3 * gs::kSymC * e, "sym_Pd")) return -1;
   if (s->sym_Kr > 0 &&
-      dev_alloc(s, &s->sym_Px, band * s->sym_kx() * 3 * gs::kSymC * e, "sym_Px"))
+      s->mem.alloc(&s->sym_Px, band * s->sym_kx() * 3 * gs::kSymC * e, "sym_Px"))
     return -1;
-  if (dev_alloc(s, &s->sym_Ti, 3 * nl * e, "sym_Ti")) return -1;
+  if (s->mem.alloc(&s->sym_Ti, 3 * nl * e, "sym_Ti")) return -1;
   const size_t nb = (size_t)((s->L.n + gs::kSymC - 1) / gs::kSymC) * gs::kSymC;  // real chunks
-  if (band < rows && dev_alloc(s, &s->sym_Bb, rows / rb * 3 * nb * e, "sym_Bbuf")) return -1;
+  if (band < rows && s->mem.alloc(&s->sym_Bb, rows / rb * 3 * nb * e, "sym_Bbuf")) return -1;
   const int r = s->cfg.rank;
-  if (dev_alloc(s, &s->sym_S, (size_t)s->nn[r] * 3 * (size_t)s->L.n_pad * e, "sym_S")) return -1;
+  if (s->mem.alloc(&s->sym_S, (size_t)s->nn[r] * 3 * (size_t)s->L.n_pad * e, "sym_S")) return -1;
   // (zeroed once: the per-rank emulation never receives the other ranks' nodes)
   GS_HIP(hipMemsetAsync(s->sym_S, 0, (size_t)s->nn[r] * 3 * (size_t)s->L.n_pad * e, s->s_comp));
   if (P > 1) {
-    if (dev_alloc(s, &s->sym_R, (size_t)s->sym_NN * 3 * nl * e, "sym_R")) return -1;
+    if (s->mem.alloc(&s->sym_R, (size_t)s->sym_NN * 3 * nl * e, "sym_R")) return -1;
     GS_HIP(hipMemsetAsync(s->sym_R, 0, (size_t)s->sym_NN * 3 * nl * e, s->s_comp));
   } else {
     s->sym_R = s->sym_S;  // [node 0][3][n_pad] either way
@@ -270,7 +270,7 @@ int ensure_sym(gs_stepper* s) {
 // when the requested cutoff lies inside that core (the default 1e-10 m does).
 int ensure_partial(gs_stepper* s) {
   if (s->partial) return 0;
-  return dev_alloc(s, &s->partial, (size_t)s->L.n_chunks * s->L.n_local * row_bytes(s), "partial");
+  return s->mem.alloc(&s->partial, (size_t)s->L.n_chunks * s->L.n_local * row_bytes(s), "partial");
 }
 
 void resolve_force_mode(gs_stepper* s) {
@@ -800,7 +800,7 @@ int gs_stepper_create(const gs_config* cfg, gs_stepper** out) {
   } while (0)
 #define ALLOC_CLEAN(ptr, bytes, tag)     \
   do {                                   \
-    if (dev_alloc(s, ptr, bytes, tag)) { \
+    if (s->mem.alloc(ptr, bytes, tag)) { \
       gs_stepper_destroy(s);             \
       return -1;                         \
     }                                    \
@@ -946,8 +946,7 @@ int gs_stepper_destroy(gs_stepper* s) {
   drop_graphs(s);
   // (a communicator aborted by a watchdog, a timeout or an async error is not destroyed)
   if (s->have_comm && s->comm_live.exchange(nullptr)) (void)ncclCommDestroy(s->comm);
-  for (const auto& m : s->mem) (void)hipFree(m.p);
-  s->mem.clear();
+  s->mem.release();
   if (s->sync_fail) (void)hipHostFree(const_cast<unsigned*>(s->sync_fail));
   for (hipEvent_t e : {s->ev_ready, s->ev_gathered, s->ev_t0, s->ev_local, s->ev_end,
                        s->ev_remote, s->ev_fork, s->ev_rem2, s->ev_sym, s->ev_stage[0],
@@ -1155,11 +1154,12 @@ int32_t gs_stepper_get_dyn_cap(gs_stepper* s) { return s->dyn_cap; }
 
 int32_t gs_stepper_mem_entry(gs_stepper* s, int32_t i, const char** tag, uint64_t* bytes) {
   if (!s) return -1;
-  if (i >= 0 && i < (int32_t)s->mem.size()) {
-    if (tag) *tag = s->mem[i].tag;
-    if (bytes) *bytes = s->mem[i].bytes;
+  const auto& mem = s->mem.entries();
+  if (i >= 0 && i < (int32_t)mem.size()) {
+    if (tag) *tag = mem[i].tag;
+    if (bytes) *bytes = mem[i].bytes;
   }
-  return (int32_t)s->mem.size();
+  return (int32_t)mem.size();
 }
 
 int gs_stepper_graph_steps(gs_stepper* s) {

@@ -22,9 +22,22 @@
 
 #include "gravsim.h"
 #include "gs_common.h"
+#include "gs_devmem.h"
 #include "gs_kernels.h"
 
-void gs_set_error(const char* msg);
+namespace gs::rt {
+// The device memory behind every DevGroup of the runtime (gs_devmem.h).
+struct HipMem {
+  static const char* alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) (void)hipGetLastError();  // (cleared: the group reports it)
+    return e == hipSuccess ? nullptr : hipGetErrorString(e);
+  }
+  static void free(void* p) { (void)hipFree(p); }
+  static void mem_info(size_t* free_b, size_t* total_b) { (void)hipMemGetInfo(free_b, total_b); }
+};
+using DevMem = gs::DevGroup<HipMem>;
+}  // namespace gs::rt
 
 #define GS_HIP(call)                                                                \
   do {                                                                              \
@@ -227,13 +240,10 @@ struct gs_stepper {
   int pev_plan = 0;          // timed steps that ran from a replayed plan (phase_stats)
   // Device memory ledger: every HBM buffer the stepper owns, by name (gs_stepper_mem_entry);
   // destroy frees exactly these. All of them are allocated before the first step, sized from
-  // the layout (the sym bands from the free HBM), so nothing is allocated inside the loop.
-  struct MemEntry {
-    void* p;
-    size_t bytes;
-    const char* tag;
-  };
-  std::vector<MemEntry> mem;
+  // the layout (the sym bands from the free HBM), so nothing is allocated inside the loop. A
+  // failed mem.alloc names the buffer, its size and the free HBM (a 16M-body rank needs ~110 GB
+  // of partial slots).
+  gs::rt::DevMem mem;
   // Flag sync (fsync(): the multi-rank all-gather sym schedule): the cross-stream ordering
   // points are device counters with signal / wait kernels (comm_model.hip) instead of hipEvent
   // record / wait, so a replayed period is ONE compute graph plus the comm stream's eager ops,
@@ -272,27 +282,6 @@ enum : int { kMarkNone = 0, kMarkGather = 1, kMarkExchange = 2 };
 enum : int { kSyncReady = 0, kSyncStage0 = 1, kSyncStage1 = 2, kSyncExch = 3, kSyncCount = 4 };
 
 inline size_t row_bytes(const gs_stepper* s) { return 4 * s->esz; }
-
-// hipMalloc through the ledger; on failure the error names the buffer, its size and the
-// free HBM (a 16M-body rank needs ~110 GB of partial slots).
-template <typename T>
-inline int dev_alloc(gs_stepper* s, T** p, size_t bytes, const char* tag) {
-  void* v = nullptr;
-  const hipError_t e = hipMalloc(&v, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    size_t free_b = 0, total_b = 0;
-    (void)hipMemGetInfo(&free_b, &total_b);
-    char b[320];
-    snprintf(b, sizeof(b), "device allocation of %s (%.3f GB) failed: %s (free %.3f of %.3f GB)",
-             tag, bytes / 1e9, hipGetErrorString(e), free_b / 1e9, total_b / 1e9);
-    gs_set_error(b);
-    return -1;
-  }
-  *p = static_cast<T*>(v);
-  s->mem.push_back({v, bytes, tag});
-  return 0;
-}
 
 // A multi-rank exchange is active: a real communicator, or the per-rank emulation.
 inline bool xcomm(const gs_stepper* s) { return s->have_comm || s->emulate; }

@@ -234,6 +234,67 @@ def test_all_at_level_0_is_the_shared_step_bit_for_bit(hip, dtype):
         assert np.array_equal(x, y)
 
 
+def test_mode_toggles_reach_the_bits_of_a_fresh_engine(hip):
+    """The device buffers of a mode are built and dropped with the mode (gs_hermite's groups): an
+    engine brought to block steps with collisions through every toggle, off and on again, runs to
+    the bits of one created that way. n = 2049: two chunks, n_pad 4096. The narrow path's
+    neighbour and snap partials are re-derived at the switches of collisions, block mode, the
+    narrow slots and the order.
+    (Order 6 refuses collisions, so the switch to it with collisions on is refused and leaves the
+    engine as it was; it is then taken with collisions off, holds block steps of its own once, and
+    collisions go back on after order 4.)"""
+    n, K = 2049, 3
+    kw = dict(dt=DAY, max_level=6)  # (levels up to 6 in use, about 40 block steps a macro step)
+    rng = np.random.default_rng(11)
+    b = ic.solar_random(n, 7 + n)
+    b = BodySet(b.pos, b.vel, b.mass, np.abs(rng.normal(size=n)) * 1e8 * (rng.random(n) > 0.25))
+    A = _engine(n, "fp64", collisions="detect", **kw)
+    B = _engine(n, "fp64", block_steps=False, **kw)
+    try:
+        lib, h, L = B.lib, B._h, int(B.cfg.max_level)
+
+        def ok(rc):
+            assert rc == 0, lib.gs_last_error().decode()
+
+        ok(lib.gs_hermite_set_collisions(h, 1))
+        ok(lib.gs_hermite_set_block(h, 1, L))
+        ok(lib.gs_hermite_set_block_tuning(h, 0))
+        ok(lib.gs_hermite_set_block_tuning(h, n))
+        ok(lib.gs_hermite_set_collisions(h, 0))
+        ok(lib.gs_hermite_set_collisions(h, 1))
+        ok(lib.gs_hermite_set_block(h, 0, L))
+        assert lib.gs_hermite_set_order(h, 6) != 0 and lib.gs_hermite_get_order(h) == 4
+        assert b"order 6 has no collisions" in lib.gs_last_error()
+        ok(lib.gs_hermite_set_collisions(h, 0))
+        ok(lib.gs_hermite_set_order(h, 6))
+        assert lib.gs_hermite_get_order(h) == 6
+        ok(lib.gs_hermite_set_block6(h, 1, L))  # (the narrow slots with the snap partials)
+        ok(lib.gs_hermite_set_block_tuning(h, n))
+        ok(lib.gs_hermite_set_block6(h, 0, L))
+        ok(lib.gs_hermite_set_order(h, 4))
+        ok(lib.gs_hermite_set_collisions(h, 1))
+        ok(lib.gs_hermite_set_block(h, 1, L))
+        ok(lib.gs_hermite_set_block_tuning(h, n))
+        B.block = B.collisions = True  # (what load() and the reads of the Python engine ask)
+        A.set_block_tuning(n)
+        out = []
+        for eng in (A, B):
+            assert eng.status_narrow_max() == n  # (every active set takes the narrow path)
+            eng.load(b)
+            eng.step(K)
+            st, s = eng.status(), eng.state()
+            assert st.steps == K and st.time == K * DAY and st.block_steps > K
+            out.append((s.pos, s.vel, *eng.carried(), eng.levels(), eng.body_times(),
+                        *eng.neighbours(), *eng.closest(),
+                        np.array([st.block_steps, st.body_steps, st.level_max, st.overlaps])))
+        assert out[0][4].any() and (out[0][7] >= 0).all()  # (levels in use, neighbours found)
+        for x, y in zip(*out):
+            assert x.tobytes() == y.tobytes()
+    finally:
+        A.close()
+        B.close()
+
+
 @functools.lru_cache(maxsize=None)
 def _oracle_run(n, days=32):
     b = ic.plummer(n, seed=PLUMMER[n])
